@@ -6,10 +6,19 @@ HBM-resident synthetic relations with the reference generator's key multiset
 (src/generator.c:304-415): |R| = 128M, |S| = 1024M, q = 0.01, -b blocked, m = 2^30, k = 1,
 B = 1024 (the reference default, src/main.c:393). value = probe tuples (|S|) per second over the
 whole job. The K timed joins are enqueued back to back (hwbrj_join_device_async) and waited for
-once, as a pipeline of joins runs; the phase breakdown comes from K synchronous joins afterwards.
+once, as a pipeline of joins runs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
+
+A plain run does what the headline needs and no more: it generates the relations, runs one untimed
+join for the counts, warms up, times the K joins and prints the line. --dump-outputs DIR writes
+what the last timed join returned to its caller (its filtered and matches counts) as
+DIR/counts.npy (float64; DIR/counts_rank<r>.npy at N > 1); the relations are seeded, so two
+builds run with the same arguments can be compared output for output. --full adds every other
+measurement, each in runs of its own after the timed region: the phase breakdown (K synchronous
+joins), the dominant kernel in the async schedule, the measured copy rate, the PCIe-inclusive time,
+the CPU baseline, and at N > 1 the other multi-GPU designs (alt_designs).
 
 N > 1: one rank per GPU (RCCL backend). Strong scaling by default (BASELINE config 4): one
 |S| = 1024M range-sharded over the ranks (the reference's per-thread chunking of S,
@@ -18,8 +27,9 @@ copy of R, so the data path has no collective; value = |S| / the slowest rank's 
 per-rank counts summed over the ranks must equal the golden. --scaling weak (every rank its own
 full |S|) is an A/B option, never the default. Counts are reduced after the timed region.
 
-Prints ONE JSON line (rank 0) with roofline (dominant kernel, HIP-event timed) and cpu_baseline
-(the oracle's multithreaded restatement of the reference, "port", on a bounded sample).
+Prints ONE JSON line (rank 0) with the roofline of the timed joins; with --full also the dominant
+kernel (HIP-event timed) and cpu_baseline (the oracle's multithreaded restatement of the reference,
+"port", on a bounded sample).
 """
 from __future__ import annotations
 
@@ -45,6 +55,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed join's outputs (its filtered and matches counts) to "
+                         "DIR/counts.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the phase breakdown, the dominant kernel, "
+                         "the copy rate, the end-to-end time, the CPU baseline and (N > 1) the other "
+                         "multi-GPU designs; a plain run reports null for them")
     ap.add_argument("-r", "--r-size", type=int, default=128000000)
     ap.add_argument("-s", "--s-size", type=int, default=1024000000)
     ap.add_argument("-q", "--s-sel", type=float, default=0.01)
@@ -70,14 +87,14 @@ def parse():
                     help="replicated design: rank 0 builds the filter, ncclBroadcast sends it to "
                          "every rank (the north_star's bitmap broadcast) instead of a rebuild per rank")
     ap.add_argument("--no-alt-designs", action="store_true",
-                    help="N > 1 (or any process group): skip the extra legs that time the other "
+                    help="--full at N > 1 (or any process group): skip the extra legs that time the other "
                          "multi-GPU designs on the same ranks after the headline (alt_designs)")
     ap.add_argument("--alt-steps", type=int, default=5, help="timed joins per alt_designs leg")
     ap.add_argument("--alt-timeout", type=float, default=150.0,
                     help="seconds the alt_designs legs may take before the headline is printed without "
                          "the rest and every rank exits (a collective that never completes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive end-to-end time")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the PCIe-inclusive end-to-end time")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="S tuples in the CPU baseline run (0: the full |S|, the same workload)")
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -251,7 +268,51 @@ def main():
         dist.all_reduce(timed_ok)
     timed_ok = [int(x) for x in timed_ok.tolist()]
     last = timed[-1] if timed else hw.join_wait()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last, rank, world)
 
+    sums, async_sc = {}, []
+    if a.full:
+        sums, async_sc = phase_runs(a, hw, dR, dS, args, stream, ref)
+    if dist:
+        t = torch.tensor([elapsed, dev_ms], dtype=torch.float64, device=cdev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed, dev_ms = (float(x) for x in t.tolist())
+    out = headline_line(a, hw, torch, dist, rank, world, dR, dS, args, st, last, sums, elapsed, dev_ms,
+                        total_units, filtered, matches, ranks_agree, per_rank, shared, async_sc) if rank == 0 else None
+    if out is not None:
+        out["parity"]["timed_joins_ok"] = f"{timed_ok[0]}/{timed_ok[1]}"
+        out["parity"]["timed_joins_what"] = ("every timed join's own (filtered, matches) equal to the parity "
+                                             "run's (hwbrj_join_wait_all), summed over the ranks")
+    # the other multi-GPU designs on the same ranks, after the headline (never its value); every
+    # leg runs under its own watchdog: a leg that has not finished in --alt-timeout seconds (a
+    # collective that never completes) makes rank 0 print the headline with the legs reported so far
+    # and the stalled leg named, and every rank exit with status 124 (a timeout is not a clean run)
+    alt = None
+    if a.full and dist and not a.no_alt_designs and not a.filter_bcast:
+        alt = {}
+        alt_designs(a, hw, torch, dist, rank, world, local, dR, dS, args, shared, alt, out)
+    if rank == 0:
+        out["alt_designs"] = alt
+        print(json.dumps(out), flush=True)
+    if dist:
+        dist.destroy_process_group()
+
+
+def dump_outputs(path: str, st, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: what the last timed join handed back to its caller, its (filtered, matches)
+    counts (the join counts its results, as the reference's default build does), as a float64
+    array of two in path/counts.npy (every rank its own path/counts_rank<r>.npy at N > 1)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    name = "counts.npy" if world == 1 else f"counts_rank{rank}.npy"
+    np.save(os.path.join(path, name), np.array([st.filtered, st.matches], dtype=np.float64))
+
+
+def phase_runs(a, hw, dR, dS, args, stream, ref):
+    """--full: (sums, async_sc) from runs of their own after the timed region. sums: per-phase
+    device times (HIP events) summed over K synchronous joins; async_sc: the S scatter's ms in each
+    of K more async joins."""
     # per-phase device times (HIP events, one synchronous join each, after the timed region)
     sums = {}
     for _ in range(a.steps):
@@ -271,35 +332,39 @@ def main():
         hw.set_async_timing(False)
     if any((s.filtered, s.matches) != ref for s in tj):
         raise SystemExit("the async-timed joins differ from the parity run")
-    async_sc = [s.ms_s_scatter for s in tj if s.ms_s_scatter > 0]
-    if dist:
-        t = torch.tensor([elapsed, dev_ms], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, dev_ms = (float(x) for x in t.tolist())
-    out = headline_line(a, hw, torch, dist, rank, world, dR, dS, args, st, last, sums, elapsed, dev_ms,
-                        total_units, filtered, matches, ranks_agree, per_rank, shared, async_sc) if rank == 0 else None
-    if out is not None:
-        out["parity"]["timed_joins_ok"] = f"{timed_ok[0]}/{timed_ok[1]}"
-        out["parity"]["timed_joins_what"] = ("every timed join's own (filtered, matches) equal to the parity "
-                                             "run's (hwbrj_join_wait_all), summed over the ranks")
-    # the other multi-GPU designs on the same ranks, after the headline (never its value); every
-    # leg runs under its own watchdog: a leg that has not finished in --alt-timeout seconds (a
-    # collective that never completes) makes rank 0 print the headline with the legs reported so far
-    # and the stalled leg named, and every rank exit with status 124 (a timeout is not a clean run)
-    alt = None
-    if dist and not a.no_alt_designs and not a.filter_bcast:
-        alt = {}
-        alt_designs(a, hw, torch, dist, rank, world, local, dR, dS, args, shared, alt, out)
-    if rank == 0:
-        out["alt_designs"] = alt
-        print(json.dumps(out), flush=True)
-    if dist:
-        dist.destroy_process_group()
+    return sums, [s.ms_s_scatter for s in tj if s.ms_s_scatter > 0]
+
+
+def dominant_kernel(nR, nS, mean, async_sc, pm):
+    """--full: the phase with the largest mean time against its own s8(d) bytes."""
+    # the dominant kernel against its own s8(d) bytes: k_scatter_s reads every S tuple once (8 B)
+    dom = max(("r_scatter", "build", "s_scatter", "probe", "join"), key=lambda p: mean["ms_" + p])
+    dom_alg = {"r_scatter": 8.0 * nR, "s_scatter": 8.0 * nS}.get(dom)
+    dom_ms_sync = mean["ms_" + dom]
+    # its ms in the timed joins' own schedule (S scatter on the side stream beside the R side; the
+    # frac below uses it), the one-stream synchronous joins' phase time beside it
+    use_async = dom == "s_scatter" and len(async_sc) > 0
+    dom_ms = statistics.median(async_sc) if use_async else dom_ms_sync  # (median: one slow join of K moves a mean)
+    return {
+        "name": {"s_scatter": "k_scatter_s", "r_scatter": "k_scatter_r",
+                 "probe": "k_probe", "build": "k_build", "join": "k_join"}[dom],
+        "ms": round(dom_ms, 4), "algorithmic_bytes": dom_alg,
+        "schedule": ("async two-stream joins (the timed schedule): S scatter events on its side "
+                     f"stream, median of {len(async_sc)} back-to-back joins" if use_async else
+                     "synchronous one-stream joins (phase events)"),
+        "ms_async_min_max": [round(min(async_sc), 4), round(max(async_sc), 4)] if use_async else None,
+        "ms_async_mean": round(statistics.mean(async_sc), 4) if use_async else None,
+        "ms_sync_phase": round(dom_ms_sync, 4),
+        "achieved": round(dom_alg / (dom_ms * 1e-3) / 1e9, 1) if dom_alg else None,
+        "frac": round(dom_alg / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dom_alg else None,
+        "traffic": pm["phases"].get(dom, {}).get("hbm_bytes") if pm else None}
 
 
 def headline_line(a, hw, torch, dist, rank, world, dR, dS, args, st, last, sums, elapsed, dev_ms, total_units,
                   filtered, matches, ranks_agree, per_rank, shared, async_sc=()):
-    """Rank 0's bench line of the replicated design (its alt_designs are filled in by the caller)."""
+    """Rank 0's bench line of the replicated design (its alt_designs are filled in by the caller).
+    What --full measures (phase_ms, roofline.dominant_kernel and copy_measured, cpu_baseline, e2e) is
+    null in a plain run."""
     nR, nS_total = a.r_size, a.s_size
     nS = dS.shape[0]
     K = max(a.steps, 1)
@@ -313,14 +378,6 @@ def headline_line(a, hw, torch, dist, rank, world, dR, dS, args, st, last, sums,
     pm, pmc_note = load_pmc(a.pmc_json, [nR, nS, a.s_sel, a.bloom_filter, a.bloom_size, a.bloom_hashes,
                                          a.bloom_block_size], hw.version()) if world == 1 else (None, "N > 1")
     traffic = sum(p.get("hbm_bytes", 0) for p in pm["phases"].values()) if pm else None
-    # the dominant kernel against its own s8(d) bytes: k_scatter_s reads every S tuple once (8 B)
-    dom = max(("r_scatter", "build", "s_scatter", "probe", "join"), key=lambda p: mean["ms_" + p])
-    dom_alg = {"r_scatter": 8.0 * nR, "s_scatter": 8.0 * nS}.get(dom)
-    dom_ms_sync = mean["ms_" + dom]
-    # its ms in the timed joins' own schedule (S scatter on the side stream beside the R side; the
-    # frac below uses it), the one-stream synchronous joins' phase time beside it
-    use_async = dom == "s_scatter" and len(async_sc) > 0
-    dom_ms = statistics.median(async_sc) if use_async else dom_ms_sync  # (median: one slow join of K moves a mean)
     word_bytes = 4.0  # S partition words (4 bytes in every format)
     roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": peak, "unit": "GB/s",
                 "frac": round(achieved / peak, 4), "traffic": traffic,
@@ -335,31 +392,19 @@ def headline_line(a, hw, torch, dist, rank, world, dR, dS, args, st, last, sums,
                 "pmc_source": os.path.relpath(a.pmc_json, ROOT) if pm else None,
                 "pmc_library": pm.get("library") if pm else None,
                 "traffic_note": pmc_note,
-                "dominant_kernel": {
-                    "name": {"s_scatter": "k_scatter_s", "r_scatter": "k_scatter_r",
-                             "probe": "k_probe", "build": "k_build", "join": "k_join"}[dom],
-                    "ms": round(dom_ms, 4), "algorithmic_bytes": dom_alg,
-                    "schedule": ("async two-stream joins (the timed schedule): S scatter events on its side "
-                                 f"stream, median of {len(async_sc)} back-to-back joins" if use_async else
-                                 "synchronous one-stream joins (phase events)"),
-                    "ms_async_min_max": [round(min(async_sc), 4), round(max(async_sc), 4)] if use_async else None,
-                    "ms_async_mean": round(statistics.mean(async_sc), 4) if use_async else None,
-                    "ms_sync_phase": round(dom_ms_sync, 4),
-                    "achieved": round(dom_alg / (dom_ms * 1e-3) / 1e9, 1) if dom_alg else None,
-                    "frac": round(dom_alg / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if dom_alg else None,
-                    "traffic": pm["phases"].get(dom, {}).get("hbm_bytes") if pm else None}}
+                "dominant_kernel": dominant_kernel(nR, nS, mean, async_sc, pm) if mean else None}
 
-    if world == 1:  # the measured copy rate beside the spec peak (not the frac's denominator)
+    if world == 1 and a.full:  # the measured copy rate beside the spec peak (not the frac's denominator)
         cbw = round(hw.copy_bandwidth(4 << 30, 5), 1)
         roofline["copy_measured"] = {"GBps": cbw, "frac_of_copy": round(achieved / cbw, 4),
                                      "what": "hwbrj_copy_bandwidth: streaming 16-byte nt copy of 4 GiB, "
                                              "(read + write) bytes / median time of 5; the spec peak "
                                              "stays the denominator"}
     cpu = None
-    if world == 1 and not a.no_cpu_baseline:
+    if world == 1 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a, hw)
     e2e = None
-    if world == 1 and not a.no_e2e:
+    if world == 1 and a.full and not a.no_e2e:
         e2e = e2e_time(hw, torch, dR, dS, args, nS)
 
     key = (nR, nS_total, a.s_sel, a.bloom_filter, a.bloom_size, a.bloom_hashes, a.bloom_block_size)
@@ -401,7 +446,7 @@ def headline_line(a, hw, torch, dist, rank, world, dR, dS, args, st, last, sums,
         "dist": {"world_size_seen": dist.get_world_size() if dist else 1,
                  "backend": dist.get_backend() if dist else None,
                  "shared_gpu_rehearsal": shared},
-        "phase_ms": {k[3:]: round(v, 4) for k, v in mean.items()},
+        "phase_ms": {k[3:]: round(v, 4) for k, v in mean.items()} if mean else None,
         "alt_designs": None,
         "published_ref": {"value": 3.98e8, "config": "blocked B=512 k=1 m=2^30, 2x Xeon Gold 6226 "
                           "48 threads (thesis data, BASELINE.md)"},
@@ -627,6 +672,8 @@ def run_partitioned(a, hw, torch, dist, rank, world, local, dR, dS, args, shared
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and a.steps > 0:
+        dump_outputs(a.dump_outputs, sts[-1] if use_async else st, rank, world)
     if use_async:
         info1 = pjoin.pj_async_info()
         async_rep = {"plan_blocks": {"BR_chunks": info1["BR"], "BI_items": info1["BI"], "BW_words": info1["BW"]},

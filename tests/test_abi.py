@@ -219,6 +219,23 @@ def test_bench_modeled_join_key_bytes():
     assert mb["join_codes_R"] == 60.0 and mb["survivors"] == 30.0
 
 
+def test_bench_dump_outputs_writes_the_counts(tmp_path):
+    """bench.py --dump-outputs: the last timed join's (filtered, matches) as a float64 array of two,
+    counts.npy on one GPU and counts_rank<r>.npy per rank at N > 1 (the directory is created)."""
+    import importlib.util
+    from types import SimpleNamespace as NS
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    st = NS(filtered=124236515, matches=10240000)
+    bench.dump_outputs(str(tmp_path / "new" / "dir"), st)
+    bench.dump_outputs(str(tmp_path / "new" / "dir"), st, rank=3, world=4)
+    assert sorted(os.listdir(tmp_path / "new" / "dir")) == ["counts.npy", "counts_rank3.npy"]
+    for name in ("counts.npy", "counts_rank3.npy"):
+        c = np.load(tmp_path / "new" / "dir" / name)
+        assert c.dtype == np.float64 and c.tolist() == [124236515.0, 10240000.0]
+
+
 def test_write_result_relation_reference_order(hw, tmp_path):
     """hwbrj_write_result_relation emits the pairs in write_result_relation's order
     (src/tuple_buffer.h:205-231): per thread, the newest chained buffer first, every buffer from its

@@ -432,7 +432,7 @@ def test_bench_alt_watchdog_world1(hw):
     partitioned_async (the first leg) reported with the F3 counts, bcast named as the timed-out leg,
     partitioned as not run, and the run exits non-zero (status 124 on the rank)."""
     g = GOLD["F3_grid"]
-    rc, out, err = torchrun(1, ["-r", g["r"], "-s", g["s"], "-m", g["m"], "--alt-timeout", "30"],
+    rc, out, err = torchrun(1, ["-r", g["r"], "-s", g["s"], "-m", g["m"], "--full", "--alt-timeout", "30"],
                             {"HWBRJ_BENCH_DIST": "1", "HWBRJ_BENCH_HOOK_STALL_LEG": "bcast"})
     assert rc not in (0, None), out[-2000:] + err[-3000:]
     line = last_json(out)

@@ -381,7 +381,7 @@ def test_bench_two_ranks(hw):
     out = subprocess.run(["python", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "-r", str(g["r"]), "-s", str(g["s"]), "-m", str(g["m"])],
+                          "--full", "-r", str(g["r"]), "-s", str(g["s"]), "-m", str(g["m"])],
                          capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
@@ -414,7 +414,7 @@ def test_bench_rccl_process_group(hw):
     out = subprocess.run(["python", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port),
                           os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "-r", str(g["r"]), "-s", str(g["s"]), "-m", str(g["m"]), "--no-cpu-baseline"],
+                          "--full", "-r", str(g["r"]), "-s", str(g["s"]), "-m", str(g["m"]), "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
@@ -426,6 +426,30 @@ def test_bench_rccl_process_group(hw):
         leg = line["alt_designs"][name]
         assert leg.get("sum") == [g["rows"]["1024"][0], g["results"]] and leg["ms"] > 0, (name, leg)
         assert leg["per_rank"] == [leg["sum"]]
+
+
+def test_bench_plain_run_dumps_counts(hw, tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps joins, leaves every --full measurement
+    null, and --dump-outputs writes the last timed join's (filtered, matches) as float64: the F3
+    golden counts (the relations are seeded, so every run with these arguments joins the same input)."""
+    g = GOLD["F3_grid"]
+    root = os.path.dirname(HERE)
+    want = [g["rows"]["1024"][0], g["results"]]
+    out = subprocess.run(["python", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "-r", str(g["r"]), "-s", str(g["s"]), "-m", str(g["m"]),
+                          "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 3 and line["parity"]["timed_joins_ok"] == "3/3"
+    assert line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "probe-tuples/s"
+    assert [line["parity"]["filtered"], line["parity"]["matches"]] == want
+    for moved in ("phase_ms", "cpu_baseline", "e2e", "alt_designs"):
+        assert line[moved] is None, (moved, line[moved])
+    assert line["roofline"]["dominant_kernel"] is None and "copy_measured" not in line["roofline"]
+    assert os.listdir(tmp_path / "dump") == ["counts.npy"]
+    c = np.load(tmp_path / "dump" / "counts.npy")
+    assert c.dtype == np.float64 and c.tolist() == want
 
 
 def _sorted_pairs(p):

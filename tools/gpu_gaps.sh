@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$1
 shift
 mkdir -p $OUT
-B="bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e"
+B="bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-e2e"
 timeout -k 10 240 python3 $B > $OUT/bench.log 2>&1 || { echo BENCH_FAIL; tail -5 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('A', d['ms_per_step'], d['phase_ms'])"
 if [ $# -gt 0 ]; then
