@@ -28,20 +28,15 @@ extern "C" {
 
 const char* hwbrj_last_error(void) { return g_last_error.c_str(); }
 // "<name> <version> (gfx950) src <hash>", then " knobs: ..." naming every compile-time switch of
-// the kernels and every dev environment knob (dev builds only) that differs from the product
-// default. The hash is the Makefile's stamp of the product sources and flags ("dev" otherwise).
+// the kernels that differs from the product default. The hash is the Makefile's stamp of the
+// product sources and flags ("dev" otherwise).
 #ifndef HWBRJ_SRC_SHA
 #define HWBRJ_SRC_SHA "dev"
 #endif
 // Test hooks that are set (hwbrj_set_test_hook) are named too, so a bench line or a PMC stamp of a
 // process that set one shows it.
 const char* hwbrj_version(void) {
-    static const std::string base = [] {
-        std::string k = kernel_build_knobs();
-        const std::string d = dev_knobs_string();
-        if (!d.empty()) k += (k.empty() ? "" : " ") + d;
-        return k;
-    }();
+    static const std::string base = kernel_build_knobs();
     // one immutable string per distinct hook state, never freed: a pointer returned earlier stays
     // valid whatever hooks are set later
     static std::mutex            mu;

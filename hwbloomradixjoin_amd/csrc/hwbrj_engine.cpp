@@ -168,7 +168,6 @@ bool plan_geometry(const bloom_filter_args_t* a, uint64_t nR, Geometry* g, std::
             if (B >= 8 && m >= 32 && (m / B) <= 0xFFFFFFFFull) {
                 g->mode = MODE_SLICE_BLOCK;
                 F       = std::min<uint64_t>(std::min<uint64_t>(1024, m / B), m / 32);
-                if (dev_knobs().maxf) F = std::min<uint64_t>(F, dev_knobs().maxf);  // dev A/B
             } else {
                 g->mode = MODE_GLOBAL;
             }
@@ -207,8 +206,6 @@ bool plan_geometry(const bloom_filter_args_t* a, uint64_t nR, Geometry* g, std::
         while (l2s < 6 && (rper >> l2s) > 1536) l2s++;
     } else if (g->sub_shift > 0 && g->log2F + 6 >= 14) {
         l2s = g->log2F >= 14 ? 0 : 14 - g->log2F;
-        if (dev_knobs().l2sub && g->log2F + dev_knobs().l2sub >= 14)  // dev A/B: more, smaller jobs
-            l2s = std::min<uint32_t>(6, dev_knobs().l2sub);
     } else {
         while (l2s < 6 && (rper >> l2s) > 4096) l2s++;
     }
@@ -238,55 +235,44 @@ void DevBuf::release() {
     bytes = 0;
 }
 
-// ------------------------------------------------------------- dev knobs and test hooks
-const DevKnobs& dev_knobs() {
-    static const DevKnobs k = [] {
-        DevKnobs d;
-#ifdef HWBRJ_DEV_BUILD
-        auto u = [](const char* n) -> uint32_t {
-            const char* e = getenv(n);
-            return e ? (uint32_t) strtoul(e, nullptr, 0) : 0u;
-        };
-        d.kk1       = getenv("HWBRJ_DEV_KK1") != nullptr;
-        d.kk_gather = getenv("HWBRJ_DEV_KK_GATHER") != nullptr;
-        d.noxcd     = getenv("HWBRJ_DEV_NOXCD") != nullptr;
-        d.dbg       = getenv("HWBRJ_DBG") != nullptr;
-        d.maxf      = u("HWBRJ_DEV_MAXF");
-        d.scwpc     = u("HWBRJ_DEV_SCWPC");
-        if (getenv("HWBRJ_DEV_EVFLAGS")) d.evflags = (int) u("HWBRJ_DEV_EVFLAGS");
-        d.l2sub     = u("HWBRJ_DEV_L2SUB");
-        d.ovl       = getenv("HWBRJ_DEV_OVL") != nullptr;
-        d.rfirst    = getenv("HWBRJ_DEV_RFIRST") != nullptr;
-#endif
-        return d;
-    }();
-    return k;
+bool PartSide::ensure(uint64_t chunks, uint32_t G, uint32_t F) {
+    const uint64_t GF = (uint64_t) G * F;
+    return pool.ensure(chunks * 128) && meta.ensure(chunks * 2) && list.ensure(chunks * 4) &&
+           used.ensure(G * 4) && wgqc.ensure(GF * 4) && wgqe.ensure(GF * 4) && wgqo.ensure(GF * 4) &&
+           lstart.ensure((F + 1) * 4) && estart.ensure((F + 1) * 8) && istart.ensure((F + 1) * 4) &&
+           col.ensure(F * 12);
 }
 
-std::string dev_knobs_string() {
-    const DevKnobs& d = dev_knobs();
-    std::string     r;
-    auto add = [&](const std::string& w) { r += (r.empty() ? "" : " ") + w; };
-    if (d.kk1) add("HWBRJ_DEV_KK1");
-    if (d.kk_gather) add("HWBRJ_DEV_KK_GATHER");
-    if (d.noxcd) add("HWBRJ_DEV_NOXCD");
-    if (d.dbg) add("HWBRJ_DBG");
-    if (d.maxf) add("HWBRJ_DEV_MAXF=" + std::to_string(d.maxf));
-    if (d.scwpc) add("HWBRJ_DEV_SCWPC=" + std::to_string(d.scwpc));
-    if (d.evflags >= 0) add("HWBRJ_DEV_EVFLAGS=" + std::to_string(d.evflags));
-    if (d.l2sub) add("HWBRJ_DEV_L2SUB=" + std::to_string(d.l2sub));
-    if (d.ovl) add("HWBRJ_DEV_OVL");
-    if (d.rfirst) add("HWBRJ_DEV_RFIRST");
-    return r;
+void PartSide::release() {
+    for (DevBuf* b : {&pool, &meta, &used, &wgqc, &wgqe, &wgqo, &lstart, &estart, &istart, &list, &col}) b->release();
 }
 
+void PartSide::bind(ScatterParams* sp, uint64_t cap) const {
+    sp->pool       = pool.as<uint32_t>();
+    sp->meta       = meta.as<uint32_t>();
+    sp->wg_used    = used.as<uint32_t>();
+    sp->wgq_chunks = wgqc.as<uint32_t>();
+    sp->wgq_elems  = wgqe.as<uint32_t>();
+    sp->cap        = cap;
+}
+
+void index_side(const PartSide& s, uint64_t cap, uint32_t log2F, uint32_t per_item, uint32_t nseg,
+                uint32_t G, hipStream_t st) {
+    uint32_t* colc = s.col.as<uint32_t>() + 2 * (1u << log2F);  // (behind the u64 element totals)
+    launch_plan(s.wgqc.as<uint32_t>(), s.wgqe.as<uint32_t>(), G, log2F, s.wgqo.as<uint32_t>(), colc,
+                s.col.as<uint64_t>(), st);
+    launch_list_fill(s.meta.as<uint32_t>(), s.used.as<uint32_t>(), cap, log2F, s.wgqo.as<uint32_t>(), colc,
+                     s.col.as<uint64_t>(), per_item, nseg, s.lstart.as<uint32_t>(), s.estart.as<uint64_t>(),
+                     s.istart.as<uint32_t>(), s.list.as<uint32_t>(), G, st);
+}
+
+// ---------------------------------------------------------------------------- test hooks
 TestHooks& test_hooks() {
     static TestHooks h;
     return h;
 }
 
 Engine::Engine(int device) : device_(device) {
-    (void) dev_knobs();  // the dev environment is read once, here (dev builds only)
     (void) hipSetDevice(device);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) cus_ = prop.multiProcessorCount;
@@ -294,9 +280,8 @@ Engine::Engine(int device) : device_(device) {
     // ev_[0..7] only time phases (elapsed-time reads after ev_[8] has completed): no system-scope
     // fence on record, whose cache writeback idled the GPU ~6 us per marker. ev_[8] (waited on,
     // and ordering later joins) and ev_[9] keep the default release.
-    const unsigned evf = dev_knobs().evflags >= 0 ? (unsigned) dev_knobs().evflags : hipEventDisableSystemFence;
     for (int i = 0; i < 10; i++)
-        (void) (i < 8 ? hipEventCreateWithFlags(&ev_[i], evf) : hipEventCreate(&ev_[i]));
+        (void) (i < 8 ? hipEventCreateWithFlags(&ev_[i], hipEventDisableSystemFence) : hipEventCreate(&ev_[i]));
     CrcTables t;
     if (!build_crc_tables(&t)) set_last_error("CRC table inversion failed");
     (void) hipMalloc((void**) &d_tabs_, sizeof(CrcTables));
@@ -311,10 +296,10 @@ void Engine::release() {
     pj_q_.clear();                       // (joins in flight are dropped)
     if (pj_plan_.valid) pj_lost_ = true;  // (the next async join runs in the failed mode: a new plan)
     for (DevBuf* b : {&pjX, &pjRitems, &pjRing}) b->release();
-    for (DevBuf* b : {&poolR, &metaR, &usedR, &wgqcR, &wgqeR, &wgqoR, &lstartR, &estartR, &istartR,
-                      &listR, &poolS, &metaS, &usedS, &wgqcS, &wgqeS, &wgqoS, &lstartS, &estartS,
-                      &istartS, &listS, &slices, &bitmap, &rjoin, &rrun, &surv, &survcnt, &survoff,
-                      &dense, &small, &bpos, &colR, &colS, &mtab, &mcount, &jtask, &jparts, &pjList,
+    R_.release();
+    S_.release();
+    for (DevBuf* b : {&slices, &bitmap, &rjoin, &rrun, &surv, &survcnt, &survoff,
+                      &dense, &small, &bpos, &mtab, &mcount, &jtask, &jparts, &pjList,
                       &pjLstart, &pjSweep, &pjTab, &pjRegion, &pjTot, &pjSoff, &pjIbase, &pjCnt, &pjOff,
                       &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
         b->release();
@@ -328,7 +313,7 @@ void Engine::release() {
 // One join's result slot: 128 bytes of result words (read_join_counts), then k_join's partial sums
 static size_t ring_slot_bytes() { return 128 + join_sum_slots() * join_sum_stride() * 8; }
 
-static uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
+uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
     const uint64_t units = (n + 3) / 4;
     const uint64_t per   = ((units + G - 1) / G) * 4;
     return (per + 31) / 32 + F + 1;
@@ -336,7 +321,7 @@ static uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
 
 int Engine::run(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                 const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, dev_knobs().dbg, jkind);
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind);
     return rc ? rc : wait(st);
 }
 
@@ -345,7 +330,7 @@ int Engine::run_async(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS
     // back-to-back joins: no phase events (each marker idles the GPU ~6 us between the kernels
     // around it, profiles/r03/gaps_*), so hwbrj_join_wait reports counts only
     phase_ev_    = false;
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, false, jkind);
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind);
     phase_ev_    = true;
     return rc;
 }
@@ -360,7 +345,7 @@ hipError_t Engine::mark(int i, hipStream_t stream) {
 int Engine::reserve(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                     const bloom_filter_args_t* args, int jkind) {
     alloc_only_  = true;
-    const int rc = enqueue(dR, nR, dS, nS, args, nullptr, false, jkind);
+    const int rc = enqueue(dR, nR, dS, nS, args, nullptr, jkind);
     alloc_only_  = false;
     last_nj_     = 0;  // buffers may be new: the next join clears its job table
     return rc;
@@ -369,12 +354,12 @@ int Engine::reserve(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
 int Engine::run_mat(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
                     hwbrj_stats_t* st) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, false, 0, &mat);
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, &mat);
     return rc ? rc : wait(st);
 }
 
 int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                    const bloom_filter_args_t* args, hipStream_t stream, bool dbg, int jkind,
+                    const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                     const MatReq* mat) {
     if (jkind < 0 || jkind > 2) {
         set_last_error("unknown per-partition join algorithm");
@@ -391,9 +376,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         set_last_error("global-bitmap mode: materialized by the side pass");
         return kRcMatGlobal;
     }
-    const bool kk1 = dev_knobs().kk1;  // dev A/B: basic k = 1 on the bit-pass path
-    if (!mat && g.mode == MODE_SLICE_BASIC && (g.k > 1 || kk1) && (uint64_t) g.k * nR <= (1ull << 31) &&
-        !dev_knobs().kk_gather) {
+    if (!mat && g.mode == MODE_SLICE_BASIC && g.k > 1 && (uint64_t) g.k * nR <= (1ull << 31)) {
         if (!stream) stream = own_stream_;
         if (pending_ && stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(stream, ev_[8], 0));
         return enqueue_basic_kk(dR, nR, dS, nS, g, stream, jkind);
@@ -408,10 +391,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     const uint32_t nseg       = slice_mode ? g.nseg : 1;
     const uint32_t CH         = probe_chunks_per_item();  // chunks per probe item
     const size_t   sc_lds     = mat ? scatter_pay_lds_bytes(g.log2F) : scatter_lds_bytes(g.log2F);
-    uint32_t       sc_wpc     = (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / sc_lds));
-    if (dev_knobs().scwpc)  // dev A/B: scatter workgroups per CU
-        sc_wpc = std::max(1u, std::min(sc_wpc, dev_knobs().scwpc));
-    const uint32_t G          = (uint32_t) cus_ * sc_wpc;
+    const uint32_t G          = (uint32_t) cus_ * wg_per_cu(sc_lds);
     // basic k >= 2: the S-side buffers first partition the R keys' k * |R| bit positions
     const bool     basic_kk = g.mode == MODE_SLICE_BASIC && g.k > 1;
     const uint64_t nRk      = basic_kk ? (uint64_t) g.k * nR : 0;
@@ -427,12 +407,11 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     const uint64_t capR = region_cap(nR, G, F), capS = region_cap(std::max(nS, nRk), G, F);
     const uint64_t LR = (uint64_t) G * capR, LS = (uint64_t) G * capS;  // max chunks
     const uint64_t items_max = (LS / CH + F + 1) * nseg;
-    // list entries hold a 27-bit chunk id (hwbrj_kernels.hip, K4); metas a 22-bit region offset
     if (G > 512) {
         set_last_error("more than 512 scatter workgroups (k_plan row groups)");
         return pre(3);
     }
-    if (LS > (1ull << 27) || LR > (1ull << 27) || capS >= (1u << 22) || capR >= (1u << 22)) {
+    if (!part_fits(G, capR, capS)) {
         set_last_error("relation too large for 27-bit chunk ids (|S| or |R| > ~4.2e9 tuples per GPU)");
         return pre(3);
     }
@@ -440,20 +419,13 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         set_last_error("relation too large for the materializing scatter's 22-bit half indices");
         return pre(3);
     }
-    const uint64_t GF = (uint64_t) G * F;
-    bool ok = true;
-    ok &= poolR.ensure(LR * 128) && metaR.ensure(LR * 2) && listR.ensure(LR * 4);
-    ok &= usedR.ensure(G * 4) && wgqcR.ensure(GF * 4) && wgqeR.ensure(GF * 4) && wgqoR.ensure(GF * 4);
-    ok &= lstartR.ensure((F + 1) * 4) && estartR.ensure((F + 1) * 8) && istartR.ensure((F + 1) * 4);
-    ok &= poolS.ensure(LS * 128) && metaS.ensure(LS * 2) && listS.ensure(LS * 4);
-    ok &= usedS.ensure(G * 4) && wgqcS.ensure(GF * 4) && wgqeS.ensure(GF * 4) && wgqoS.ensure(GF * 4);
-    ok &= lstartS.ensure((F + 1) * 4) && estartS.ensure((F + 1) * 8) && istartS.ensure((F + 1) * 4);
+    bool ok = R_.ensure(LR, G, F) && S_.ensure(LS, G, F);
     const uint64_t BSW = build_chunks_per_sweep(), SLOT = build_sweep_slot();
     const uint64_t sweeps_max = LR / BSW + F + 1;  // build sweeps over all R partitions
     ok &= rjoin.ensure(sweeps_max * SLOT * 4) && rrun.ensure(2 * sweeps_max * NSUB * 4);
     ok &= surv.ensure(nseg * LS * 128) && survcnt.ensure(items_max * NSUB * 4) &&
           survoff.ensure(items_max * NSUB * 4);
-    ok &= jring_.ensure(kJoinRing * ring_slot_bytes()) && colR.ensure(F * 12) && colS.ensure(F * 12);  // u64 elems | u32 chunks
+    ok &= jring_.ensure(kJoinRing * ring_slot_bytes());
     // jparts: nparts [NJ] | job_surv [NJ] | nextra; jtask: extra parts {job, part}
     // (job_surv is left zero by k_join_split for the NJ jobs it saw: a join with another NJ
     // clears the whole buffer, so no stale count of an earlier job layout is read)
@@ -494,8 +466,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     sp.zero_small = (uint32_t*) sm;  // (the R scatter only: cleared below)
     sp.zero_word  = jparts.as<uint32_t>() + 2 * NJ;
 
-    // S pass-1 and its lists (below; dev A/B HWBRJ_DEV_OVL: on a second stream, concurrent with
-    // the R side)
+    // S pass-1 and its lists (below; async joins: on a second stream, concurrent with the R side)
     auto s_pass = [&](hipStream_t st, bool marks, hipEvent_t* tev = nullptr) -> int {
         ScatterParams ss = sp;
         ss.zero_small    = nullptr;
@@ -511,36 +482,18 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
             ss.n     = nS;
             ss.n_dev = nullptr;
         }
-        ss.pool       = poolS.as<uint32_t>();
-        ss.meta       = metaS.as<uint32_t>();
-        ss.wg_used    = usedS.as<uint32_t>();
-        ss.wgq_chunks = wgqcS.as<uint32_t>();
-        ss.wgq_elems  = wgqeS.as<uint32_t>();
-        ss.cap        = capS;
-        if (dbg) {  // dev-only phase stamps (HWBRJ_DBG)
-            if (!dbgS.ensure((size_t) G * 64)) {
-                set_last_error("hipMalloc failed (device memory)");
-                return 4;
-            }
-            HWBRJ_CHECK(hipMemsetAsync(dbgS.p, 0, dbgS.bytes, st));
-            ss.dbg = dbgS.as<uint64_t>();
-        }
+        S_.bind(&ss, capS);
         ss.ppool = mat ? ppoolS.as<uint32_t>() : nullptr;
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
         launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : SRC_TUPLES, SIDE_S, G, st);
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
         if (marks) HWBRJ_CHECK(mark(4, st));
-        launch_plan(wgqcS.as<uint32_t>(), wgqeS.as<uint32_t>(), G, g.log2F, wgqoS.as<uint32_t>(),
-                    colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), st);
-        launch_list_fill(metaS.as<uint32_t>(), usedS.as<uint32_t>(), capS, g.log2F, wgqoS.as<uint32_t>(),
-                         colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), CH, nseg, lstartS.as<uint32_t>(),
-                         estartS.as<uint64_t>(), istartS.as<uint32_t>(), listS.as<uint32_t>(), G, st);
+        index_side(S_, capS, g.log2F, CH, nseg, G, st);
         if (marks) HWBRJ_CHECK(mark(5, st));
         return 0;
     };
     HWBRJ_CHECK(mark(0, stream));
-    const bool ovl = (dev_knobs().ovl || (HWBRJ_OVL_ASYNC && !phase_ev_)) && g.mode != MODE_GLOBAL && !basic_kk &&
-                     !mat && !bcast;
+    const bool ovl = HWBRJ_OVL_ASYNC && !phase_ev_ && g.mode != MODE_GLOBAL && !basic_kk && !mat && !bcast;
     if (ovl) {  // S pass on the side stream (with phase events, its phases would show inside the R side's)
         if (!ovl_stream_) {
             HWBRJ_CHECK(hipStreamCreateWithFlags(&ovl_stream_, hipStreamNonBlocking));
@@ -566,7 +519,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     // Cache still holds much of them. Not in the global mode (the R scatter's workgroup 0 zeroes the
     // dense count the S pass's global probe adds to) nor for basic k >= 2 (the R side borrows the
     // S-side buffers).
-    const bool s_first = !ovl && !dev_knobs().rfirst && g.mode != MODE_GLOBAL && !basic_kk;
+    const bool s_first = !ovl && g.mode != MODE_GLOBAL && !basic_kk;
     if (s_first)
         if (const int rc = s_pass(stream, true)) return rc;
     // ---------------------------------------------------------------- R: pass-1 (+ filter)
@@ -575,20 +528,11 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     sp.src        = dR;
     sp.n          = nR;
     sp.n_dev      = nullptr;
-    sp.pool       = poolR.as<uint32_t>();
     sp.ppool      = mat ? ppoolR.as<uint32_t>() : nullptr;
-    sp.meta       = metaR.as<uint32_t>();
-    sp.wg_used    = usedR.as<uint32_t>();
-    sp.wgq_chunks = wgqcR.as<uint32_t>();
-    sp.wgq_elems  = wgqeR.as<uint32_t>();
-    sp.cap        = capR;
+    R_.bind(&sp, capR);
     launch_scatter(sp, SRC_TUPLES, SIDE_R, G, stream);
     HWBRJ_CHECK(mark(1, stream));
-    launch_plan(wgqcR.as<uint32_t>(), wgqeR.as<uint32_t>(), G, g.log2F, wgqoR.as<uint32_t>(),
-                colR.as<uint32_t>() + 2 * F, colR.as<uint64_t>(), stream);
-    launch_list_fill(metaR.as<uint32_t>(), usedR.as<uint32_t>(), capR, g.log2F, wgqoR.as<uint32_t>(),
-                     colR.as<uint32_t>() + 2 * F, colR.as<uint64_t>(), (uint32_t) BSW, 1, lstartR.as<uint32_t>(),
-                     estartR.as<uint64_t>(), istartR.as<uint32_t>(), listR.as<uint32_t>(), G, stream);
+    index_side(R_, capR, g.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
     sp.ppool      = nullptr;
     sp.zero_small = nullptr;
@@ -596,12 +540,12 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     BuildParams bp{};
     bp.g          = g;
     bp.tabs       = d_tabs_;
-    bp.pool       = poolR.as<uint32_t>();
-    bp.list       = listR.as<uint32_t>();
-    bp.list_start = lstartR.as<uint32_t>();
-    bp.elem_start = estartR.as<uint64_t>();
+    bp.pool       = R_.pool.as<uint32_t>();
+    bp.list       = R_.list.as<uint32_t>();
+    bp.list_start = R_.lstart.as<uint32_t>();
+    bp.elem_start = R_.estart.as<uint64_t>();
     bp.slices     = slice_mode ? slices.as<uint32_t>() : nullptr;
-    bp.sweep_start = istartR.as<uint32_t>();  // (R items = build sweeps)
+    bp.sweep_start = R_.istart.as<uint32_t>();  // (R items = build sweeps)
     bp.out_codes   = rjoin.as<uint32_t>();
     bp.run_cnt     = rrun.as<uint32_t>();
     bp.run_off     = rrun.as<uint32_t>() + sweeps_max * NSUB;
@@ -638,20 +582,10 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         sp.src        = bpos.p;
         sp.n          = nRk;
         sp.n_dev      = nullptr;
-        sp.pool       = poolS.as<uint32_t>();
-        sp.meta       = metaS.as<uint32_t>();
-        sp.wg_used    = usedS.as<uint32_t>();
-        sp.wgq_chunks = wgqcS.as<uint32_t>();
-        sp.wgq_elems  = wgqeS.as<uint32_t>();
-        sp.cap        = capS;
+        S_.bind(&sp, capS);
         launch_scatter(sp, SRC_CODES, SIDE_R, G, stream);
-        launch_plan(wgqcS.as<uint32_t>(), wgqeS.as<uint32_t>(), G, g.log2F, wgqoS.as<uint32_t>(),
-                    colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), stream);
-        launch_list_fill(metaS.as<uint32_t>(), usedS.as<uint32_t>(), capS, g.log2F, wgqoS.as<uint32_t>(),
-                         colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), (uint32_t) BSW, 1,
-                         lstartS.as<uint32_t>(), estartS.as<uint64_t>(), istartS.as<uint32_t>(),
-                         listS.as<uint32_t>(), G, stream);
-        launch_slice_fill(poolS.as<uint32_t>(), listS.as<uint32_t>(), lstartS.as<uint32_t>(), g,
+        index_side(S_, capS, g.log2F, (uint32_t) BSW, 1, G, stream);
+        launch_slice_fill(S_.pool.as<uint32_t>(), S_.list.as<uint32_t>(), S_.lstart.as<uint32_t>(), g,
                           slices.as<uint32_t>(), stream);
     }
     HWBRJ_CHECK(mark(3, stream));
@@ -666,10 +600,10 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     ProbeParams pp{};
     pp.g               = g;
     pp.tabs            = d_tabs_;
-    pp.pool            = poolS.as<uint32_t>();
-    pp.list            = listS.as<uint32_t>();
-    pp.list_start      = lstartS.as<uint32_t>();
-    pp.item_start      = istartS.as<uint32_t>();
+    pp.pool            = S_.pool.as<uint32_t>();
+    pp.list            = S_.list.as<uint32_t>();
+    pp.list_start      = S_.lstart.as<uint32_t>();
+    pp.item_start      = S_.istart.as<uint32_t>();
     pp.slices          = slice_mode ? slices.as<uint32_t>() : nullptr;
     pp.surv            = surv.as<uint32_t>();
     pp.surv_seg_stride = LS * 32;
@@ -681,37 +615,28 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     pp.kbits           = kbits;
     pp.fmt_cnt         = mat ? nullptr : (uint32_t*) sm + 10;  // (u64 word 5 of the slot: zeroed by the R scatter)
     const size_t   pl_lds = probe_lds_bytes(g, nullptr, mat != nullptr);
-    const uint32_t PG = (uint32_t) cus_ * (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / pl_lds));
-    const bool dbg_on = dbg;  // dev-only phase stamps (HWBRJ_DBG)
-    if (dbg_on) {
-        ok &= dbgP.ensure((size_t) std::max<uint32_t>(PG, F) * 64) && dbgJ.ensure((size_t) std::max<uint64_t>(F, 1024) * 64);
-        HWBRJ_CHECK(hipMemsetAsync(dbgP.p, 0, dbgP.bytes, stream));
-        HWBRJ_CHECK(hipMemsetAsync(dbgJ.p, 0, dbgJ.bytes, stream));
-        pp.dbg = dbgP.as<uint64_t>();
-    }
-    launch_probe(pp, PG, stream);
+    launch_probe(pp, (uint32_t) cus_ * wg_per_cu(pl_lds), stream);
     HWBRJ_CHECK(mark(6, stream));  // (survivor sub-partitioning is fused into k_probe: no ev_[7])
     surv_fused_ = true;
     // -------------------------------------------------------------------------- join
     JoinParams jp{};
     jp.r_codes         = rjoin.as<uint32_t>();
-    jp.r_sweep_start   = istartR.as<uint32_t>();
+    jp.r_sweep_start   = R_.istart.as<uint32_t>();
     jp.r_cnt           = rrun.as<uint32_t>();
     jp.r_off           = rrun.as<uint32_t>() + sweeps_max * NSUB;
     jp.slot            = (uint32_t) SLOT;
     jp.surv            = surv.as<uint32_t>();
     jp.surv_cnt        = survcnt.as<uint32_t>();
     jp.surv_off        = survoff.as<uint32_t>();
-    jp.item_start      = istartS.as<uint32_t>();
-    jp.list_start      = lstartS.as<uint32_t>();
+    jp.item_start      = S_.istart.as<uint32_t>();
+    jp.list_start      = S_.lstart.as<uint32_t>();
     jp.surv_seg_stride = LS * 32;
     jp.nseg            = nseg;
     jp.CH              = CH;
     jp.log2NSUB        = g.log2NSUB;
     jp.hash_shift      = g.hash_shift;
-    jp.bitmap          = (g.sub_shift > 0 && 32 - g.hash_shift <= join_bitmap_log2()) ? 1u : 0u;
+    jp.bitmap          = join_uses_bitmap(g) ? 1u : 0u;
     jp.jsum            = (uint64_t*) (sm + 128);  // 64 partial sums, one per 128-B line
-    jp.dbg             = dbg_on ? dbgJ.as<uint64_t>() : nullptr;
     jp.nparts          = jparts.as<uint32_t>();
     jp.extra           = jtask.as<uint2>();
     jp.nextra          = jparts.as<uint32_t>() + 2 * NJ;
@@ -775,47 +700,6 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         r.g     = g;
         ring_push(r);
     }
-
-    if (dbg_on) {
-        HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
-        std::vector<uint64_t> hp(PG * 8);
-        HWBRJ_CHECK(hipMemcpy(hp.data(), dbgP.p, hp.size() * 8, hipMemcpyDeviceToHost));
-        double sp_[6] = {0};
-        for (uint32_t b = 0; b < PG; b++)
-            for (int k = 0; k < 6; k++) sp_[k] += (double) hp[b * 8 + k] / PG;
-        std::vector<uint64_t> hs(G * 8);
-        HWBRJ_CHECK(hipMemcpy(hs.data(), dbgS.p, hs.size() * 8, hipMemcpyDeviceToHost));
-        double ss[6] = {0};
-        for (uint32_t b = 0; b < G; b++)
-            for (int k = 0; k < 6; k++) ss[k] += (double) hs[b * 8 + k] / G;
-        fprintf(stderr, "[dbg] S scatter cyc/WG: hash %.0f load+flush %.0f rank %.0f b1 %.0f write+plan %.0f b2 %.0f\n",
-                ss[0], ss[1], ss[2], ss[3], ss[4], ss[5]);
-        {  // workgroup start/end spread (100 MHz real-time clock): the kernel's tail
-            uint64_t t0 = ~0ull;
-            std::vector<double> st(G), en(G);
-            for (uint32_t b = 0; b < G; b++) t0 = std::min<uint64_t>(t0, hs[b * 8 + 6]);
-            for (uint32_t b = 0; b < G; b++) {
-                st[b] = (hs[b * 8 + 6] - t0) / 100.0;
-                en[b] = (hs[b * 8 + 7] - t0) / 100.0;
-            }
-            std::sort(st.begin(), st.end());
-            std::sort(en.begin(), en.end());
-            fprintf(stderr, "[dbg] S scatter WG start us: max %.1f | end us: min %.1f p10 %.1f p50 %.1f p90 %.1f max %.1f\n",
-                    st[G - 1], en[0], en[G / 10], en[G / 2], en[G * 9 / 10], en[G - 1]);
-        }
-        fprintf(stderr, "[dbg] probe cyc/WG: top %.0f test %.0f b1 %.0f scan+b2 %.0f write %.0f b3+copy %.0f\n",
-                sp_[0], sp_[1], sp_[2], sp_[3], sp_[4], sp_[5]);
-        {  // k_join: workgroups summed into 1024 slots
-            std::vector<uint64_t> hj2(1024 * 8);
-            HWBRJ_CHECK(hipMemcpy(hj2.data(), dbgJ.p, hj2.size() * 8, hipMemcpyDeviceToHost));
-            double sj2[6] = {0};
-            const double nwg = (double) F * (1u << g.log2NSUB);
-            for (uint32_t b = 0; b < 1024; b++)
-                for (int k = 0; k < 6; k++) sj2[k] += (double) hj2[b * 8 + k] / nwg;
-            fprintf(stderr, "[dbg] join cyc/WG (wave 0): desc %.0f R+sets %.0f popcnt %.0f surv1 %.0f surv2 %.0f end %.0f\n",
-                    sj2[0], sj2[1], sj2[2], sj2[3], sj2[4], sj2[5]);
-        }
-    }
     return 0;
 }
 
@@ -846,23 +730,16 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     const uint64_t capS = std::max(region_cap(std::max(nS, nRk), G, Fm), rw / 32 + Fm + 1);
     const uint64_t LR = (uint64_t) G * capR, LS = (uint64_t) G * capS;
     const uint64_t items_max = (LS / CH + Fm + 1) * nseg;
-    if (G > 512 || LS > (1ull << 27) || LR > (1ull << 27) || capS >= (1u << 22) || capR >= (1u << 22)) {
+    if (!part_fits(G, capR, capS)) {
         set_last_error("relation too large for 27-bit chunk ids (|S| or |R| > ~4.2e9 tuples per GPU)");
         return 3;
     }
-    const uint64_t GF = (uint64_t) G * Fm;
-    bool ok = true;
-    ok &= poolR.ensure(LR * 128) && metaR.ensure(LR * 2) && listR.ensure(LR * 4);
-    ok &= usedR.ensure(G * 4) && wgqcR.ensure(GF * 4) && wgqeR.ensure(GF * 4) && wgqoR.ensure(GF * 4);
-    ok &= lstartR.ensure((Fm + 1) * 4) && estartR.ensure((Fm + 1) * 8) && istartR.ensure((Fm + 1) * 4);
-    ok &= poolS.ensure(LS * 128) && metaS.ensure(LS * 2) && listS.ensure(LS * 4);
-    ok &= usedS.ensure(G * 4) && wgqcS.ensure(GF * 4) && wgqeS.ensure(GF * 4) && wgqoS.ensure(GF * 4);
-    ok &= lstartS.ensure((Fm + 1) * 4) && estartS.ensure((Fm + 1) * 8) && istartS.ensure((Fm + 1) * 4);
+    bool ok = R_.ensure(LR, G, Fm) && S_.ensure(LS, G, Fm);
     const uint64_t BSW = build_chunks_per_sweep(), SLOT = build_sweep_slot();
     const uint64_t sweeps_max = LR / BSW + Fm + 1;
     ok &= rjoin.ensure(sweeps_max * SLOT * 4) && rrun.ensure(2 * sweeps_max * NSUB * 4);
     ok &= surv.ensure(LS * 128) && survcnt.ensure(items_max * NSUB * 4) && survoff.ensure(items_max * NSUB * 4);
-    ok &= jring_.ensure(kJoinRing * ring_slot_bytes()) && colR.ensure(Fm * 12) && colS.ensure(Fm * 12);
+    ok &= jring_.ensure(kJoinRing * ring_slot_bytes());
     const bool jnew = jparts.bytes < (size_t) (2 * NJ + 1) * 4 || NJ != last_nj_;
     last_nj_ = NJ;
     ok &= jtask.ensure((size_t) join_extra_tasks() * 8) && jparts.ensure((size_t) (2 * NJ + 1) * 4);
@@ -885,52 +762,37 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     if (jnew) HWBRJ_CHECK(hipMemsetAsync(jparts.p, 0, jparts.bytes, stream));
     HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + 2 * NJ, 0, 4, stream));
 
-    auto side = [&](bool r) {
+    auto side = [&](const PartSide& s, uint64_t cap) {
         ScatterParams sp{};
-        sp.tabs       = d_tabs_;
-        sp.pool       = (r ? poolR : poolS).as<uint32_t>();
-        sp.meta       = (r ? metaR : metaS).as<uint32_t>();
-        sp.wg_used    = (r ? usedR : usedS).as<uint32_t>();
-        sp.wgq_chunks = (r ? wgqcR : wgqcS).as<uint32_t>();
-        sp.wgq_elems  = (r ? wgqeR : wgqeS).as<uint32_t>();
-        sp.cap        = r ? capR : capS;
+        sp.tabs = d_tabs_;
+        s.bind(&sp, cap);
         return sp;
-    };
-    auto index = [&](bool r, uint32_t log2F, uint32_t ch, uint32_t ns) {
-        const uint32_t Fx = 1u << log2F;
-        DevBuf& col = r ? colR : colS;
-        launch_plan((r ? wgqcR : wgqcS).as<uint32_t>(), (r ? wgqeR : wgqeS).as<uint32_t>(), G, log2F,
-                    (r ? wgqoR : wgqoS).as<uint32_t>(), col.as<uint32_t>() + 2 * Fx, col.as<uint64_t>(), stream);
-        launch_list_fill((r ? metaR : metaS).as<uint32_t>(), (r ? usedR : usedS).as<uint32_t>(), r ? capR : capS,
-                         log2F, (r ? wgqoR : wgqoS).as<uint32_t>(), col.as<uint32_t>() + 2 * Fx, col.as<uint64_t>(),
-                         ch, ns, (r ? lstartR : lstartS).as<uint32_t>(), (r ? estartR : estartS).as<uint64_t>(),
-                         (r ? istartR : istartS).as<uint32_t>(), (r ? listR : listS).as<uint32_t>(), G, stream);
     };
 
     HWBRJ_CHECK(mark(0, stream));
     // ---------------------------------------------------------------- R: the join layout
-    ScatterParams sp = side(true);
+    ScatterParams sp = side(R_, capR);
     sp.g   = gj;
     sp.src = dR;
     sp.n   = nR;
     launch_scatter(sp, SRC_TUPLES, SIDE_R, G, stream);
     HWBRJ_CHECK(mark(1, stream));
-    index(true, gj.log2F, (uint32_t) BSW, 1);
+    index_side(R_, capR, gj.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
     BuildParams bp{};
     bp.g           = gj;
     bp.tabs        = d_tabs_;
-    bp.pool        = poolR.as<uint32_t>();
-    bp.list        = listR.as<uint32_t>();
-    bp.list_start  = lstartR.as<uint32_t>();
-    bp.elem_start  = estartR.as<uint64_t>();
-    bp.sweep_start = istartR.as<uint32_t>();
+    bp.pool        = R_.pool.as<uint32_t>();
+    bp.list        = R_.list.as<uint32_t>();
+    bp.list_start  = R_.lstart.as<uint32_t>();
+    bp.elem_start  = R_.estart.as<uint64_t>();
+    bp.sweep_start = R_.istart.as<uint32_t>();
     bp.out_codes   = rjoin.as<uint32_t>();
     bp.run_cnt     = rrun.as<uint32_t>();
     bp.run_off     = rrun.as<uint32_t>() + sweeps_max * NSUB;
     launch_build(bp, Fj, stream);
     // ---------------------------------------------------------------- the filter slices
-    sp = side(false);
+    sp = side(S_, capS);
     if (g.k <= G) {  // R's k bit positions partitioned by slice straight from the tuples
         Geometry gp = g;
         gp.mode     = MODE_BASIC_POS;
@@ -946,26 +808,26 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
         sp.n   = nRk;
         launch_scatter(sp, SRC_CODES, SIDE_R, G, stream);
     }
-    index(false, g.log2F, (uint32_t) BSW, 1);
-    launch_slice_fill(poolS.as<uint32_t>(), listS.as<uint32_t>(), lstartS.as<uint32_t>(), g,
+    index_side(S_, capS, g.log2F, (uint32_t) BSW, 1, G, stream);
+    launch_slice_fill(S_.pool.as<uint32_t>(), S_.list.as<uint32_t>(), S_.lstart.as<uint32_t>(), g,
                       slices.as<uint32_t>(), stream);
     HWBRJ_CHECK(mark(3, stream));
     // ---------------------------------------------------------------- S: by the slice of bit 0
-    sp     = side(false);
+    sp     = side(S_, capS);
     sp.g   = g;
     sp.src = dS;
     sp.n   = nS;
     launch_scatter(sp, SRC_TUPLES, SIDE_S, G, stream);
     HWBRJ_CHECK(mark(4, stream));
-    index(false, g.log2F, CH, nseg);
+    index_side(S_, capS, g.log2F, CH, nseg, G, stream);
     HWBRJ_CHECK(mark(5, stream));
     // ---------------------------------------------------------------- one bit per pass
     const uint32_t PG = G;
     ProbeParams    pb{};
-    pb.pool       = poolS.as<uint32_t>();
-    pb.list       = listS.as<uint32_t>();
-    pb.list_start = lstartS.as<uint32_t>();
-    pb.item_start = istartS.as<uint32_t>();
+    pb.pool       = S_.pool.as<uint32_t>();
+    pb.list       = S_.list.as<uint32_t>();
+    pb.list_start = S_.lstart.as<uint32_t>();
+    pb.item_start = S_.istart.as<uint32_t>();
     pb.slices     = slices.as<uint32_t>();
     uint32_t* dz[2] = {dense.as<uint32_t>(), dense2.as<uint32_t>()};
     for (uint32_t j = 0; j < g.k; j++) {
@@ -973,13 +835,13 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
         gb.bitj     = j;
         if (j > 0) {  // the candidates of pass j - 1, by the slice of bit j
             gb.mode       = MODE_BASIC_BITJ;
-            sp            = side(false);
+            sp            = side(S_, capS);
             sp.g          = gb;
             sp.src        = dz[(j - 1) & 1];
             sp.seg_cnt    = wgc[(j - 1) & 1];
             sp.seg_stride = rw;
             launch_scatter(sp, SRC_CODES, SIDE_S, G, stream);
-            index(false, g.log2F, CH, nseg);
+            index_side(S_, capS, g.log2F, CH, nseg, G, stream);
         }
         pb.g               = gb;
         pb.surv            = dz[j & 1];
@@ -993,21 +855,21 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     {
         Geometry gc = gj;
         gc.mode     = MODE_CODE_OF_KEY;
-        sp          = side(false);
+        sp          = side(S_, capS);
         sp.g        = gc;
         sp.src        = dz[(g.k - 1) & 1];
         sp.seg_cnt    = wgc[(g.k - 1) & 1];
         sp.seg_stride = rw;
         launch_scatter(sp, SRC_CODES, SIDE_S, G, stream);
-        index(false, gj.log2F, CH, 1);
+        index_side(S_, capS, gj.log2F, CH, 1, G, stream);
     }
     ProbeParams pp{};
     pp.g               = gj;
     pp.tabs            = d_tabs_;
-    pp.pool            = poolS.as<uint32_t>();
-    pp.list            = listS.as<uint32_t>();
-    pp.list_start      = lstartS.as<uint32_t>();
-    pp.item_start      = istartS.as<uint32_t>();
+    pp.pool            = S_.pool.as<uint32_t>();
+    pp.list            = S_.list.as<uint32_t>();
+    pp.list_start      = S_.lstart.as<uint32_t>();
+    pp.item_start      = S_.istart.as<uint32_t>();
     pp.surv            = surv.as<uint32_t>();
     pp.surv_seg_stride = LS * 32;
     pp.surv_cnt        = survcnt.as<uint32_t>();
@@ -1015,27 +877,27 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     pp.filtered        = cnt + NC - 1;  // (counted by the last bit pass)
     pp.job_surv        = jparts.as<uint32_t>() + NJ;
     const size_t   pl_lds = probe_lds_bytes(gj, nullptr);
-    launch_probe(pp, (uint32_t) cus_ * (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / pl_lds)), stream);
+    launch_probe(pp, (uint32_t) cus_ * wg_per_cu(pl_lds), stream);
     HWBRJ_CHECK(mark(7, stream));
     surv_fused_ = false;
     // -------------------------------------------------------------------------- join
     JoinParams jp{};
     jp.r_codes         = rjoin.as<uint32_t>();
-    jp.r_sweep_start   = istartR.as<uint32_t>();
+    jp.r_sweep_start   = R_.istart.as<uint32_t>();
     jp.r_cnt           = rrun.as<uint32_t>();
     jp.r_off           = rrun.as<uint32_t>() + sweeps_max * NSUB;
     jp.slot            = (uint32_t) SLOT;
     jp.surv            = surv.as<uint32_t>();
     jp.surv_cnt        = survcnt.as<uint32_t>();
     jp.surv_off        = survoff.as<uint32_t>();
-    jp.item_start      = istartS.as<uint32_t>();
-    jp.list_start      = lstartS.as<uint32_t>();
+    jp.item_start      = S_.istart.as<uint32_t>();
+    jp.list_start      = S_.lstart.as<uint32_t>();
     jp.surv_seg_stride = LS * 32;
     jp.nseg            = 1;
     jp.CH              = CH;
     jp.log2NSUB        = gj.log2NSUB;
     jp.hash_shift      = gj.hash_shift;
-    jp.bitmap          = (gj.sub_shift > 0 && 32 - gj.hash_shift <= join_bitmap_log2()) ? 1u : 0u;
+    jp.bitmap          = join_uses_bitmap(gj) ? 1u : 0u;
     jp.jsum            = (uint64_t*) (sm + 128);
     jp.nparts          = jparts.as<uint32_t>();
     jp.extra           = jtask.as<uint2>();

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <deque>
 #include <string>
 #include <vector>
@@ -35,6 +36,38 @@ struct DevBuf {
     void   release();
     template <class T> T* as() const { return (T*) p; }
 };
+
+// Pass-1 output of one relation: its chunk pool and metas, the scatter's per-workgroup queues, and
+// the chunk lists / element / item starts indexed from them (k_plan, k_list_fill).
+struct PartSide {
+    DevBuf pool, meta, used, wgqc, wgqe, wgqo, lstart, estart, istart, list;
+    DevBuf col;  // per-partition totals from k_plan: u64 elements [F], then u32 chunks [F]
+    // chunks: G regions of the scatter's region capacity; F partitions
+    bool   ensure(uint64_t chunks, uint32_t G, uint32_t F);
+    void   release();
+    // the scatter's outputs (pool, meta, wg_used, wgq_chunks, wgq_elems, cap)
+    void   bind(ScatterParams* sp, uint64_t cap) const;
+};
+// k_plan + k_list_fill of one scattered side: lists and starts for items of per_item chunks, nseg
+// items per piece
+void index_side(const PartSide& s, uint64_t cap, uint32_t log2F, uint32_t per_item, uint32_t nseg,
+                uint32_t G, hipStream_t st);
+// chunks of one scatter workgroup's region for n tuples over G workgroups and F partitions
+uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F);
+// Pass-1 limits: k_plan's row groups (G <= 512), the list entries' 27-bit chunk ids (hwbrj_kernels.hip,
+// K4) and the metas' 22-bit region offsets
+inline bool part_fits(uint32_t G, uint64_t capR, uint64_t capS) {
+    return G <= 512 && G * capR <= (1ull << 27) && G * capS <= (1ull << 27) && capR < (1u << 22) &&
+           capS < (1u << 22);
+}
+// workgroups per CU of a kernel with this much LDS (160 KB per CU), at most 2
+inline uint32_t wg_per_cu(size_t lds_bytes) {
+    return (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / lds_bytes));
+}
+// JoinParams::bitmap: the job keys v = code >> hash_shift fit k_join's direct-address bitmap
+inline bool join_uses_bitmap(const Geometry& g) {
+    return g.sub_shift > 0 && 32 - g.hash_shift <= join_bitmap_log2();
+}
 
 class Engine {
   public:
@@ -180,7 +213,7 @@ class Engine {
     int          device_;
     int          cus_ = 256;
     hipStream_t  own_stream_ = nullptr;
-    hipStream_t  ovl_stream_ = nullptr;             // dev A/B HWBRJ_DEV_OVL: the S pass's stream
+    hipStream_t  ovl_stream_ = nullptr;             // async joins: the S pass's stream
     hipEvent_t   ovl_ev_[2]  = {nullptr, nullptr};  // (fork, join of ovl_stream_)
     hipEvent_t   ev_[10];
     bool         have_filter_ = false;
@@ -229,22 +262,18 @@ class Engine {
     hipError_t   mark(int i, hipStream_t stream);  // ev_[i] when phase_ev_
     bool         alloc_only_   = false;  // reserve(): enqueue returns after its allocations
     int          enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                         const bloom_filter_args_t* args, hipStream_t stream, bool dbg, int jkind,
+                         const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                          const MatReq* mat = nullptr);
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                                   const Geometry& g, hipStream_t stream, int jkind);
     CrcTables*   d_tabs_ = nullptr;
     GenPlan*     d_plan_ = nullptr;
-    // R side
-    DevBuf poolR, metaR, usedR, wgqcR, wgqeR, wgqoR, lstartR, estartR, istartR, listR;
-    // S side
-    DevBuf poolS, metaS, usedS, wgqcS, wgqeS, wgqoS, lstartS, estartS, istartS, listS;
-    DevBuf slices, bitmap, rjoin, rrun, surv, survcnt, survoff, dense, small, dbgP, dbgJ, dbgS;
+    PartSide R_, S_;
+    DevBuf slices, bitmap, rjoin, rrun, surv, survcnt, survoff, dense, small;
     DevBuf bpos;        // basic k >= 2: R bit positions (k_bitpos)
-    DevBuf colR, colS;  // per-partition totals from k_plan: u64 elements [F], then u32 chunks [F]
     DevBuf mtab, mcount;  // materialization (side pass): R table, pair counter
-    // materializing pipeline: payload pools (chunk layout of poolR / poolS), R payloads of the
+    // materializing pipeline: payload pools (chunk layout of R_.pool / S_.pool), R payloads of the
     // build sweeps, survivors' chunk positions
     DevBuf ppoolR, ppoolS, rpay, survpos;
     DevBuf dense2, kkcnt;  // basic k >= 2: the second dense candidate buffer, per-pass counts
@@ -270,8 +299,6 @@ int rccl_alltoall_u64_dev(Engine* e, const uint64_t* d_send, uint64_t* d_recv, u
 int rccl_allreduce_max_u64(Engine* e, uint64_t* d, uint64_t n);
 // HWBRJ_RCCL_SELF (tests): a rank's own exchange blocks go through ncclSend / ncclRecv too
 bool rccl_self_blocks();
-// chunks of a shard's partition pool for n tuples over G scatter workgroups and F partitions
-uint64_t pj_region_cap(uint64_t n, uint32_t G, uint32_t F);
 
 // glibc's rand() (stdlib/random_r.c TYPE_3) with private state (hwbrj_gen.cpp).
 struct GlibcRand {

@@ -24,7 +24,6 @@ struct ScatterParams {
     uint32_t*        wg_used;      // [G] chunks used by each workgroup
     uint32_t*        wgq_chunks;   // [G][F] chunks of partition q in workgroup wg's region
     uint32_t*        wgq_elems;    // [G][F] elements of partition q in workgroup wg's region
-    uint64_t*        dbg;          // dev-only: per-workgroup phase cycles (HWBRJ_DBG), or nullptr
     uint64_t         cap;          // chunk capacity of one workgroup region
     const uint32_t*  seg_cnt;      // SRC_CODES from per-workgroup segments: workgroup w partitions
     uint64_t         seg_stride;   // src + w * seg_stride (elements), seg_cnt[w] of them; or nullptr
@@ -103,7 +102,6 @@ struct ProbeParams {
                                   // index in the S payload pool), parallel to surv; or nullptr
     uint32_t*        wg_cnt;      // k_probe_bitj: words appended to workgroup w's region
                                   // (surv + w * surv_seg_stride)
-    uint64_t*        dbg;         // dev-only: per-workgroup phase cycles (HWBRJ_DBG), or nullptr
     uint32_t         kbits;       // 18 / 24: staged items store their join keys (code >> hash_shift)
                                   // as a stream of kbits-bit fields from the item region's byte 0,
                                   // flagged by bit 31 of their surv_off entries (unstaged items keep
@@ -132,7 +130,6 @@ struct JoinParams {
     uint2*          extra;        // [join_extra_tasks()] {job, part} of the further parts
     uint32_t*       nextra;       // parts requested beyond part 0 (zeroed before the join)
     uint32_t        split_surv;   // survivors per join part (0: the default, kJoinTaskSurv)
-    uint64_t*       dbg;          // dev-only: per-workgroup phase cycles (HWBRJ_DBG), or nullptr
     uint32_t        jkind;        // per-partition join: 0 bucket chaining's role (bitmap / hash
                                   // table, PRO), 1 histogram join (PRH), 2 + 16-byte compares (PRHO)
     const uint64_t* item_base;    // [items] survivor region of each item (partitioned multi-GPU
@@ -287,25 +284,6 @@ void   launch_copy_bw(const void* src, void* dst, uint64_t bytes, int grid, hipS
 // every compile-time switch of hwbrj_kernels.hip that differs from the product default ("" for the
 // product build); hwbrj_version() appends it
 const char* kernel_build_knobs();
-
-// Dev-only runtime switches (A/B experiments of measured alternatives), read from the HWBRJ_DEV_*
-// environment once, at the first Engine's construction, and only in builds with -DHWBRJ_DEV_BUILD:
-// a product build ignores the environment, so no stray variable changes its path.
-struct DevKnobs {
-    bool     kk1 = false;        // HWBRJ_DEV_KK1: basic k = 1 on the bit-pass pipeline
-    bool     kk_gather = false;  // HWBRJ_DEV_KK_GATHER: basic k >= 2 by global-slice gathers
-    bool     noxcd = false;      // HWBRJ_DEV_NOXCD: k_join_mat without XCD-aware job order
-    bool     dbg = false;        // HWBRJ_DBG: in-kernel phase stamps (a -DHWBRJ_STAMPS build)
-    uint32_t maxf = 0;           // HWBRJ_DEV_MAXF: cap on the partition count F
-    uint32_t scwpc = 0;          // HWBRJ_DEV_SCWPC: scatter workgroups per CU
-    int      evflags = -1;       // HWBRJ_DEV_EVFLAGS: phase-event creation flags
-    uint32_t l2sub = 0;          // HWBRJ_DEV_L2SUB: join sub-partition bits (code-digit joins)
-    bool     ovl   = false;      // HWBRJ_DEV_OVL: S pass on a second stream beside the R side
-    bool     rfirst = false;     // HWBRJ_DEV_RFIRST: R side before the S pass (the round-3 order)
-};
-const DevKnobs& dev_knobs();
-// "name=value" of every dev knob that is set ("" in product builds); hwbrj_version() appends it
-std::string dev_knobs_string();
 
 // Test hooks (hwbrj_set_test_hook, include/hwbrj.h): explicit process-wide settings that force
 // rarely taken paths (no result changes) or inject a failure; all off by default.

@@ -28,19 +28,6 @@
 #include "hwbrj_common.h"
 #include "hwbrj_kernels.h"
 
-// Ablations ("results invalid": they skip work to time what is left) and cycle stamps exist for
-// measurements only. They build only with -DHWBRJ_DEV_BUILD (tools/build_abl.sh sets it), so no
-// product build can carry one by accident; hwbrj_version() names every non-default knob.
-#if !defined(HWBRJ_DEV_BUILD) &&                                                                   \
-    (defined(HWBRJ_ABL_NOCRC) || defined(HWBRJ_ABL_NOCRAP) || defined(HWBRJ_ABL_NOSTORE) ||        \
-     defined(HWBRJ_ABL_SPLITH) || defined(HWBRJ_ABL_PNOPST) || defined(HWBRJ_ABL_BNOBITS) ||       \
-     defined(HWBRJ_ABL_BNOSORT) || defined(HWBRJ_ABL_PNOB1) || defined(HWBRJ_ABL_JNOR) ||          \
-     defined(HWBRJ_ABL_JNOS) || defined(HWBRJ_ABL_MJ_EMPTY) || defined(HWBRJ_ABL_MJ_NOLOAD) ||     \
-     defined(HWBRJ_ABL_MJ_NOINS) || defined(HWBRJ_ABL_MJ_R) || defined(HWBRJ_ABL_PROBE) ||         \
-     defined(HWBRJ_STAMPS))
-#error "HWBRJ_ABL_* / HWBRJ_STAMPS give invalid results or perturb timing: dev builds only (-DHWBRJ_DEV_BUILD)"
-#endif
-
 namespace hwbrj {
 
 // ================================================================== small device helpers
@@ -505,11 +492,7 @@ __device__ __forceinline__ void sc_word_lds0(uint32_t x, const Geometry& g, cons
         return;
     }
     const uint32_t key  = x;
-#ifdef HWBRJ_ABL_NOCRC
-    const uint32_t code = key * 0x9E3779B1u;  // dev ablation (results invalid)
-#else
     const uint32_t code = crc_nib(tab, key);
-#endif
     if (MODE == MODE_SLICE_BASIC) {
         // the partition is the first filter bit's slice, not a code digit, so the word carries
         // the key (mixed, bmix): the join compares words, and nothing downstream needs the CRC
@@ -517,11 +500,7 @@ __device__ __forceinline__ void sc_word_lds0(uint32_t x, const Geometry& g, cons
         w = bmix(key);
     } else if (MODE == MODE_SLICE_BLOCK && FMT == FMT_PACKED) {
         q = code & F1;
-#ifdef HWBRJ_ABL_NOCRAP
-        w = (key & (g.B - 1u)) | ((code >> g.log2F) << g.log2B);  // dev ablation (results invalid)
-#else
         w = (crapwow(kSeed, key) & (g.B - 1u)) | ((code >> g.log2F) << g.log2B);
-#endif
     } else {
         q = code & F1;
         w = code;
@@ -572,7 +551,6 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
     if (blockIdx.x == 0 && P.zero_small && tid < 16) P.zero_small[tid] = 0;
     if (blockIdx.x == 0 && P.zero_word && tid == 0) *P.zero_word = 0;
 
-    if (P.dbg && tid == 0) P.dbg[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime();  // dev-only: start
     const uint64_t n     = P.n_dev ? *P.n_dev : P.n;
     const uint64_t units = (n + 3) >> 2;
     const uint64_t G = gridDim.x, wg = blockIdx.x;
@@ -660,9 +638,6 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
             const uint32_t l8 = k & 7;
             const uint32_t cb = ncb[(par ^ 1u) * F + qq] & kCbMask;
             const v4u      v  = *(const v4u*) &stage[qq * 32 + l8 * 4];
-#ifdef HWBRJ_ABL_NOSTORE
-            if (v.x == 0x12345678u && v.y == 0x9abcdef0u)  // dev ablation: practically never stores
-#endif
             __builtin_amdgcn_raw_buffer_store_b128(v, rpool, ok ? (cb * 32 + l8 * 4) * 4 : kOob, 0, SAUX);
             __builtin_amdgcn_raw_buffer_store_b16((short) meta16(qq, 32u), rmeta, ok && l8 == 0 ? cb * 2 : kOob, 0, 0);
         };
@@ -671,19 +646,6 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         for (uint32_t k = kScK * kScThreads + tid; k < nf * 8; k += kScThreads) task(k);  // rare
     };
 
-    uint64_t tph[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-    (void) tlast;
-    auto stamp = [&](int k) {  // dev-only phase stamps (build with -DHWBRJ_STAMPS, run with HWBRJ_DBG)
-#ifdef HWBRJ_STAMPS
-        if (P.dbg) {
-            const uint64_t t = __builtin_amdgcn_s_memtime();
-            tph[k] += t - tlast;
-            tlast = t;
-        }
-#else
-        (void) k;
-#endif
-    };
     ScRaw<SRC> RA, RB;
     load_round(0, RA);
     if (kScPre == 2) load_round(kScRound, RB);
@@ -754,7 +716,6 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         const bool full = base + kScRound <= len;  // uniform
         // ---- A: hash (consumes R), refill R, copy out the last plan, rank
         hash(base, R);
-        stamp(0);
         load_round(base + kScPre * kScRound, R);
         uint32_t slot[kScE];  // ranks issued first: their returns overlap the copy-out
 #pragma unroll
@@ -764,7 +725,6 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
             misc[1 + par]        = 0;  // (last read by the previous round's flush_copy)
             misc[3 + (par ^ 1u)] = 0;  // (last read by the previous round's phase B)
         }
-        stamp(1);
         bool sk = false;  // a slot >= 63: some partition reaches 64 words this round
 #pragma unroll
         for (int j = 0; j < kScE; j++) {
@@ -772,9 +732,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
             sk |= q[j] >= (63u << 11) && (q[j] & 2047u) < F;
         }
         if (__builtin_amdgcn_ballot_w64(sk) != 0 && lane == 0) misc[3 + par] = 1u;
-        stamp(2);
         __syncthreads();  // B1: last plan copied out; every rank of this round taken
-        stamp(3);
         // ---- B: overflow words of the previous round, in-stage words of this round, plan
         write_pending();
         const bool skew = __builtin_amdgcn_readfirstlane(misc[3 + par]) != 0;
@@ -816,9 +774,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
                 for (uint32_t c = 1; c < nch; c++) meta[cb + c] = meta16(qq, 32u);  // direct chunks
             }
         }
-        stamp(4);
         __syncthreads();  // B2: plan visible
-        stamp(5);
         par ^= 1u;
     };
     uint32_t base = 0;
@@ -865,10 +821,6 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         }
         __syncthreads();
         if (tid == 0) P.wg_used[wg] = misc[0];
-        if (P.dbg && tid == 0) {
-            for (int k = 0; k < 6; k++) P.dbg[wg * 8 + k] = tph[k];
-            P.dbg[wg * 8 + 7] = __builtin_amdgcn_s_memrealtime();  // dev-only: end (100 MHz clock)
-        }
         // this workgroup's row of the (workgroup x partition) chunk / element matrices (k_plan
         // scans them column-wise: no global atomics)
 #pragma unroll
@@ -951,11 +903,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     const auto rmeta  = buf_rsrc(meta, (uint32_t) (P.cap * 2));
     __syncthreads();
 
-#ifdef HWBRJ_ABL_SPLITH  // dev ablation (results invalid): second halves in a separate array
-    auto hword = [&](uint32_t H) { return (H & 1u) * (uint32_t) (P.cap * 16) + (H >> 1) * 16u; };
-#else
     auto hword = [&](uint32_t H) { return H * 16u; };  // word offset of half H in the region
-#endif
     auto load_round = [&](uint32_t base, v2u (&R)[kScE]) {  // {key, payload} as one 8-byte load
         if (base + kScRound <= len) {
 #pragma unroll
@@ -985,9 +933,6 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
             vp.x = x0.y; vp.y = x0.w; vp.z = x1.y; vp.w = x1.w;
             const uint32_t o  = ok ? (hword(H) + l4 * 4) * 4 : kOob;
             __builtin_amdgcn_raw_buffer_store_b128(vw, rpool, o, 0, 0);
-#ifdef HWBRJ_ABL_PNOPST  // dev ablation (results invalid): no payload stores
-            if (vp.x == 0x12345678u && vp.y == 0x9abcdef0u)
-#endif
             __builtin_amdgcn_raw_buffer_store_b128(vp, rppool, o, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b16((short) meta16(qq, 32u), rmeta, ok && l4 == 0 && (H & 1u) ? (H >> 1) * 2 : kOob, 0, 0);
         };
@@ -1544,28 +1489,14 @@ __global__ __launch_bounds__(1024) void k_build(BuildParams P) {
                 for (int t = 0; t < 4; t++) {
                     const bool     ok = (uint32_t) t < SA.n[jj];
                     const uint32_t w  = sweep_word(SA, jj, t);
-#ifndef HWBRJ_ABL_BNOBITS
                     if (wr && ok) {
                         const Loc L = locate<KIND>(w, g, inv, q);
                         if (L.seg == seg) apply_bits<KIND, true>(L, g, slice);
                     }
-#endif
                     c[t]  = decode_k<KIND>(w, q, g);
                     rk[t] = 0xFFFFFFFFu;
-#ifndef HWBRJ_ABL_BNOSORT
                     if (last && ok) rk[t] = atomicAdd(&cnt[(nsw & 1u) * 64 + ((c[t] >> g.sub_shift) & (NSUB - 1u))], 1u);
-#else
-                    if (ok && c[t] == 0x12345678u) P.out_codes[0] = c[t];  // dev ablation: keep the loads live
-#endif
                 }
-#ifdef HWBRJ_ABL_BNOSORT
-                if (last && (uint32_t) tid < NSUB) {  // dev ablation (results invalid): empty runs
-                    const uint64_t r = (uint64_t) (sw0 + (sb - l0) / kBSweep) * NSUB + tid;
-                    P.run_cnt[r]     = 0;
-                    P.run_off[r]     = 0;
-                }
-                continue;
-#endif
                 if (!last) continue;
                 const uint32_t sw = sw0 + (sb - l0) / kBSweep;
                 __syncthreads();  // B1: every rank of the sweep taken (and the last sweep copied out)
@@ -1660,12 +1591,6 @@ template <int KIND> constexpr uint32_t scr_cap() {
     return KIND == KIND_BLOCK_PKK || KIND == KIND_BASIC_KK ? (uint32_t) HWBRJ_SCRK
                                                                                      : (uint32_t) HWBRJ_SCR1;
 }
-// Dev ablations of the probe's parts (dev builds only; results invalid except `filtered`):
-// 1 = loads + test + barrier only, 2 = + the compaction, 3 = everything but the copy-out.
-#ifndef HWBRJ_ABL_PROBE
-#define HWBRJ_ABL_PROBE 0
-#endif
-constexpr int kAblProbe = HWBRJ_ABL_PROBE;
 // The counting probe's copy-out: b128 stores per thread per piece (a fixed count: vmcnt), so its
 // stage holds at most kPco * 4096 words. Every store instruction costs its whole wave's issue and
 // data path even when its lanes are out of range (the copy-out of 3 per thread was 0.21 ms of the
@@ -1732,19 +1657,6 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
     const uint32_t it0  = __builtin_amdgcn_readfirstlane((uint32_t) ((uint64_t) blockIdx.x * I / gridDim.x));
     const uint32_t it1  = __builtin_amdgcn_readfirstlane((uint32_t) ((uint64_t) (blockIdx.x + 1) * I / gridDim.x));
     const uint32_t nseg = SEG1 || !slices ? 1u : g.nseg;
-    uint64_t tph[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-    (void) tlast;
-    auto stamp = [&](int k) {  // dev-only phase stamps (build with -DHWBRJ_STAMPS, run with HWBRJ_DBG)
-#ifdef HWBRJ_STAMPS
-        if (P.dbg) {
-            const uint64_t t = __builtin_amdgcn_s_memtime();
-            tph[k] += t - tlast;
-            tlast = t;
-        }
-#else
-        (void) k;
-#endif
-    };
     // Copy-out of the previous item's staged survivors and its run table: a fixed number of
     // buffer stores whatever the counts (out-of-range ones are dropped), so the compiler never has
     // to wait for them (vmcnt counts stores on gfx9).
@@ -1759,8 +1671,7 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
         const uint32_t nbytes = ((prev_total + 3u) & ~3u) * 4u;  // item region holds round_up(total, 4)
         const auto     ro     = buf_rsrc(prev_out, nbytes);
         const v4u*     src    = (const v4u*) (stage + prev_buf * sstr);
-        if (kAblProbe != 0) {  // (ablations: the run table only; 1 and 2 write empty runs)
-        } else if (PAY) {  // codes and their chunk positions (half a stage buffer each)
+        if (PAY) {  // codes and their chunk positions (half a stage buffer each)
             const auto rp = buf_rsrc(P.surv_pos + (prev_out - P.surv), nbytes);
 #pragma unroll
             for (int k = 0; k < (kPC + 1) / 2; k++) {
@@ -1805,7 +1716,6 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
     };
     uint64_t filtered = 0;  // wave 0: survivors of this workgroup's items
     uint32_t nstep    = 0;  // items processed (selects the counter / stage buffers)
-    uint64_t abl_n    = 0;  // (probe ablations 1 and 2: this wave's survivors)
     // Outer loop: runs of items with one (q, seg), i.e. one slice segment in LDS. Inner loop:
     // the pieces of the run, software-pipelined: piece p is tested while p+1 and p+2 are in flight
     // (three register buffers rotate, so no load result is ever copied; past the end the loads
@@ -1849,7 +1759,6 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
             const uint32_t cb3 = nstep % 3;  // counter buffer of this piece
             load_chunks_u<kPC, kPrNT>(P.pool, en, lb_of(p2), le_of(p2), Sl);
             load_list_u<kPC>(P.list, lb_of(p3), le_of(p3), enn);
-            stamp(0);
             uint32_t* cnt = subc + cb3 * 128;
             uint32_t* scr = scratch + wave * kScrCap;
             // ---- test. One-bit kinds: all slice reads first, then per word slot the pass bit, its
@@ -1899,7 +1808,7 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
                 // wave ballot compacts the survivors there (no exec masking: the others write a
                 // shared garbage slot). Otherwise no scratch write at all (high selectivity: the
                 // words are ranked one by one, and 12 LDS writes per thread would buy nothing)
-                if (!PAY && kScrCap > 0 && nsv <= kScrCap && kAblProbe != 1) {  // wave-uniform
+                if (!PAY && kScrCap > 0 && nsv <= kScrCap) {  // wave-uniform
                     // lane-major: this lane's survivors from its exclusive prefix (the scan above) on.
                     // Word i goes to byte address dmy + t_i * x (t_i its pass bit, x = the next
                     // survivor slot - dmy, dmy the lane's garbage slot below the scratch): one bfe,
@@ -1932,9 +1841,7 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
             constexpr uint32_t kNoRank = 0xFFFFFFFFu;
             uint32_t   dr[kDense];
             uint32_t   rank2[NW / 2];            // word by word: two 16-bit ranks per register
-            if (kAblProbe == 1 || kAblProbe == 2) {
-                abl_n += nsv;
-            } else if (dense) {
+            if (dense) {
                 // KIND_BASIC_KK: bits 2..k of every slot's candidate from the slices in HBM, bit by
                 // bit, each bit loaded for all of the wave's live slots before any is tested
                 // (kDense loads in flight instead of one at a time); stops when no slot is live
@@ -2007,11 +1914,7 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
                     rank2[i / 2] = r[0] | (r[1] << 16);
                 }
             }
-            stamp(1);
-#ifndef HWBRJ_ABL_PNOB1  // (dev ablation, results invalid: the probe without its per-piece barrier)
             __syncthreads();  // B1: every rank of this piece taken; the previous piece staged
-#endif
-            stamp(2);
             // ---- every wave: run offsets of this piece (DPP scan over the NSUB counters)
             const uint32_t cs    = lane < (int) NSUB ? cnt[lane] : 0u;
             const uint32_t incl  = wave_incl_scan_dpp(cs);
@@ -2025,14 +1928,12 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
                 subo_v = incl - cs;
                 filtered += total;
             }
-            stamp(3);
             uint32_t* __restrict__ out = P.surv + (uint64_t) seg * P.surv_seg_stride + (uint64_t) lb_of(p) * 32;
             const uint32_t buf    = nstep & 1u;
             const bool     staged = PAY ? total <= hp : total <= scap;
             uint32_t*      stg    = stage + buf * sstr;
             const auto     ro     = buf_rsrc(out, total * 4);
-            if (kAblProbe == 1 || kAblProbe == 2) {
-            } else if (dense) {
+            if (dense) {
 #pragma unroll
                 for (int k = 0; k < kDense; k++) {
                     const bool     ok = dr[k] != kNoRank;
@@ -2064,7 +1965,6 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
                                                               rpo, oo, 0, 0);
                 }
             }
-            stamp(4);
             prev_total = staged ? total : 0u;
             prev_pk    = pk3 && staged;
             n_unst += staged ? 0u : 1u;
@@ -2073,7 +1973,6 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
             prev_it    = rit0 + (p - p0);
             prev_q     = q;
             nstep++;
-            stamp(5);
         };
         for (uint32_t p = p0; p < p1; p += 3) {
             step(p, SA, SC, eC, eA);
@@ -2086,10 +1985,6 @@ __global__ __launch_bounds__(1024) void k_probe(ProbeParams P) {
     copy_out();
     if (tid == 0 && filtered) atomicAdd((unsigned long long*) P.filtered, (unsigned long long) filtered);
     if (tid == 0 && n_unst && P.fmt_cnt) atomicAdd(P.fmt_cnt, n_unst);
-    if (kAblProbe == 1 || kAblProbe == 2)
-        if (lane == 0 && abl_n) atomicAdd((unsigned long long*) P.filtered, (unsigned long long) abl_n);
-    if (P.dbg && tid == 0)
-        for (int k = 0; k < 6; k++) P.dbg[blockIdx.x * 8 + k] = tph[k];
 }
 
 // ================================================ K7b: basic k >= 2, one bit per pass
@@ -2420,22 +2315,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
     auto probe_end = [&]() {
         if (P.timing) t_probe += wall_clock64() - t_mark;
     };
-    // dev-only phase stamps of wave 0 (build with -DHWBRJ_STAMPS, run with HWBRJ_DBG): fused path
-    // 0 descriptors, 1 R loads + bit sets, 2 popcount, 3 first survivor runs, 4 further runs, 5 sum
-    uint64_t tph[6] = {0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
-    (void) tlast;
-    (void) tph;
-    auto stamp = [&](int k) {
-#ifdef HWBRJ_STAMPS
-        if (P.dbg) {
-            const uint64_t t = __builtin_amdgcn_s_memtime();
-            tph[k] += t - tlast;
-            tlast = t;
-        }
-#else
-        (void) k;
-#endif
-    };
     // Run formats. A run is addressed by a tag tb from its array's base: bit 63 set = packed keys
     // (P.r_kbits = kw bits each: 18 or 24), tb their bit address, key o the kw bits at tb + kw o
     // (the unaligned dword at byte (tb + kw o) >> 3, shifted by (tb + kw o) & 7); else 32-bit codes at
@@ -2614,7 +2493,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
             rbase[tid]       = rtag(w0 + tid, P.r_off[r]);
             rc = rcnt[tid];
         }
-        stamp(0);
         if (wave == 0) {  // the job's R keys (nRd <= 64: every R descriptor is in wave 0)
             const uint32_t t = __builtin_amdgcn_readlane(wave_incl_scan_dpp(rc), 63);
             if (lane == 0) npieces = t;
@@ -2641,9 +2519,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
         for (int r = 0; r < FR; r++) {
             const uint32_t dd = wave + r * kJoinWaves;
             rn[r]             = dd < nRd ? rcnt[dd] : 0u;
-#ifdef HWBRJ_ABL_JNOR
-            rn[r] = 0;  // dev ablation (results invalid)
-#endif
             const uint64_t bb = dd < nRd ? rbase[dd] : 0ull;
             r7m |= b7_of(bb) << (3 * r);
 #pragma unroll
@@ -2656,9 +2531,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
         for (int r = 0; r < FS; r++) {
             const uint32_t dd = wave + r * kJoinWaves;
             sn[r]             = dd < nSd ? dcnt[dd] : 0u;
-#ifdef HWBRJ_ABL_JNOS
-            sn[r] = 0;  // dev ablation (results invalid)
-#endif
             const uint64_t bb = dd < nSd ? dbase[dd] : 0ull;
             spk |= (uint32_t) (bb >> 63) << r;
             s7m |= b7_of(bb) << (3 * r);
@@ -2682,7 +2554,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
             }
         }
         __syncthreads();
-        stamp(1);
         {
             uint32_t pc = 0;
             for (uint32_t i = tid; i < kJoinWords / 4; i += kJoinThreads) {
@@ -2694,7 +2565,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
         }
         __syncthreads();
         hashed = dupflag != npieces;  // uniform
-        stamp(2);
         if (!hashed) {
             probe_begin();
             auto test = [&](uint32_t x) { cnt += (tab[x >> 5] >> (x & 31u)) & 1u; };
@@ -2708,11 +2578,7 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
                     tail_run(SideS{}, bb, 64u * FSW, sn[r], test);
                 }
             }
-            stamp(3);
-#ifndef HWBRJ_ABL_JNOS
             walk(SR{}, SW{}, SideS{}, dcnt, dbase, (uint32_t) (kJoinWaves * FS), nSd, test);
-#endif
-            stamp(4);
             probe_end();
             done = true;
         }
@@ -2817,11 +2683,6 @@ __device__ __forceinline__ void join_job(const JoinParams& P, const uint32_t blk
     }
     cnt_acc += cnt;
     tp_acc += t_probe;
-    stamp(5);
-#ifdef HWBRJ_STAMPS
-    if (P.dbg && tid == 0)
-        for (int k = 0; k < 6; k++) atomicAdd((unsigned long long*) &P.dbg[(blk & 1023u) * 8 + k], (unsigned long long) tph[k]);
-#endif
 }
 
 // The uniform-format join (every launch without unstaged probe items, the north star's) and the
@@ -2988,14 +2849,6 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(8))
     // together, so the job costs four dependent global round trips
     if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
         const uint32_t nrd = r1 - r0, nsd = qi1 - qi0;
-#ifdef HWBRJ_ABL_MJ_EMPTY  // dev ablation (results invalid): descriptors only
-        if (nrd != 0x12345) {
-            uint32_t c0 = (uint32_t) tid < nrd ? P.r_cnt[(uint64_t) (r0 + tid) * NSUB + s] : 0u, t0;
-            c0 = mat_block_scan(c0, wsum, t0);
-            if (t0 == 0x12345678u) P.out[0] = make_uint2(c0, 0);
-            return;
-        }
-#endif
         uint32_t       rcn = 0, scn = 0;
         if ((uint32_t) tid < nrd) {
             const uint64_t r = (uint64_t) (r0 + tid) * NSUB + s;
@@ -3111,15 +2964,10 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(8))
             for (int k = 0; k < kMatU; k++) {
                 const uint32_t e = tid + k * kMatThreads;
                 if (e < rtot) {
-#ifdef HWBRJ_ABL_MJ_NOLOAD  // dev ablation (results invalid): no R loads
-                    rc[k] = e * 2654435761u;
-                    rp[k] = e;
-#else
                     const uint32_t d  = mat_find(rpre, nrd, e);
                     const uint64_t ra = rbase[d] + (e - rpre[d]);
                     rc[k] = P.r_codes[ra];
                     rp[k] = P.r_pay[ra];
-#endif
                 }
                 v[k] = kEmpty;
                 a[k] = 0;
@@ -3129,17 +2977,10 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(8))
                     v[k] = P.surv[a[k]] >> hs;
                 }
             }
-#ifdef HWBRJ_ABL_MJ_NOINS  // dev ablation (results invalid): R loaded, not inserted
-            if (rc[0] + rc[1] + rc[2] + rc[3] + rp[0] + rp[1] + rp[2] + rp[3] == 0x12345678u) P.out[0] = make_uint2(0, 0);
-            return;
-#endif
 #pragma unroll
             for (int k = 0; k < kMatU; k++)
                 if (tid + k * kMatThreads < rtot) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
             __syncthreads();  // table complete
-#ifdef HWBRJ_ABL_MJ_R  // dev ablation (results invalid): R table only
-            if (v[0] != 0x12345678u) return;
-#endif
             mat_count(tk, v, m);
             uint32_t cnt = 0;
 #pragma unroll
@@ -3264,7 +3105,7 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(8))
 
 void launch_join_mat(const MatJoinParams& p0, uint32_t jobs, hipStream_t st) {
     MatJoinParams p = p0;
-    p.xcd8          = ((jobs >> p.log2NSUB) % 8 == 0 && !dev_knobs().noxcd) ? 1u : 0u;
+    p.xcd8          = ((jobs >> p.log2NSUB) % 8 == 0) ? 1u : 0u;
     k_join_mat<<<jobs, kMatThreads, 0, st>>>(p);
 }
 
@@ -4238,11 +4079,6 @@ const char* kernel_build_knobs() {
         auto num = [&](const char* n, long v, long d) {
             if (v != d) r += std::string(r.empty() ? "" : " ") + n + "=" + std::to_string(v);
         };
-        auto flag = [&](const char* n) { r += std::string(r.empty() ? "" : " ") + n; };
-        (void) flag;
-#ifdef HWBRJ_DEV_BUILD
-        flag("HWBRJ_DEV_BUILD");
-#endif
         num("HWBRJ_SC_T", HWBRJ_SC_T, 1024);
         num("HWBRJ_SC_E", HWBRJ_SC_E, 8);
         num("HWBRJ_SC_K", HWBRJ_SC_K, 2);
@@ -4277,56 +4113,8 @@ const char* kernel_build_knobs() {
         num("HWBRJ_JBM", HWBRJ_JBM, 18);
         num("HWBRJ_OVL_ASYNC", HWBRJ_OVL_ASYNC, 1);
         num("HWBRJ_PJ_OVL", HWBRJ_PJ_OVL, 1);
-        num("HWBRJ_ABL_PROBE", HWBRJ_ABL_PROBE, 0);
         num("HWBRJ_PCO", HWBRJ_PCO, 1);
         num("HWBRJ_PCO_AUX", HWBRJ_PCO_AUX, 0);
-#define HWBRJ_FLAG_KNOB(X) flag(#X)
-#ifdef HWBRJ_STAMPS
-        HWBRJ_FLAG_KNOB(HWBRJ_STAMPS);
-#endif
-#ifdef HWBRJ_ABL_NOCRC
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_NOCRC);
-#endif
-#ifdef HWBRJ_ABL_NOCRAP
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_NOCRAP);
-#endif
-#ifdef HWBRJ_ABL_NOSTORE
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_NOSTORE);
-#endif
-#ifdef HWBRJ_ABL_SPLITH
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_SPLITH);
-#endif
-#ifdef HWBRJ_ABL_PNOPST
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_PNOPST);
-#endif
-#ifdef HWBRJ_ABL_BNOBITS
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_BNOBITS);
-#endif
-#ifdef HWBRJ_ABL_BNOSORT
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_BNOSORT);
-#endif
-#ifdef HWBRJ_ABL_PNOB1
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_PNOB1);
-#endif
-#ifdef HWBRJ_ABL_JNOR
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_JNOR);
-#endif
-#ifdef HWBRJ_ABL_JNOS
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_JNOS);
-#endif
-#ifdef HWBRJ_ABL_MJ_EMPTY
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_MJ_EMPTY);
-#endif
-#ifdef HWBRJ_ABL_MJ_NOLOAD
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_MJ_NOLOAD);
-#endif
-#ifdef HWBRJ_ABL_MJ_NOINS
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_MJ_NOINS);
-#endif
-#ifdef HWBRJ_ABL_MJ_R
-        HWBRJ_FLAG_KNOB(HWBRJ_ABL_MJ_R);
-#endif
-#undef HWBRJ_FLAG_KNOB
         return r;
     }();
     return s.c_str();

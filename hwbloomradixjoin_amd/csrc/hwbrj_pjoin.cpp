@@ -51,12 +51,6 @@ namespace hwbrj {
         }                                                                                  \
     } while (0)
 
-uint64_t pj_region_cap(uint64_t n, uint32_t G, uint32_t F) {
-    const uint64_t units = (n + 3) / 4;
-    const uint64_t per   = ((units + G - 1) / G) * 4;
-    return (per + 31) / 32 + F + 1;
-}
-
 template <class T>
 static int to_dev(DevBuf& b, const std::vector<T>& v, hipStream_t st) {
     if (!b.ensure(std::max<size_t>(16, v.size() * sizeof(T)))) return 4;
@@ -119,7 +113,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
     const uint32_t CH         = probe_chunks_per_item();
     const uint64_t BSW = build_chunks_per_sweep(), SLOT = build_sweep_slot();
     const size_t   sc_lds = scatter_lds_bytes(g.log2F);
-    const uint32_t G      = (uint32_t) cus_ * (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / sc_lds));
+    const uint32_t G      = (uint32_t) cus_ * wg_per_cu(sc_lds);
     hipStream_t    stream = own_stream_;
     // A callback transport runs its collectives on its own stream: the join stream is drained
     // before each (the native RCCL transport enqueues them on the join stream itself).
@@ -216,26 +210,18 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
     // ------------------------------------------------------------- 1. R shard: local partitions
     const int rc1 = [&]() -> int {
         if (pending_) PJ_CHECK(hipStreamWaitEvent(stream, ev_[8], 0));
-        capR = pj_region_cap(nR, G, F), capS = pj_region_cap(nS, G, F);
+        capR = region_cap(nR, G, F), capS = region_cap(nS, G, F);
         const uint64_t LR = (uint64_t) G * capR;
         LS = (uint64_t) G * capS;
         // (HWBRJ_HOOK_PJ_FAIL_RANK = r, tests: rank r fails this check, as an oversized shard would)
-        if (G > 512 || LS > (1ull << 27) || LR > (1ull << 27) || capS >= (1u << 22) || capR >= (1u << 22) ||
-            test_hooks().pj_fail_rank == rank) {
+        if (!part_fits(G, capR, capS) || test_hooks().pj_fail_rank == rank) {
             set_last_error("shard too large for 27-bit chunk ids");
             return 3;
         }
-        const uint64_t GF = (uint64_t) G * F;
-        bool ok = true;
-        ok &= poolR.ensure(LR * 128) && metaR.ensure(LR * 2) && listR.ensure(LR * 4);
-        ok &= usedR.ensure(G * 4) && wgqcR.ensure(GF * 4) && wgqeR.ensure(GF * 4) && wgqoR.ensure(GF * 4);
-        ok &= lstartR.ensure((F + 1) * 4) && estartR.ensure((F + 1) * 8) && istartR.ensure((F + 1) * 4);
-        ok &= poolS.ensure(LS * 128) && metaS.ensure(LS * 2) && listS.ensure(LS * 4);
-        ok &= usedS.ensure(G * 4) && wgqcS.ensure(GF * 4) && wgqeS.ensure(GF * 4) && wgqoS.ensure(GF * 4);
-        ok &= lstartS.ensure((F + 1) * 4) && estartS.ensure((F + 1) * 8) && istartS.ensure((F + 1) * 4);
+        bool ok = R_.ensure(LR, G, F) && S_.ensure(LS, G, F);
         const uint64_t items_max = (LS / CH + F + 1) * nseg;
         ok &= surv.ensure(nseg * LS * 128) && survcnt.ensure(items_max * NSUB * 4) && survoff.ensure(items_max * NSUB * 4);
-        ok &= small.ensure(128 + 64 * 128) && colR.ensure(F * 12) && colS.ensure(F * 12);
+        ok &= small.ensure(128 + 64 * 128);
         ok &= jtask.ensure((size_t) join_extra_tasks() * 8) && jparts.ensure((size_t) (2 * F * NSUB + 1) * 4);
         if (native) {
             // R received by this rank: its QL partitions' chunks from every source, each source
@@ -268,20 +254,11 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
         sp.g          = g;
         sp.src        = dR;
         sp.n          = nR;
-        sp.pool       = poolR.as<uint32_t>();
-        sp.meta       = metaR.as<uint32_t>();
-        sp.wg_used    = usedR.as<uint32_t>();
-        sp.wgq_chunks = wgqcR.as<uint32_t>();
-        sp.wgq_elems  = wgqeR.as<uint32_t>();
-        sp.cap        = capR;
+        R_.bind(&sp, capR);
         launch_scatter(sp, SRC_TUPLES, SIDE_R, G, stream);
-        launch_plan(wgqcR.as<uint32_t>(), wgqeR.as<uint32_t>(), G, g.log2F, wgqoR.as<uint32_t>(),
-                    colR.as<uint32_t>() + 2 * F, colR.as<uint64_t>(), stream);
-        launch_list_fill(metaR.as<uint32_t>(), usedR.as<uint32_t>(), capR, g.log2F, wgqoR.as<uint32_t>(),
-                         colR.as<uint32_t>() + 2 * F, colR.as<uint64_t>(), (uint32_t) BSW, 1, lstartR.as<uint32_t>(),
-                         estartR.as<uint64_t>(), istartR.as<uint32_t>(), listR.as<uint32_t>(), G, stream);
+        index_side(R_, capR, g.log2F, (uint32_t) BSW, 1, G, stream);
         if (native) return 0;  // (the counts message is built on the device)
-        PJ_CHECK(hipMemcpyAsync(ls.data(), lstartR.p, (F + 1) * 4, hipMemcpyDeviceToHost, stream));
+        PJ_CHECK(hipMemcpyAsync(ls.data(), R_.lstart.p, (F + 1) * 4, hipMemcpyDeviceToHost, stream));
         PJ_CHECK(hipStreamSynchronize(stream));
         const uint32_t nch = ls[F];
         sendC = x->buffer(x->ctx, HWBRJ_PJ_R_SEND, std::max<uint64_t>(16, (uint64_t) nch * 128));
@@ -291,7 +268,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
             return 20;
         }
         PJ_STAGE("R scatter");
-        launch_pj_gather(poolR.as<uint32_t>(), listR.as<uint32_t>(), nch, sendC, sendE, stream);
+        launch_pj_gather(R_.pool.as<uint32_t>(), R_.list.as<uint32_t>(), nch, sendC, sendE, stream);
         PJ_STAGE("k_pj_gather");
         // per destination j: chunks of its QL partitions, then the position of its block's first chunk
         for (uint32_t j = 0; j < W; j++) {
@@ -318,7 +295,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
         return 0;
     };
     if (native) {
-        if (const int rc = native_counts(lstartR.as<uint32_t>(), nullptr, rc1, nS, ls.data(), nullptr)) return rc;
+        if (const int rc = native_counts(R_.lstart.as<uint32_t>(), nullptr, rc1, nS, ls.data(), nullptr)) return rc;
         if (const int rc = peers(rcnt.data() + QL + 1, NC, rc1)) return rc;
         if (const int rc = check_r_total()) return rc;
         for (uint32_t j = 0; j < W; j++) {  // (the async join's plan: the largest R block)
@@ -338,7 +315,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
             own.out   = recvC;
             own.ent   = recvE;
         }
-        launch_pj_gather(poolR.as<uint32_t>(), listR.as<uint32_t>(), ls[F], sendC, sendE, stream, own);
+        launch_pj_gather(R_.pool.as<uint32_t>(), R_.list.as<uint32_t>(), ls[F], sendC, sendE, stream, own);
         PJ_STAGE("k_pj_gather");
     } else {
         for (uint32_t j = 0; j < W; j++) scnt[j * NC + QL + 1] = (uint64_t) (uint32_t) rc1;
@@ -485,25 +462,16 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
     const int rc5 = [&]() -> int {
         sp.src        = dS;
         sp.n          = nS;
-        sp.pool       = poolS.as<uint32_t>();
-        sp.meta       = metaS.as<uint32_t>();
-        sp.wg_used    = usedS.as<uint32_t>();
-        sp.wgq_chunks = wgqcS.as<uint32_t>();
-        sp.wgq_elems  = wgqeS.as<uint32_t>();
-        sp.cap        = capS;
+        S_.bind(&sp, capS);
         launch_scatter(sp, SRC_TUPLES, SIDE_S, G, stream);
-        launch_plan(wgqcS.as<uint32_t>(), wgqeS.as<uint32_t>(), G, g.log2F, wgqoS.as<uint32_t>(),
-                    colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), stream);
-        launch_list_fill(metaS.as<uint32_t>(), usedS.as<uint32_t>(), capS, g.log2F, wgqoS.as<uint32_t>(),
-                         colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), CH, nseg, lstartS.as<uint32_t>(),
-                         estartS.as<uint64_t>(), istartS.as<uint32_t>(), listS.as<uint32_t>(), G, stream);
+        index_side(S_, capS, g.log2F, CH, nseg, G, stream);
         ProbeParams pp{};
         pp.g               = g;
         pp.tabs            = d_tabs_;
-        pp.pool            = poolS.as<uint32_t>();
-        pp.list            = listS.as<uint32_t>();
-        pp.list_start      = lstartS.as<uint32_t>();
-        pp.item_start      = istartS.as<uint32_t>();
+        pp.pool            = S_.pool.as<uint32_t>();
+        pp.list            = S_.list.as<uint32_t>();
+        pp.list_start      = S_.lstart.as<uint32_t>();
+        pp.item_start      = S_.istart.as<uint32_t>();
         pp.slices          = slice_mode ? d_slices : nullptr;
         pp.surv            = surv.as<uint32_t>();
         pp.surv_seg_stride = LS * 32;
@@ -512,7 +480,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
         pp.filtered        = d_filtered;
         pp.job_surv        = jparts.as<uint32_t>() + F * NSUB;
         const size_t   pl_lds = probe_lds_bytes(g, nullptr);
-        const uint32_t PG     = (uint32_t) cus_ * (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / pl_lds));
+        const uint32_t PG     = (uint32_t) cus_ * wg_per_cu(pl_lds);
         launch_probe(pp, PG, stream);
         PJ_STAGE("S scatter + probe");
         // ------------------------------------------------------------- 6. survivor exchange
@@ -525,7 +493,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
             set_last_error("hipMalloc failed (device memory)");
             return 4;
         }
-        launch_pj_items(istartS.as<uint32_t>(), lstartS.as<uint32_t>(), survcnt.as<uint32_t>(), items_max, F, nseg,
+        launch_pj_items(S_.istart.as<uint32_t>(), S_.lstart.as<uint32_t>(), survcnt.as<uint32_t>(), items_max, F, nseg,
                         CH, LS * 32, NSUB, pjRegion.as<uint64_t>(), pjTot.as<uint32_t>(), pjBsum.as<uint64_t>(),
                         pjSoff.as<uint64_t>(), pjBound.as<uint64_t>(), stream);
         if (native) {
@@ -537,7 +505,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
             for (uint32_t j = 0; j < W; j++) {
                 const uint64_t nSj = rcnt[(uint64_t) j * NC + QL + 2];
                 nS_all += nSj;
-                RImax += ((uint64_t) G * pj_region_cap(nSj, G, F) / CH + F + 1) * nseg;
+                RImax += ((uint64_t) G * region_cap(nSj, G, F) / CH + F + 1) * nseg;
             }
             RWmax = nS_all;
             const uint32_t NJ  = QL * NSUB;
@@ -558,7 +526,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
             }
             return 0;  // (the counts message is built on the device)
         }
-        PJ_CHECK(hipMemcpyAsync(isS.data(), istartS.p, (F + 1) * 4, hipMemcpyDeviceToHost, stream));
+        PJ_CHECK(hipMemcpyAsync(isS.data(), S_.istart.p, (F + 1) * 4, hipMemcpyDeviceToHost, stream));
         PJ_CHECK(hipMemcpyAsync(bnd.data(), pjBound.p, (F + 1) * 8, hipMemcpyDeviceToHost, stream));
         PJ_CHECK(hipStreamSynchronize(stream));
         return 0;
@@ -612,7 +580,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
     };
     lap(4);
     if (native) {
-        if (const int rc = native_counts(istartS.as<uint32_t>(), pjBound.as<uint64_t>(), rc5, 0, isS.data(), bnd.data()))
+        if (const int rc = native_counts(S_.istart.as<uint32_t>(), pjBound.as<uint64_t>(), rc5, 0, isS.data(), bnd.data()))
             return rc;
         if (const int rc = peers(rcnt.data() + QL + 1, NC, rc5)) return rc;
         // (what follows allocates nothing: a failure here is a bug or a broken device, and returns)
@@ -775,7 +743,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
     jp.CH              = CH;
     jp.log2NSUB        = g.log2NSUB;
     jp.hash_shift      = g.hash_shift;
-    jp.bitmap          = (g.sub_shift > 0 && 32 - g.hash_shift <= join_bitmap_log2()) ? 1u : 0u;
+    jp.bitmap          = join_uses_bitmap(g) ? 1u : 0u;
     jp.jsum            = (uint64_t*) ((char*) small.p + 128);
     jp.nparts          = jparts.as<uint32_t>();
     jp.extra           = jtask.as<uint2>();

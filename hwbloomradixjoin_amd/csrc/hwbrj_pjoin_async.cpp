@@ -88,9 +88,9 @@ bool Engine::pj_geom(int world, int rank, uint64_t nR, uint64_t nR_total, uint64
     G->BSW        = build_chunks_per_sweep();
     G->SLOT       = build_sweep_slot();
     const size_t sc_lds = scatter_lds_bytes(g.log2F);
-    G->G         = (uint32_t) cus_ * (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / sc_lds));
-    G->capR      = pj_region_cap(nR, G->G, G->F);
-    G->capS      = pj_region_cap(nS, G->G, G->F);
+    G->G         = (uint32_t) cus_ * wg_per_cu(sc_lds);
+    G->capR      = region_cap(nR, G->G, G->F);
+    G->capS      = region_cap(nS, G->G, G->F);
     G->LS        = (uint64_t) G->G * G->capS;
     G->items_max = (uint32_t) ((G->LS / G->CH + G->F + 1) * G->nseg);
     G->NC        = G->QL + 4;
@@ -387,18 +387,9 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
         ss.g          = g;
         ss.src        = dS;
         ss.n          = nS;
-        ss.pool       = poolS.as<uint32_t>();
-        ss.meta       = metaS.as<uint32_t>();
-        ss.wg_used    = usedS.as<uint32_t>();
-        ss.wgq_chunks = wgqcS.as<uint32_t>();
-        ss.wgq_elems  = wgqeS.as<uint32_t>();
-        ss.cap        = G.capS;
+        S_.bind(&ss, G.capS);
         launch_scatter(ss, SRC_TUPLES, SIDE_S, G.G, st);
-        launch_plan(wgqcS.as<uint32_t>(), wgqeS.as<uint32_t>(), G.G, g.log2F, wgqoS.as<uint32_t>(),
-                    colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), st);
-        launch_list_fill(metaS.as<uint32_t>(), usedS.as<uint32_t>(), G.capS, g.log2F, wgqoS.as<uint32_t>(),
-                         colS.as<uint32_t>() + 2 * F, colS.as<uint64_t>(), G.CH, G.nseg, lstartS.as<uint32_t>(),
-                         estartS.as<uint64_t>(), istartS.as<uint32_t>(), listS.as<uint32_t>(), G.G, st);
+        index_side(S_, G.capS, g.log2F, G.CH, G.nseg, G.G, st);
     };
     const bool s_side = HWBRJ_PJ_OVL && !fail;
     if (s_side) {
@@ -421,20 +412,10 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
         sp.g          = g;
         sp.src        = dR;
         sp.n          = nR;
-        sp.pool       = poolR.as<uint32_t>();
-        sp.meta       = metaR.as<uint32_t>();
-        sp.wg_used    = usedR.as<uint32_t>();
-        sp.wgq_chunks = wgqcR.as<uint32_t>();
-        sp.wgq_elems  = wgqeR.as<uint32_t>();
-        sp.cap        = G.capR;
+        R_.bind(&sp, G.capR);
         launch_scatter(sp, SRC_TUPLES, SIDE_R, G.G, stream);
-        launch_plan(wgqcR.as<uint32_t>(), wgqeR.as<uint32_t>(), G.G, g.log2F, wgqoR.as<uint32_t>(),
-                    colR.as<uint32_t>() + 2 * F, colR.as<uint64_t>(), stream);
-        launch_list_fill(metaR.as<uint32_t>(), usedR.as<uint32_t>(), G.capR, g.log2F, wgqoR.as<uint32_t>(),
-                         colR.as<uint32_t>() + 2 * F, colR.as<uint64_t>(), (uint32_t) G.BSW, 1,
-                         lstartR.as<uint32_t>(), estartR.as<uint64_t>(), istartR.as<uint32_t>(),
-                         listR.as<uint32_t>(), G.G, stream);
-        launch_pj_counts(lstartR.as<uint32_t>(), nullptr, W, QL, NC, 0, nS, nR, rc1s, stream);
+        index_side(R_, G.capR, g.log2F, (uint32_t) G.BSW, 1, G.G, stream);
+        launch_pj_counts(R_.lstart.as<uint32_t>(), nullptr, W, QL, NC, 0, nS, nR, rc1s, stream);
     } else {
         PX_CHECK(hipMemcpyAsync(flag, &kFlagPeerFailed, 8, hipMemcpyHostToDevice, stream));
         if (const int rc = fail_msg(rc1s)) return rc;
@@ -442,7 +423,7 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
     // ---- 2. R exchange: blocks of BR chunks
     if (const int rc = pj_a2a_u64(c, rc1s, rc1r, NC)) return rc;
     if (!fail)
-        launch_pjx_gather(poolR.as<uint32_t>(), listR.as<uint32_t>(), lstartR.as<uint32_t>(), F, QL, W, p.BR, sendC,
+        launch_pjx_gather(R_.pool.as<uint32_t>(), R_.list.as<uint32_t>(), R_.lstart.as<uint32_t>(), F, QL, W, p.BR, sendC,
                           sendE, own, recvC, recvE, flag, stream);
     if (const int rc = xchg(HWBRJ_PJ_R_SEND, HWBRJ_PJ_R_RECV, p.BR * 128, "R chunks")) return rc;
     if (const int rc = xchg(HWBRJ_PJ_R_SEND_ENT, HWBRJ_PJ_R_RECV_ENT, p.BR * 4, "R chunk entries")) return rc;
@@ -482,10 +463,10 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
         ProbeParams pp{};
         pp.g               = g;
         pp.tabs            = d_tabs_;
-        pp.pool            = poolS.as<uint32_t>();
-        pp.list            = listS.as<uint32_t>();
-        pp.list_start      = lstartS.as<uint32_t>();
-        pp.item_start      = istartS.as<uint32_t>();
+        pp.pool            = S_.pool.as<uint32_t>();
+        pp.list            = S_.list.as<uint32_t>();
+        pp.list_start      = S_.lstart.as<uint32_t>();
+        pp.item_start      = S_.istart.as<uint32_t>();
         pp.slices          = G.slice_mode ? d_slices : nullptr;
         pp.surv            = surv.as<uint32_t>();
         pp.surv_seg_stride = G.LS * 32;
@@ -494,12 +475,12 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
         pp.filtered        = small.as<uint64_t>() + 2;
         pp.job_surv        = jparts.as<uint32_t>() + F * NSUB;
         const size_t   pl_lds = probe_lds_bytes(g, nullptr);
-        const uint32_t PG     = (uint32_t) cus_ * (uint32_t) std::max<size_t>(1, std::min<size_t>(2, 163840 / pl_lds));
+        const uint32_t PG     = (uint32_t) cus_ * wg_per_cu(pl_lds);
         launch_probe(pp, PG, stream);
-        launch_pj_items(istartS.as<uint32_t>(), lstartS.as<uint32_t>(), survcnt.as<uint32_t>(), G.items_max, F,
+        launch_pj_items(S_.istart.as<uint32_t>(), S_.lstart.as<uint32_t>(), survcnt.as<uint32_t>(), G.items_max, F,
                         G.nseg, G.CH, G.LS * 32, NSUB, pjRegion.as<uint64_t>(), pjTot.as<uint32_t>(),
                         pjBsum.as<uint64_t>(), pjSoff.as<uint64_t>(), pjBound.as<uint64_t>(), stream);
-        launch_pj_counts(istartS.as<uint32_t>(), pjBound.as<uint64_t>(), W, QL, NC, 0, 0, nR, rc2s, stream);
+        launch_pj_counts(S_.istart.as<uint32_t>(), pjBound.as<uint64_t>(), W, QL, NC, 0, 0, nR, rc2s, stream);
     } else if (const int rc = fail_msg(rc2s)) {
         return rc;
     }
@@ -507,7 +488,7 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
     if (const int rc = pj_a2a_u64(c, rc2s, rc2r, NC)) return rc;
     if (!fail)
         launch_pjx_surv_pack(surv.as<uint32_t>(), pjRegion.as<uint64_t>(), pjTot.as<uint32_t>(),
-                             pjSoff.as<uint64_t>(), istartS.as<uint32_t>(), pjBound.as<uint64_t>(),
+                             pjSoff.as<uint64_t>(), S_.istart.as<uint32_t>(), pjBound.as<uint64_t>(),
                              survcnt.as<uint32_t>(), F, QL, NSUB, p.BI, p.BW, sendS, sendM, own, recvS, recvM, flag,
                              stream);
     if (const int rc = xchg(HWBRJ_PJ_S_SEND, HWBRJ_PJ_S_RECV, p.BW * 4, "survivors")) return rc;
@@ -539,7 +520,7 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
         jp.CH              = G.CH;
         jp.log2NSUB        = g.log2NSUB;
         jp.hash_shift      = g.hash_shift;
-        jp.bitmap          = (g.sub_shift > 0 && 32 - g.hash_shift <= join_bitmap_log2()) ? 1u : 0u;
+        jp.bitmap          = join_uses_bitmap(g) ? 1u : 0u;
         jp.jsum            = (uint64_t*) ((char*) small.p + 128);
         jp.nparts          = jparts.as<uint32_t>();
         jp.extra           = jtask.as<uint2>();
@@ -548,7 +529,7 @@ int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int wor
         jp.split_surv      = test_hooks().join_split;
         jp.timing          = 0;
         launch_join(jp, NJ, pjJobs.as<uint32_t>(), stream);
-        launch_pjx_stat(rc1r, rc2r, lstartR.as<uint32_t>(), istartS.as<uint32_t>(), pjBound.as<uint64_t>(), W, QL,
+        launch_pjx_stat(rc1r, rc2r, R_.lstart.as<uint32_t>(), S_.istart.as<uint32_t>(), pjBound.as<uint64_t>(), W, QL,
                         NC, flag, stat, stream);
     } else {
         const uint64_t h[4] = {kFlagPeerFailed, 0, 0, 0};

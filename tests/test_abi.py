@@ -170,16 +170,21 @@ def test_product_build_reports_no_knobs(hw):
     assert "knobs" not in v, v
 
 
-def test_ablations_need_dev_build(tmp_path):
-    """A results-invalid ablation cannot slip into a product build: hwbrj_kernels.hip refuses
-    HWBRJ_ABL_* / HWBRJ_STAMPS unless HWBRJ_DEV_BUILD is defined (preprocessing only)."""
-    src = os.path.join(ROOT, "hwbloomradixjoin_amd", "csrc", "hwbrj_kernels.hip")
-    inc = ["-I", os.path.join(ROOT, "hwbloomradixjoin_amd", "csrc"), "-I", os.path.join(ROOT, "include")]
-    base = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-std=c++17", "-E", "-o", str(tmp_path / "k.i")] + inc
-    r = subprocess.run(base + ["-DHWBRJ_ABL_NOCRC", src], capture_output=True, text=True)
-    assert r.returncode != 0 and "dev builds only" in r.stderr, r.stderr[-2000:]
-    r = subprocess.run(base + ["-DHWBRJ_ABL_NOCRC", "-DHWBRJ_DEV_BUILD", src], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
+def test_no_dev_build_switches():
+    """There is one product and no dev build: no source of the library or its public header knows
+    a results-invalid ablation (HWBRJ_ABL_*), the in-kernel phase stamps (HWBRJ_STAMPS) or a dev
+    environment switch (HWBRJ_DEV_*, HWBRJ_DBG). A plain text search of those files."""
+    banned = ("HWBRJ_ABL_", "HWBRJ_STAMPS", "HWBRJ_DEV_", "HWBRJ_DBG")
+    files = []
+    for d in (os.path.join(ROOT, "hwbloomradixjoin_amd", "csrc"), os.path.join(ROOT, "include")):
+        files += [os.path.join(d, f) for f in sorted(os.listdir(d)) if os.path.isfile(os.path.join(d, f))]
+    assert len(files) >= 13, files  # (the sources were found)
+    hits = []
+    for path in files:
+        with open(path, errors="replace") as fh:
+            for no, line in enumerate(fh, 1):
+                hits += [f"{os.path.relpath(path, ROOT)}:{no}: {w}" for w in banned if w in line]
+    assert not hits, hits
 
 
 def test_bench_uses_pmc_traffic_only_for_the_profiled_library(tmp_path, hw):

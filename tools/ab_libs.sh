@@ -3,7 +3,7 @@
 # (tree = the in-tree libhwbrj.so, NAME = tools/abl_so/libhwbrj_NAME.so), one bench line each.
 #   bash tools/ab_libs.sh <tag> <passes> tree NAME [NAME ...]   (extra bench flags: $ABFLAGS)
 #   a variant VAR=VALUE runs the in-tree library with that environment variable set, NAME:VAR=VALUE
-#   the variant library NAME with it (dev builds read HWBRJ_DEV_*)
+#   the variant library NAME with it
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/$1; P=$2; shift 2

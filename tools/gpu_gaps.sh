@@ -1,7 +1,7 @@
 #!/bin/bash
 # North-star bench line plus a kernel trace of the same command, with the dispatch timeline of the
 # last join (per-kernel durations, start offsets, idle gaps between dispatches).
-#   bash tools/gpu_gaps.sh <tag> [extra env assignments for the A/B leg, e.g. HWBRJ_DEV_X=1]
+#   bash tools/gpu_gaps.sh <tag> [extra env assignments for the A/B leg, e.g. HWBRJ_LIB=tools/abl_so/libhwbrj_NAME.so]
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
