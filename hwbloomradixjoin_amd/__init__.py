@@ -22,7 +22,7 @@ __all__ = [
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
-    "export_filter", "hash_crc", "hash_crapwow", "lib", "LIB_PATH", "shard_range", "write_relation",
+    "export_filter", "tables_info", "tables_read", "hash_crc", "hash_crapwow", "lib", "LIB_PATH", "shard_range", "write_relation",
 ]
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -624,6 +624,63 @@ def export_filter(m_bits: int) -> np.ndarray:
     """The last join's filter in the reference's byte layout (m/8 uint8)."""
     out = np.empty(m_bits // 8, dtype=np.uint8)
     _err(lib().hwbrj_export_filter(out.ctypes.data, out.nbytes), "hwbrj_export_filter")
+    return out
+
+
+# include/hwbrj.h HWBRJ_TI_* (the words of hwbrj_tables_info, in order) and HWBRJ_TAB_*
+_TI_NAMES = ("mode", "format", "F", "NSUB", "sub_shift", "hash_shift", "nseg", "bitmap", "jkind",
+             "key_bits", "G", "CH", "BSW", "slot", "stage_cap", "sweeps", "items", "jobs", "mat",
+             "split", "sc_round", "sc_flushes", "j_fused", "j_fw", "j_fs", "j_waves", "j_desc",
+             "j_piece", "j_task_surv", "j_extra", "j_tail_u", "j_tail_s", "j_rw", "j_sw", "m_piece",
+             "m_desc", "m_rcap")
+(TAB_R_ELEM_START, TAB_S_ELEM_START, TAB_R_SWEEP_START, TAB_R_RUN_CNT, TAB_R_RUN_OFF, TAB_R_KEYS,
+ TAB_S_LIST_START, TAB_S_ITEM_START, TAB_SURV_CNT, TAB_SURV_OFF, TAB_NPARTS) = range(11)
+TAB_SURV_ITEM = 64
+_TAB_U64 = (TAB_R_ELEM_START, TAB_S_ELEM_START)
+# return codes of hwbrj_tables_info / hwbrj_tables_read
+TABLES_NONE, TABLES_PENDING, TABLES_OTHER_PIPELINE, TABLES_TOO_SMALL = 6, 12, 13, 7
+
+
+class TablesError(RuntimeError):
+    """hwbrj_tables_info / hwbrj_tables_read refused: .code is the library's return code."""
+
+    def __init__(self, code: int, what: str):
+        super().__init__(f"{what} failed ({code}): {lib().hwbrj_last_error().decode()}")
+        self.code = code
+
+
+def tables_info() -> dict:
+    """hwbrj_tables_info (test-only): the geometry, launch shape and kernel constants of the last
+    collected synchronous join on this device, by the names of _TI_NAMES. Raises TablesError."""
+    L = lib()
+    L.hwbrj_tables_info.restype = ctypes.c_int
+    L.hwbrj_tables_info.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    out = np.zeros(len(_TI_NAMES), dtype=np.uint64)
+    rc = L.hwbrj_tables_info(out.ctypes.data, out.shape[0])
+    if rc:
+        raise TablesError(rc, "hwbrj_tables_info")
+    return {n: int(v) for n, v in zip(_TI_NAMES, out)}
+
+
+def tables_read(which: int, item: Optional[int] = None) -> np.ndarray:
+    """hwbrj_tables_read (test-only): table `which` (TAB_*) of the last collected synchronous join as
+    a flat array (uint64 for the element starts, else uint32); TAB_SURV_ITEM with `item`: that probe
+    item's survivor region, raw. Raises TablesError."""
+    L = lib()
+    L.hwbrj_tables_read.restype = ctypes.c_int
+    L.hwbrj_tables_read.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+                                    ctypes.POINTER(ctypes.c_uint64)]
+    w = which + (int(item) if which == TAB_SURV_ITEM else 0)
+    need = ctypes.c_uint64()
+    rc = L.hwbrj_tables_read(w, None, 0, ctypes.byref(need))
+    if rc not in (0, TABLES_TOO_SMALL):
+        raise TablesError(rc, "hwbrj_tables_read")
+    out = np.zeros(need.value // 8 if which in _TAB_U64 else need.value // 4,
+                   dtype=np.uint64 if which in _TAB_U64 else np.uint32)
+    if need.value:
+        rc = L.hwbrj_tables_read(w, out.ctypes.data, out.nbytes, ctypes.byref(need))
+        if rc:
+            raise TablesError(rc, "hwbrj_tables_read")
     return out
 
 

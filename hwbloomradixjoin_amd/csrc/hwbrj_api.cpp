@@ -335,6 +335,18 @@ int hwbrj_export_filter(uint8_t* host_out, uint64_t nbytes) {
     return e->export_filter(host_out, nbytes);
 }
 
+int hwbrj_tables_info(uint64_t* out, int n) {
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;  // (last error set by engine_for_current_device)
+    return e->tables_info(out, n);
+}
+
+int hwbrj_tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t* bytes) {
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;  // (last error set by engine_for_current_device)
+    return e->tables_read(which, host_out, cap_bytes, bytes);
+}
+
 // src/bloom_filter.c:25-34 -- prints the reference's message and exits(1).
 void assert_args(bloom_filter_args_t* args) {
     if ((args->m & (args->m - 1)) != 0) {

@@ -308,6 +308,7 @@ void Engine::release() {
     ring_drop();
     jring_.release();
     have_filter_ = false;
+    tab_.state   = kTabNone;
 }
 
 // One join's result slot: 128 bytes of result words (read_join_counts), then k_join's partial sums
@@ -366,6 +367,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         return 2;
     }
     HWBRJ_CHECK(hipSetDevice(device_));
+    tab_.state = kTabNone;  // (buffers may grow or be rewritten from here on: tables_read)
     Geometry    g;
     std::string err;
     if (!plan_geometry(args, nR, &g, &err, mat != nullptr)) {
@@ -688,6 +690,25 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     pending_stream_ = stream;
     have_filter_  = args != nullptr;
     last_g_       = g;
+    {  // the shape of this join's tables (tables_info / tables_read)
+        tab_.state = kTabJoin;
+        tab_.sync  = phase_ev_;
+        tab_.mat   = mat != nullptr;
+        tab_.g     = g;
+        tab_.G     = G;
+        tab_.nseg  = nseg;
+        tab_.CH    = CH;
+        tab_.BSW   = (uint32_t) BSW;
+        tab_.SLOT  = (uint32_t) SLOT;
+        (void) probe_lds_bytes(g, &tab_.stage_cap, mat != nullptr);
+        tab_.jkind  = (uint32_t) jkind;
+        tab_.kbits  = kbits;
+        tab_.bitmap = mat ? ((g.sub_shift > 0 && 32 - g.hash_shift <= 17) ? 1u : 0u) : jp.bitmap;
+        tab_.split  = jp.split_surv;
+        tab_.NJ     = NJ;
+        tab_.sweeps_max = sweeps_max;
+        tab_.seg_stride = LS * 32;
+    }
     {
         JoinRec r;
         r.slot  = rslot;
@@ -919,6 +940,8 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     pending_stream_ = stream;
     have_filter_  = true;
     last_g_       = g;
+    tab_.state    = kTabOther;  // (the repartitioning passes' tables: not read back)
+    tab_.sync     = phase_ev_;
     {
         JoinRec r;
         r.slot  = rslot;
@@ -1120,6 +1143,150 @@ int Engine::export_filter(uint8_t* host_out, uint64_t nbytes) {
     HWBRJ_CHECK(hipStreamSynchronize(own_stream_));
     HWBRJ_CHECK(hipMemcpy(host_out, tmp.p, nbytes, hipMemcpyDeviceToHost));
     tmp.release();
+    return 0;
+}
+
+// ---- test-only table readback (include/hwbrj.h hwbrj_tables_info / hwbrj_tables_read) ----
+int Engine::tables_ready() {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!jr_.empty() || !pj_q_.empty()) {  // (enqueued and not collected: its kernels may be running)
+        set_last_error("a join is pending (wait for it first)");
+        return 12;
+    }
+    if (tab_.state == kTabOther) {
+        set_last_error("the last join's pipeline keeps other tables (basic k >= 2, partitioned joins)");
+        return 13;
+    }
+    if (tab_.state != kTabJoin || !tab_.sync) {
+        set_last_error("no synchronous join has completed");
+        return 6;
+    }
+    return 0;
+}
+
+int Engine::tables_info(uint64_t* out, int n) {
+    if (const int rc = tables_ready()) return rc;
+    if (!out || n < HWBRJ_TI_COUNT) {
+        set_last_error("out must hold HWBRJ_TI_COUNT words");
+        return 7;
+    }
+    const TabRec&  t = tab_;
+    const uint32_t F = 1u << t.g.log2F;
+    uint32_t       sweeps = 0, items = 0;
+    HWBRJ_CHECK(hipMemcpy(&sweeps, R_.istart.as<uint32_t>() + F, 4, hipMemcpyDeviceToHost));
+    HWBRJ_CHECK(hipMemcpy(&items, S_.istart.as<uint32_t>() + F, 4, hipMemcpyDeviceToHost));
+    const PathConstants c = path_constants();
+    for (int i = 0; i < n; i++) out[i] = 0;
+    out[HWBRJ_TI_MODE]        = (uint64_t) t.g.mode;
+    out[HWBRJ_TI_FORMAT]      = (uint64_t) t.g.s_format;
+    out[HWBRJ_TI_F]           = F;
+    out[HWBRJ_TI_NSUB]        = 1u << t.g.log2NSUB;
+    out[HWBRJ_TI_SUB_SHIFT]   = t.g.sub_shift;
+    out[HWBRJ_TI_HASH_SHIFT]  = t.g.hash_shift;
+    out[HWBRJ_TI_NSEG]        = t.nseg;
+    out[HWBRJ_TI_BITMAP]      = t.bitmap;
+    out[HWBRJ_TI_JKIND]       = t.jkind;
+    out[HWBRJ_TI_KEY_BITS]    = t.kbits ? t.kbits : 32u;
+    out[HWBRJ_TI_GRID]        = t.G;
+    out[HWBRJ_TI_CH]          = t.CH;
+    out[HWBRJ_TI_BSW]         = t.BSW;
+    out[HWBRJ_TI_SLOT]        = t.SLOT;
+    out[HWBRJ_TI_STAGE_CAP]   = t.stage_cap;
+    out[HWBRJ_TI_SWEEPS]      = sweeps;
+    out[HWBRJ_TI_ITEMS]       = items;
+    out[HWBRJ_TI_JOBS]        = t.NJ;
+    out[HWBRJ_TI_MAT]         = t.mat ? 1u : 0u;
+    out[HWBRJ_TI_SPLIT]       = t.split ? t.split : c.join_task_surv;
+    out[HWBRJ_TI_SC_ROUND]    = c.sc_round;
+    out[HWBRJ_TI_SC_FLUSHES]  = c.sc_flushes;
+    out[HWBRJ_TI_J_FUSED]     = c.join_fused_sweeps;
+    out[HWBRJ_TI_J_FW]        = c.join_fw;
+    out[HWBRJ_TI_J_FS]        = c.join_fs;
+    out[HWBRJ_TI_J_WAVES]     = c.join_waves;
+    out[HWBRJ_TI_J_DESC]      = c.join_desc;
+    out[HWBRJ_TI_J_PIECE]     = c.join_piece;
+    out[HWBRJ_TI_J_TASK_SURV] = c.join_task_surv;
+    out[HWBRJ_TI_J_EXTRA]     = c.join_extra;
+    out[HWBRJ_TI_J_TAIL_U]    = c.join_tail_u;
+    out[HWBRJ_TI_J_TAIL_S]    = c.join_tail_s;
+    out[HWBRJ_TI_J_RW]        = c.join_rw;
+    out[HWBRJ_TI_J_SW]        = c.join_sw;
+    out[HWBRJ_TI_M_PIECE]     = c.mat_piece;
+    out[HWBRJ_TI_M_DESC]      = c.mat_desc;
+    out[HWBRJ_TI_M_RCAP]      = c.mat_rcap;
+    return 0;
+}
+
+int Engine::tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t* bytes) {
+    if (const int rc = tables_ready()) return rc;
+    const TabRec&  t = tab_;
+    const uint32_t F = 1u << t.g.log2F, NSUB = 1u << t.g.log2NSUB;
+    if (bytes) *bytes = 0;
+    const void* src  = nullptr;
+    uint64_t    need = 0;
+    auto last = [&](const DevBuf& b, uint32_t* v) -> int {  // entry [F] of a u32 start table
+        HWBRJ_CHECK(hipMemcpy(v, b.as<uint32_t>() + F, 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    uint32_t sweeps = 0, items = 0;
+    if (const int rc = last(R_.istart, &sweeps)) return rc;
+    if (const int rc = last(S_.istart, &items)) return rc;
+    if (which >= HWBRJ_TAB_SURV_ITEM) {
+        // one item's survivor region (k_probe's item regions, JoinParams::surv): the words of its
+        // input chunks, at seg * seg_stride + (list_start[q] + piece * CH) * 32
+        const uint32_t it = (uint32_t) (which - HWBRJ_TAB_SURV_ITEM);
+        if (it >= items) {
+            set_last_error("no such probe item");
+            return 2;
+        }
+        std::vector<uint32_t> is(F + 1), ls(F + 1);
+        HWBRJ_CHECK(hipMemcpy(is.data(), S_.istart.p, (F + 1) * 4, hipMemcpyDeviceToHost));
+        HWBRJ_CHECK(hipMemcpy(ls.data(), S_.lstart.p, (F + 1) * 4, hipMemcpyDeviceToHost));
+        const uint32_t q = (uint32_t) (std::upper_bound(is.begin(), is.end(), it) - is.begin()) - 1;
+        const uint32_t npc = (is[q + 1] - is[q]) / t.nseg, local = it - is[q];
+        const uint32_t seg = local / npc, piece = local - seg * npc;
+        const uint32_t nch = std::min(t.CH, ls[q + 1] - ls[q] - piece * t.CH);
+        src  = surv.as<uint32_t>() + (uint64_t) seg * t.seg_stride + (uint64_t) (ls[q] + piece * t.CH) * 32;
+        need = (uint64_t) nch * 128;
+    } else {
+        switch (which) {
+            case HWBRJ_TAB_R_ELEM_START: src = R_.estart.p, need = (uint64_t) (F + 1) * 8; break;
+            case HWBRJ_TAB_S_ELEM_START: src = S_.estart.p, need = (uint64_t) (F + 1) * 8; break;
+            case HWBRJ_TAB_R_SWEEP_START: src = R_.istart.p, need = (uint64_t) (F + 1) * 4; break;
+            case HWBRJ_TAB_R_RUN_CNT: src = rrun.p, need = (uint64_t) sweeps * NSUB * 4; break;
+            case HWBRJ_TAB_R_RUN_OFF:
+                src = rrun.as<uint32_t>() + t.sweeps_max * NSUB, need = (uint64_t) sweeps * NSUB * 4;
+                break;
+            case HWBRJ_TAB_R_KEYS: src = rjoin.p, need = (uint64_t) sweeps * t.SLOT * 4; break;
+            case HWBRJ_TAB_S_LIST_START: src = S_.lstart.p, need = (uint64_t) (F + 1) * 4; break;
+            case HWBRJ_TAB_S_ITEM_START: src = S_.istart.p, need = (uint64_t) (F + 1) * 4; break;
+            case HWBRJ_TAB_SURV_CNT: src = survcnt.p, need = (uint64_t) items * NSUB * 4; break;
+            case HWBRJ_TAB_SURV_OFF: src = survoff.p, need = (uint64_t) items * NSUB * 4; break;
+            case HWBRJ_TAB_NPARTS:
+                if (t.mat) {  // (k_join_split does not run before k_join_mat: one part per job)
+                    set_last_error("the materializing join has no parts table");
+                    return 13;
+                }
+                // nparts [NJ], then the extra-part count (jparts: nparts | job_surv | nextra)
+                need = (uint64_t) (t.NJ + 1) * 4;
+                if (bytes) *bytes = need;
+                if (cap_bytes < need || !host_out) {
+                    set_last_error("cap_bytes too small (*bytes holds the need)");
+                    return 7;
+                }
+                HWBRJ_CHECK(hipMemcpy(host_out, jparts.p, (size_t) t.NJ * 4, hipMemcpyDeviceToHost));
+                HWBRJ_CHECK(hipMemcpy((uint32_t*) host_out + t.NJ, jparts.as<uint32_t>() + 2 * t.NJ, 4,
+                                      hipMemcpyDeviceToHost));
+                return 0;
+            default: set_last_error("unknown table"); return 2;
+        }
+    }
+    if (bytes) *bytes = need;
+    if (cap_bytes < need || (need && !host_out)) {
+        set_last_error("cap_bytes too small (*bytes holds the need)");
+        return 7;
+    }
+    if (need) HWBRJ_CHECK(hipMemcpy(host_out, src, need, hipMemcpyDeviceToHost));
     return 0;
 }
 

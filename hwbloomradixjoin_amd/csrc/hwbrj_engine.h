@@ -95,6 +95,11 @@ class Engine {
     int  reserve(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                  const bloom_filter_args_t* args, int jkind = 0);
     int  export_filter(uint8_t* host_out, uint64_t nbytes);
+    // Test-only readback of the last collected synchronous join (include/hwbrj.h hwbrj_tables_info /
+    // hwbrj_tables_read): its geometry and launch shape, and one of its tables copied to the host.
+    // hipMemcpy only: no kernel, no device write.
+    int  tables_info(uint64_t* out, int n);
+    int  tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t* bytes);
     // The materializing join (the partitioned pipeline carrying payloads): st->matches = pairs
     // (all of them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
     int  run_mat(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
@@ -267,6 +272,19 @@ class Engine {
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                                   const Geometry& g, hipStream_t stream, int jkind);
+    // what tables_info / tables_read need of the last enqueued join: which pipeline left its tables
+    // in the buffers below, and the shape they are indexed with
+    enum { kTabNone = 0, kTabJoin = 1, kTabOther = 2 };  // kTabOther: a pipeline with other tables
+    struct TabRec {
+        int      state = kTabNone;
+        bool     sync = false, mat = false;
+        Geometry g{};
+        uint32_t G = 0, nseg = 1, CH = 0, BSW = 0, SLOT = 0, stage_cap = 0, jkind = 0, kbits = 0;
+        uint32_t bitmap = 0, split = 0, NJ = 0;
+        uint64_t sweeps_max = 0, seg_stride = 0;
+    };
+    TabRec       tab_;
+    int          tables_ready();  // 0, or why the tables cannot be read (the codes of hwbrj.h)
     CrcTables*   d_tabs_ = nullptr;
     GenPlan*     d_plan_ = nullptr;
     PartSide R_, S_;

@@ -213,6 +213,16 @@ uint32_t join_extra_tasks();
 uint32_t join_sum_slots();
 uint32_t join_sum_stride();
 uint32_t join_bitmap_log2();  // k_join's bitmap path: job keys v < 2^join_bitmap_log2()
+// The kernel constants the data-dependent paths of the scatter, k_join and k_join_mat depend on
+// (hwbrj_tables_info: tests derive their shapes from these instead of hard-coding them)
+struct PathConstants {
+    uint32_t sc_round, sc_flushes;                    // kScRound; kScK * kScThreads flush tasks per round
+    uint32_t join_waves, join_fused_sweeps, join_fw, join_fs;  // fused path: kJoinWaves * JFR sweeps, JFW, JFS
+    uint32_t join_desc, join_piece, join_task_surv, join_extra, join_tail_u, join_tail_s;
+    uint32_t join_rw, join_sw;                        // walk: words per lane of an R / a survivor run
+    uint32_t mat_piece, mat_desc, mat_rcap;           // k_join_mat: kMatPiece, kMatDesc, kMatRCap
+};
+PathConstants path_constants();
 void   launch_join_mat(const MatJoinParams& p, uint32_t jobs, hipStream_t st);
 // result materialization (K12): R table build, S probe writing (R.payload, S.payload) pairs
 void   launch_mat_build(const uint2* R, uint64_t n, unsigned long long* tab, uint64_t mask,

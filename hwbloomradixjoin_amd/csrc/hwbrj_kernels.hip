@@ -4064,6 +4064,27 @@ uint32_t join_extra_tasks() { return kJoinExtra; }
 uint32_t join_sum_slots() { return kJoinSumSlots; }
 uint32_t join_sum_stride() { return kJoinSumStride; }
 uint32_t join_bitmap_log2() { return kJoinBmLog2; }
+PathConstants path_constants() {
+    PathConstants c{};
+    c.sc_round          = kScRound;
+    c.sc_flushes        = (uint32_t) (kScK * kScThreads);
+    c.join_waves        = (uint32_t) kJoinWaves;
+    c.join_fused_sweeps = (uint32_t) (kJoinWaves * HWBRJ_JFR);
+    c.join_fw           = HWBRJ_JFW;
+    c.join_fs           = HWBRJ_JFS;
+    c.join_desc         = kJoinDesc;
+    c.join_piece        = kJoinPiece;
+    c.join_task_surv    = kJoinTaskSurv;
+    c.join_extra        = kJoinExtra;
+    c.join_tail_u       = kJoinTailU;
+    c.join_tail_s       = kJoinTailS;
+    c.join_rw           = HWBRJ_JRW;
+    c.join_sw           = HWBRJ_JSW;
+    c.mat_piece         = kMatPiece;
+    c.mat_desc          = kMatDesc;
+    c.mat_rcap          = kMatRCap;
+    return c;
+}
 
 void launch_export(const uint32_t* slices, const Geometry& g, uint32_t* out, uint64_t nwords,
                    hipStream_t st) {

@@ -88,6 +88,7 @@ int Engine::join_partitioned(const hwbrj_exchange_t* x, int rank, int world, con
                              uint64_t nR, uint64_t nR_total, const uint2* dS, uint64_t nS,
                              const bloom_filter_args_t* args, hwbrj_stats_t* st, bool native) {
     PJ_CHECK(hipSetDevice(device_));
+    tab_.state = kTabOther;  // (tables_read: this pipeline keeps other tables)
     const auto t_start = std::chrono::steady_clock::now();
     // Errors every rank sees alike (arguments, geometry): returned at once, on every rank.
     Geometry    g;

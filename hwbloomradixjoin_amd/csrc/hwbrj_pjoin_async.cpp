@@ -253,6 +253,7 @@ int Engine::pj_sync_join(const PjIn& in, hwbrj_stats_t* st) {
 int Engine::join_partitioned_async(const hwbrj_exchange_t* xa, int rank, int world, const uint2* dR, uint64_t nR,
                                    uint64_t nR_total, const uint2* dS, uint64_t nS, const bloom_filter_args_t* args) {
     PX_CHECK(hipSetDevice(device_));
+    tab_.state = kTabOther;  // (tables_read: this pipeline keeps other tables)
     PjX c;
     if (!xa) {
         if (!comm_) {

@@ -353,6 +353,79 @@ int hwbrj_write_result_relation(const result_t * res, const char * filename);
  * m/8 bytes, bit h of a block at byte h>>3, bit h&7). nbytes must be m/8. */
 int hwbrj_export_filter(uint8_t * host_out, uint64_t nbytes);
 
+/* Test-only readback of the tables the last collected synchronous join on this device left in HBM
+ * (hwbrj_join_device, hwbrj_join_device_algo, hwbrj_join_materialize_device), so tests can check
+ * every stage's output and tell which k_join path each (partition, sub) job must have taken. Both
+ * calls only copy device memory to the host: no kernel is launched, nothing on the device is
+ * written. They return 0, or
+ *    6  no synchronous join has completed on this device (or its buffers were released)
+ *   12  a join is pending (enqueued and not yet waited for): nothing is read
+ *   13  the last join's pipeline keeps other tables: basic k >= 2 (the repartitioning passes) and
+ *       the partitioned multi-GPU joins; also HWBRJ_TAB_NPARTS after a materializing join
+ *    7  out / host_out too small (hwbrj_tables_read: *bytes holds the need)
+ *    2  unknown table, or no such item
+ *   hwbrj_tables_info  out[HWBRJ_TI_COUNT] (n = capacity in words): that join's geometry and launch
+ *                      shape, and the kernel constants its data-dependent paths depend on.
+ *   hwbrj_tables_read  table `which` in the compact layout the kernels index; *bytes = its size.
+ *                      F, NSUB, sweeps, items, jobs, slot: the words of hwbrj_tables_info. */
+enum {
+    HWBRJ_TI_MODE = 0,    /* hwbrj_stats_t.mode */
+    HWBRJ_TI_FORMAT,      /* hwbrj_stats_t.format */
+    HWBRJ_TI_F,           /* partitions */
+    HWBRJ_TI_NSUB,        /* join sub-partitions per partition */
+    HWBRJ_TI_SUB_SHIFT,   /* sub = (code >> sub_shift) & (NSUB - 1); 0: the partition is no code digit */
+    HWBRJ_TI_HASH_SHIFT,  /* job key v = code >> hash_shift */
+    HWBRJ_TI_NSEG,        /* slice segments (probe items per piece) */
+    HWBRJ_TI_BITMAP,      /* 1: the join's direct-address bitmap holds the job keys */
+    HWBRJ_TI_JKIND,       /* HWBRJ_ALGO_* */
+    HWBRJ_TI_KEY_BITS,    /* bits per R key of the build's sweep slots: 18, 24, or 32 (codes) */
+    HWBRJ_TI_GRID,        /* scatter workgroups G */
+    HWBRJ_TI_CH,          /* chunks per probe item */
+    HWBRJ_TI_BSW,         /* chunks per build sweep */
+    HWBRJ_TI_SLOT,        /* words per build sweep slot */
+    HWBRJ_TI_STAGE_CAP,   /* survivors a probe item can stage (more: an unstaged item, 32-bit codes) */
+    HWBRJ_TI_SWEEPS,      /* build sweeps over all partitions */
+    HWBRJ_TI_ITEMS,       /* probe items over all partitions */
+    HWBRJ_TI_JOBS,        /* F * NSUB */
+    HWBRJ_TI_MAT,         /* 1: the materializing join (k_join_mat) */
+    HWBRJ_TI_SPLIT,       /* survivors per join part (HWBRJ_HOOK_JOIN_SPLIT, else kJoinTaskSurv) */
+    /* kernel constants (hwbrj_kernels.hip) */
+    HWBRJ_TI_SC_ROUND,    /* kScRound: elements per scatter workgroup round */
+    HWBRJ_TI_SC_FLUSHES,  /* kScK * kScThreads: flush tasks of a round before its "rare" loop */
+    HWBRJ_TI_J_FUSED,     /* kJoinWaves * HWBRJ_JFR: sweeps of a fused-path job (at most) */
+    HWBRJ_TI_J_FW,        /* HWBRJ_JFW: fused path, R words per lane before tail_run */
+    HWBRJ_TI_J_FS,        /* HWBRJ_JFS: fused path, survivor runs per wave loaded with R's */
+    HWBRJ_TI_J_WAVES,     /* kJoinWaves */
+    HWBRJ_TI_J_DESC,      /* kJoinDesc: run descriptors per batch */
+    HWBRJ_TI_J_PIECE,     /* kJoinPiece: R keys per hash-table piece */
+    HWBRJ_TI_J_TASK_SURV, /* kJoinTaskSurv */
+    HWBRJ_TI_J_EXTRA,     /* kJoinExtra: extra parts the task table holds */
+    HWBRJ_TI_J_TAIL_U,    /* kJoinTailU */
+    HWBRJ_TI_J_TAIL_S,    /* kJoinTailS */
+    HWBRJ_TI_J_RW,        /* HWBRJ_JRW: walk, words per lane of an R run before tail_run */
+    HWBRJ_TI_J_SW,        /* HWBRJ_JSW: ... of a survivor run */
+    HWBRJ_TI_M_PIECE,     /* kMatPiece: k_join_mat's R tuples per piece, survivors per batch */
+    HWBRJ_TI_M_DESC,      /* kMatDesc: its run descriptors per batch */
+    HWBRJ_TI_M_RCAP,      /* kMatRCap: R tuples of a job on its bitmap path (at most) */
+    HWBRJ_TI_COUNT
+};
+enum {
+    HWBRJ_TAB_R_ELEM_START = 0, /* u64 [F + 1]  first R element of each partition */
+    HWBRJ_TAB_S_ELEM_START,     /* u64 [F + 1]  S elements (the global-bitmap mode: its survivors) */
+    HWBRJ_TAB_R_SWEEP_START,    /* u32 [F + 1]  first build sweep of each partition */
+    HWBRJ_TAB_R_RUN_CNT,        /* u32 [sweeps][NSUB]  keys of each (sweep, sub) run */
+    HWBRJ_TAB_R_RUN_OFF,        /* u32 [sweeps][NSUB]  its key offset inside the sweep's slot */
+    HWBRJ_TAB_R_KEYS,           /* u32 [sweeps][slot]  the sweep slots, raw (packed keys or codes) */
+    HWBRJ_TAB_S_LIST_START,     /* u32 [F + 1]  first S chunk-list entry of each partition */
+    HWBRJ_TAB_S_ITEM_START,     /* u32 [F + 1]  first probe item of each partition */
+    HWBRJ_TAB_SURV_CNT,         /* u32 [items][NSUB]  survivors of each (item, sub) run */
+    HWBRJ_TAB_SURV_OFF,         /* u32 [items][NSUB]  its key offset in the item region; bit 31: packed */
+    HWBRJ_TAB_NPARTS,           /* u32 [jobs + 1]  parts of each job, then the extra parts requested */
+    HWBRJ_TAB_SURV_ITEM = 64    /* + item: u32 words of that probe item's survivor region, raw */
+};
+int hwbrj_tables_info(uint64_t * out, int n);
+int hwbrj_tables_read(int which, void * host_out, uint64_t cap_bytes, uint64_t * bytes);
+
 /* Cycles per second of the counter behind BPRO's "RUNTIME TOTAL, BUILD, PART (cycles)" line (the
  * reference's rdtsc timers, src/rdtsc.h:35-68), calibrated once against the steady clock. */
 uint64_t hwbrj_tsc_hz(void);
