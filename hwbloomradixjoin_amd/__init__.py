@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -118,6 +118,12 @@ def lib() -> ctypes.CDLL:
         L.hwbrj_join_materialize_device.argtypes = [
             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(_BloomArgs), ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(_Stats),
+            ctypes.POINTER(ctypes.c_double)]
+        L.hwbrj_join_semi_device.restype = ctypes.c_int
+        L.hwbrj_join_semi_device.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(_Stats),
             ctypes.POINTER(ctypes.c_double)]
         L.hwbrj_set_materialize.restype = None
@@ -506,6 +512,47 @@ def join_materialize_device(R, S, args: Optional[BloomFilterArgs] = None, stream
         capacity = n.value
     _err(rc, "hwbrj_join_materialize_device")
     stats = Stats(**{f: getattr(st2, f) for f, _ in _Stats._fields_})
+    return stats, out[: n.value], ms.value
+
+
+JOIN_SEMI, JOIN_ANTI = 0, 1  # include/hwbrj.h HWBRJ_JOIN_SEMI / HWBRJ_JOIN_ANTI
+
+
+def semi_join_device(R, S, args: Optional[BloomFilterArgs] = None, anti: bool = False, stream=None,
+                     capacity: Optional[int] = None):
+    """(Stats, rows, ms): the semi-join of device tensors S against R (hwbrj_join_semi_device) as a
+    (n, 2) int32 GPU tensor of whole S tuples {key, payload}, unordered: the S rows whose key occurs
+    in R, each once (anti=True: the S rows whose key does not). Stats.filtered is the counting join's
+    "S-tuples after filter", Stats.matches the row count; ms the device time. capacity: output rows
+    to allocate (None: one count-only call first; too small: the pipeline runs again at the exact
+    size)."""
+    import torch
+    _check_rel(R, S)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    kind = JOIN_ANTI if anti else JOIN_SEMI
+    n = ctypes.c_uint64()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_semi_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, kind, out, cap,
+                                            ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
+
+    if capacity is None:
+        rc = call(None, 0)  # count only
+        if rc not in (0, 7):
+            _err(rc, "hwbrj_join_semi_device")
+        capacity = n.value
+    for _ in range(2):
+        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=R.device)
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, "hwbrj_join_semi_device")
+    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
     return stats, out[: n.value], ms.value
 
 

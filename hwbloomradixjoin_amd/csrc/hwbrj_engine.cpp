@@ -301,7 +301,7 @@ void Engine::release() {
     for (DevBuf* b : {&slices, &bitmap, &rjoin, &rrun, &surv, &survcnt, &survoff,
                       &dense, &small, &bpos, &mtab, &mcount, &jtask, &jparts, &pjList,
                       &pjLstart, &pjSweep, &pjTab, &pjRegion, &pjTot, &pjSoff, &pjIbase, &pjCnt, &pjOff,
-                      &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
+                      &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &smark, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
         b->release();
     for (DevBuf& b : xslot_) b.release();
     if (pending_) (void) hipEventSynchronize(ev_[8]);  // (the ring's joins end before it is freed)
@@ -359,9 +359,18 @@ int Engine::run_mat(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     return rc ? rc : wait(st);
 }
 
+int Engine::run_semi(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+                     const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
+                     hwbrj_stats_t* st) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, &semi);
+    return rc ? rc : wait(st);
+}
+
+// mat / semi: the payload-carrying pipeline (pl below). mat carries both relations' payloads; semi
+// only S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
 int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                    const MatReq* mat) {
+                    const MatReq* mat, const SemiReq* semi) {
     if (jkind < 0 || jkind > 2) {
         set_last_error("unknown per-partition join algorithm");
         return 2;
@@ -370,15 +379,16 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     tab_.state = kTabNone;  // (buffers may grow or be rewritten from here on: tables_read)
     Geometry    g;
     std::string err;
-    if (!plan_geometry(args, nR, &g, &err, mat != nullptr)) {
+    const bool  pl = mat || semi;  // S payloads beside the words, the materializing geometry
+    if (!plan_geometry(args, nR, &g, &err, pl)) {
         set_last_error(err);
         return 2;
     }
-    if (mat && g.mode == MODE_GLOBAL) {
+    if (pl && g.mode == MODE_GLOBAL) {
         set_last_error("global-bitmap mode: materialized by the side pass");
         return kRcMatGlobal;
     }
-    if (!mat && g.mode == MODE_SLICE_BASIC && g.k > 1 && (uint64_t) g.k * nR <= (1ull << 31)) {
+    if (!pl && g.mode == MODE_SLICE_BASIC && g.k > 1 && (uint64_t) g.k * nR <= (1ull << 31)) {
         if (!stream) stream = own_stream_;
         if (pending_ && stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(stream, ev_[8], 0));
         return enqueue_basic_kk(dR, nR, dS, nS, g, stream, jkind);
@@ -392,7 +402,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     const bool     slice_mode = g.mode == MODE_SLICE_BLOCK || g.mode == MODE_SLICE_BASIC;
     const uint32_t nseg       = slice_mode ? g.nseg : 1;
     const uint32_t CH         = probe_chunks_per_item();  // chunks per probe item
-    const size_t   sc_lds     = mat ? scatter_pay_lds_bytes(g.log2F) : scatter_lds_bytes(g.log2F);
+    const size_t   sc_lds     = pl ? scatter_pay_lds_bytes(g.log2F) : scatter_lds_bytes(g.log2F);
     const uint32_t G          = (uint32_t) cus_ * wg_per_cu(sc_lds);
     // basic k >= 2: the S-side buffers first partition the R keys' k * |R| bit positions
     const bool     basic_kk = g.mode == MODE_SLICE_BASIC && g.k > 1;
@@ -417,7 +427,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         set_last_error("relation too large for 27-bit chunk ids (|S| or |R| > ~4.2e9 tuples per GPU)");
         return pre(3);
     }
-    if (mat && (capS >= (1u << 21) || capR >= (1u << 21))) {  // half indices (scatter_body_pay) < 2^22
+    if (pl && (capS >= (1u << 21) || capR >= (1u << 21))) {  // half indices (scatter_body_pay) < 2^22
         set_last_error("relation too large for the materializing scatter's 22-bit half indices");
         return pre(3);
     }
@@ -437,10 +447,13 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     if (slice_mode) ok &= slices.ensure((uint64_t) F * nseg * g.seg_words * 4);
     if (g.mode == MODE_GLOBAL) ok &= bitmap.ensure(((g.m + 31) / 32) * 4) && dense.ensure(nS * 4);
     if (basic_kk) ok &= bpos.ensure(nRk * 4);
-    if (mat) {
-        ok &= ppoolR.ensure(LR * 128) && ppoolS.ensure(LS * 128) && rpay.ensure(sweeps_max * SLOT * 4) &&
-              survpos.ensure(nseg * LS * 128);
-    }
+    if (pl) ok &= ppoolS.ensure(LS * 128) && survpos.ensure(nseg * LS * 128);
+    if (mat) ok &= ppoolR.ensure(LR * 128) && rpay.ensure(sweeps_max * SLOT * 4);
+    // the existence join's marks (one bit per S chunk position): anti, and the hash-set path's jobs
+    // of several R pieces
+    const bool semi_bm   = g.sub_shift > 0 && 32 - g.hash_shift <= 17;  // (k_join_mat's bitmap condition)
+    const bool semi_mark = semi && (semi->anti || !semi_bm);
+    if (semi_mark) ok &= smark.ensure(LS * 4);
     if (!ok) {
         set_last_error("hipMalloc failed (device memory)");
         return pre(4);
@@ -485,7 +498,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
             ss.n_dev = nullptr;
         }
         S_.bind(&ss, capS);
-        ss.ppool = mat ? ppoolS.as<uint32_t>() : nullptr;
+        ss.ppool = pl ? ppoolS.as<uint32_t>() : nullptr;
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
         launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : SRC_TUPLES, SIDE_S, G, st);
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
@@ -495,7 +508,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         return 0;
     };
     HWBRJ_CHECK(mark(0, stream));
-    const bool ovl = HWBRJ_OVL_ASYNC && !phase_ev_ && g.mode != MODE_GLOBAL && !basic_kk && !mat && !bcast;
+    const bool ovl = HWBRJ_OVL_ASYNC && !phase_ev_ && g.mode != MODE_GLOBAL && !basic_kk && !pl && !bcast;
     if (ovl) {  // S pass on the side stream (with phase events, its phases would show inside the R side's)
         if (!ovl_stream_) {
             HWBRJ_CHECK(hipStreamCreateWithFlags(&ovl_stream_, hipStreamNonBlocking));
@@ -556,7 +569,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     // 3-byte join keys from build / probe to k_join, unless the last join this Engine waited for had
     // probe items too large for the stage (their 32-bit survivor runs make the join read two formats,
     // k_join_mixed): a performance hint only, both paths give the same counts
-    const bool     pack3 = !mat && join_pack3(g) && pack3_hint_;
+    const bool     pack3 = !pl && join_pack3(g) && pack3_hint_;
     const uint32_t kbits = pack3 ? join_key_bits(g) : 0u;  // 18 at the north star
     bp.kbits       = kbits;
     // the broadcast: rank 0 builds the slices, the other ranks only sub-partition R for the join
@@ -613,10 +626,10 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     pp.surv_off        = survoff.as<uint32_t>();
     pp.filtered        = d_filtered;
     pp.job_surv        = jparts.as<uint32_t>() + NJ;
-    pp.surv_pos        = mat ? survpos.as<uint32_t>() : nullptr;
+    pp.surv_pos        = pl ? survpos.as<uint32_t>() : nullptr;
     pp.kbits           = kbits;
-    pp.fmt_cnt         = mat ? nullptr : (uint32_t*) sm + 10;  // (u64 word 5 of the slot: zeroed by the R scatter)
-    const size_t   pl_lds = probe_lds_bytes(g, nullptr, mat != nullptr);
+    pp.fmt_cnt         = pl ? nullptr : (uint32_t*) sm + 10;  // (u64 word 5 of the slot: zeroed by the R scatter)
+    const size_t   pl_lds = probe_lds_bytes(g, nullptr, pl);
     launch_probe(pp, (uint32_t) cus_ * wg_per_cu(pl_lds), stream);
     HWBRJ_CHECK(mark(6, stream));  // (survivor sub-partitioning is fused into k_probe: no ev_[7])
     surv_fused_ = true;
@@ -674,6 +687,50 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         mp.cap             = mat->cap;
         mp.count           = (unsigned long long*) d_result;
         launch_join_mat(mp, NJ, stream);
+    } else if (semi) {
+        HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));  // (as above)
+        if (semi_mark) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
+        SemiJoinParams sj{};
+        sj.r_codes         = jp.r_codes;
+        sj.r_sweep_start   = jp.r_sweep_start;
+        sj.r_cnt           = jp.r_cnt;
+        sj.r_off           = jp.r_off;
+        sj.slot            = jp.slot;
+        sj.surv            = jp.surv;
+        sj.surv_pos        = survpos.as<uint32_t>();
+        sj.surv_cnt        = jp.surv_cnt;
+        sj.surv_off        = jp.surv_off;
+        sj.item_start      = jp.item_start;
+        sj.list_start      = jp.list_start;
+        sj.surv_seg_stride = jp.surv_seg_stride;
+        sj.nseg            = nseg;
+        sj.CH              = CH;
+        sj.log2NSUB        = g.log2NSUB;
+        sj.hash_shift      = g.hash_shift;
+        sj.bm              = semi_bm ? 1u : 0u;
+        sj.anti            = semi->anti ? 1u : 0u;
+        sj.basic           = g.mode == MODE_SLICE_BASIC ? 1u : 0u;
+        sj.s_pay           = ppoolS.as<uint32_t>();
+        sj.mark            = semi_mark ? smark.as<uint32_t>() : nullptr;
+        sj.tabs            = d_tabs_;
+        sj.out             = semi->out;
+        sj.cap             = semi->cap;
+        sj.count           = (unsigned long long*) d_result;
+        launch_join_semi(sj, NJ, stream);
+        if (semi->anti) {  // every unmarked S tuple: the filter's rejects and the unmatched survivors
+            SemiEmitParams se{};
+            se.pool       = S_.pool.as<uint32_t>();
+            se.ppool      = ppoolS.as<uint32_t>();
+            se.list       = S_.list.as<uint32_t>();
+            se.list_start = S_.lstart.as<uint32_t>();
+            se.mark       = smark.as<uint32_t>();
+            se.g          = g;
+            se.tabs       = d_tabs_;
+            se.out        = semi->out;
+            se.cap        = semi->cap;
+            se.count      = (unsigned long long*) d_result;
+            launch_semi_emit(se, (uint32_t) cus_ * 2, stream);
+        }
     } else {
         launch_join(jp, NJ, jparts.as<uint32_t>() + NJ, stream);
     }
@@ -686,12 +743,12 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     pending_ev_   = phase_ev_;
     pending_sfirst_ = s_first;
     pending_fmt_    = pp.fmt_cnt != nullptr;
-    pending_slots_  = !mat;
+    pending_slots_  = !pl;
     pending_stream_ = stream;
     have_filter_  = args != nullptr;
     last_g_       = g;
     {  // the shape of this join's tables (tables_info / tables_read)
-        tab_.state = kTabJoin;
+        tab_.state = semi ? kTabOther : kTabJoin;  // (the existence join's tables: not read back)
         tab_.sync  = phase_ev_;
         tab_.mat   = mat != nullptr;
         tab_.g     = g;
@@ -700,7 +757,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         tab_.CH    = CH;
         tab_.BSW   = (uint32_t) BSW;
         tab_.SLOT  = (uint32_t) SLOT;
-        (void) probe_lds_bytes(g, &tab_.stage_cap, mat != nullptr);
+        (void) probe_lds_bytes(g, &tab_.stage_cap, pl);
         tab_.jkind  = (uint32_t) jkind;
         tab_.kbits  = kbits;
         tab_.bitmap = mat ? ((g.sub_shift > 0 && 32 - g.hash_shift <= 17) ? 1u : 0u) : jp.bitmap;
@@ -715,7 +772,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         r.args  = args != nullptr;
         r.fmt   = pending_fmt_;
         r.kbits = kbits;
-        r.slots = !mat;
+        r.slots = !pl;
         r.timed = rtimed;
         r.nS    = nS;
         r.g     = g;
@@ -1310,6 +1367,39 @@ int Engine::materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t 
         launch_mat_probe(dS, nS, dR, mtab.as<unsigned long long>(), T - 1, out, cap,
                          mcount.as<unsigned long long>(), g, slices.as<uint32_t>(),
                          bitmap.as<uint32_t>(), d_tabs_, stream);
+    }
+    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
+    HWBRJ_CHECK(hipGetLastError());
+    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
+    HWBRJ_CHECK(hipMemcpy(n, mcount.p, 8, hipMemcpyDeviceToHost));
+    if (ms) {
+        float f = 0;
+        HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
+        *ms = f;
+    }
+    return 0;
+}
+
+int Engine::semi_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const SemiReq& semi,
+                      uint64_t* n, hipStream_t stream, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    uint64_t T = 2;
+    while (T < 2 * nR) T <<= 1;
+    if (!mtab.ensure(T * 8) || !mcount.ensure(8)) {
+        set_last_error("hipMalloc failed (existence table)");
+        return 4;
+    }
+    HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
+    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 8, stream));
+    HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
+    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nS) {
+        Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
+        if (!have_filter_) g.mode = MODE_NOBLOOM;
+        launch_semi_probe(dS, nS, mtab.as<unsigned long long>(), T - 1, semi.anti ? 1u : 0u, semi.out, semi.cap,
+                          mcount.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(),
+                          d_tabs_, stream);
     }
     HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
     HWBRJ_CHECK(hipGetLastError());

@@ -27,7 +27,14 @@ struct MatReq {
     uint2*   out;
     uint64_t cap;
 };
-constexpr int kRcMatGlobal = 11;  // run_mat: global-bitmap mode, use the side pass (materialize)
+constexpr int kRcMatGlobal = 11;  // run_mat / run_semi: global-bitmap mode, use the side pass
+// An existence join's output: whole S tuples {key, payload} into out[0, cap). anti: the S tuples
+// without a partner in R (else those with one).
+struct SemiReq {
+    uint2*   out;
+    uint64_t cap;
+    bool     anti;
+};
 
 struct DevBuf {
     void*  p     = nullptr;
@@ -105,6 +112,15 @@ class Engine {
     int  run_mat(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                  const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
                  hwbrj_stats_t* st);
+    // The existence join (semi / anti) on the materializing pipeline's geometry: S carries its
+    // payloads, R does not (k_join_semi, and k_semi_emit for anti). st->matches = rows (all of
+    // them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
+    int  run_semi(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+                  const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
+                  hwbrj_stats_t* st);
+    // Its side pass after a counting join (global-bitmap mode): *n = number of rows.
+    int  semi_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const SemiReq& semi,
+                   uint64_t* n, hipStream_t stream, double* ms);
     // Side pass after a counting join (global-bitmap mode): (R.payload, S.payload) of every match
     // into out[0, cap); *n = number of pairs.
     int  materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, uint2* out,
@@ -268,7 +284,7 @@ class Engine {
     bool         alloc_only_   = false;  // reserve(): enqueue returns after its allocations
     int          enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                          const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                         const MatReq* mat = nullptr);
+                         const MatReq* mat = nullptr, const SemiReq* semi = nullptr);
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                                   const Geometry& g, hipStream_t stream, int jkind);
@@ -294,6 +310,7 @@ class Engine {
     // materializing pipeline: payload pools (chunk layout of R_.pool / S_.pool), R payloads of the
     // build sweeps, survivors' chunk positions
     DevBuf ppoolR, ppoolS, rpay, survpos;
+    DevBuf smark;  // existence join: one bit per S chunk position (matched survivors)
     DevBuf dense2, kkcnt;  // basic k >= 2: the second dense candidate buffer, per-pass counts
     DevBuf jtask, jparts;  // join task table; parts per job (+ the task count)
     // partitioned join: owned partitions' lists, tables and received survivor descriptors

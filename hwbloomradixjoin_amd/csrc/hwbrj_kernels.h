@@ -166,6 +166,59 @@ struct MatJoinParams {
     unsigned long long* count;      // += pairs (zero on entry)
 };
 
+// The existence join (k_join_semi): R codes of the build sweeps (no payloads), survivors + their
+// chunk positions. SEMI: {key, S.payload} of every survivor whose key is in R appended to out (up
+// to cap; count = all rows). ANTI: the matching survivors' chunk positions marked in `mark` (one
+// bit per S chunk position), for k_semi_emit.
+struct SemiJoinParams {
+    const uint32_t* r_codes;
+    const uint32_t* r_sweep_start;  // [F + 1]
+    const uint32_t* r_cnt;
+    const uint32_t* r_off;
+    uint32_t        slot;
+    const uint32_t* surv;
+    const uint32_t* surv_pos;       // ProbeParams::surv_pos
+    const uint32_t* surv_cnt;
+    const uint32_t* surv_off;
+    const uint32_t* item_start;
+    const uint32_t* list_start;
+    uint64_t        surv_seg_stride;
+    uint32_t        nseg, CH, log2NSUB, hash_shift;
+    uint32_t        bm;             // 1: job keys v = code >> hash_shift < 2^17 (the bitmap path)
+    uint32_t        xcd8;           // 1: XCD-aware job order (set by launch_join_semi)
+    uint32_t        anti;           // 1: mark only (k_semi_emit writes the rows)
+    uint32_t        basic;          // 1: the words are bmix(key) (MODE_SLICE_BASIC), else codes
+    const uint32_t* s_pay;          // S payload pool
+    uint32_t*       mark;           // [S chunks] bit i of word c: position 32 c + i matched (zero on
+                                    // entry; anti or !bm), or nullptr
+    const CrcTables* tabs;
+    uint2*          out;
+    uint64_t        cap;
+    unsigned long long* count;      // += rows (zero on entry)
+};
+void   launch_join_semi(const SemiJoinParams& p, uint32_t jobs, hipStream_t st);
+// ANTI's emission pass (k_semi_emit): {key, payload} of every S tuple of the chunk lists whose
+// position is not marked, appended to out (up to cap; *count += rows)
+struct SemiEmitParams {
+    const uint32_t*  pool;        // S chunk words
+    const uint32_t*  ppool;       // their payloads
+    const uint32_t*  list;        // S chunk lists
+    const uint32_t*  list_start;  // [F + 1]
+    const uint32_t*  mark;
+    Geometry         g;
+    const CrcTables* tabs;
+    uint2*           out;
+    uint64_t         cap;
+    unsigned long long* count;
+};
+void   launch_semi_emit(const SemiEmitParams& p, uint32_t grid, hipStream_t st);
+// the existence join's side pass (global-bitmap mode): every S tuple against launch_mat_build's
+// table of R, stopping at the first hit; rows {key, payload} on a hit (anti = 0) or on none
+void   launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
+                         uint32_t anti, uint2* out, uint64_t cap, unsigned long long* count,
+                         const Geometry& g, const uint32_t* slices, const uint32_t* bm,
+                         const CrcTables* tabs, hipStream_t st);
+
 void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                   hipStream_t st);
 void   launch_zipf(const int32_t* rnd, uint64_t cnt, uint64_t row0, const double* lut,

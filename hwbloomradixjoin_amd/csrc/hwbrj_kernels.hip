@@ -3830,6 +3830,372 @@ void launch_pjx_stat(const uint64_t* rc1, const uint64_t* rc2, const uint32_t* l
     k_pjx_stat<<<1, 1024, 0, st>>>(rc1, rc2, ls, is, bd, W, QL, NC, flag, out);
 }
 
+// ============================================================ K10s: the existence join (semi / anti)
+// One workgroup per (q, sub) job, like k_join_mat, but R is only asked "does this key exist": the
+// job's R codes (no payloads) set bits of an LDS bitmap (job keys v < 2^17: setting a bit is
+// idempotent, so duplicate R keys and any number of R tuples take this path) or go into an LDS hash
+// set (a key is stored once), in pieces of <= kMatPiece tuples. SEMI writes {key, S.payload} of every
+// survivor that hits, the key recovered from its word (code_key, or bunmix for the basic filters'
+// words), one output atomic per batch. A job whose R needs several hash pieces marks the hits of
+// every piece in `mark` (one bit per S chunk position) and writes the marked survivors after the
+// last piece: a survivor that matches in several pieces is written once. ANTI only marks, in both
+// paths: k_semi_emit then writes every unmarked S tuple, the ones the filter rejected and the
+// survivors without a partner alike. So a job without R tuples has nothing to do here under either
+// kind: under ANTI its survivors are unmarked and k_semi_emit writes them all.
+__device__ __forceinline__ void semi_insert(uint32_t* tk, uint32_t v) {
+    for (uint32_t h = mat_jslot(v);; h = (h + 1) & (kMatT - 1)) {
+        const uint32_t x = atomicCAS(&tk[h], kEmpty, v);
+        if (x == kEmpty || x == v) return;
+    }
+}
+__device__ __forceinline__ uint32_t semi_find(const uint32_t* tk, uint32_t v) {
+    for (uint32_t h = mat_jslot(v);; h = (h + 1) & (kMatT - 1)) {
+        const uint32_t x = tk[h];
+        if (x == kEmpty) return 0u;
+        if (x == v) return 1u;
+    }
+}
+
+__global__ __launch_bounds__(kMatThreads) void k_join_semi(SemiJoinParams P) {
+    // LDS: the bitmap (2^17 bits) or the hash set's slots (kEmpty: free; at most half full)
+    __shared__ uint32_t tk[kMatT];
+    static_assert(kMatT == kMatBmWords, "one LDS array for the bitmap and the hash set");
+    __shared__ uint32_t inv[128];
+    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
+    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
+    __shared__ uint32_t wsum[kMatThreads / 64];
+    __shared__ unsigned long long obase;
+    const int      tid  = threadIdx.x;
+    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
+    uint32_t job = blockIdx.x;
+    if (P.xcd8) {  // (k_join_mat's XCD-aware job order)
+        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
+        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
+    }
+    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
+    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
+    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
+    // (uniform) no survivors, or no R: nothing to write (SEMI) and nothing to mark (ANTI; the job's
+    // survivors stay unmarked, so k_semi_emit writes all of them)
+    if (r0 == r1 || qi0 == qi1) return;
+    load_tab(inv, &P.tabs->inv[0][0]);
+    const uint32_t lq0 = P.list_start[q];
+    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment
+    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
+        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
+        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
+        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
+               P.surv_off[(uint64_t) it * NSUB + s];
+    };
+    // R run descriptors [rd0, rd0 + nrd) into rbase / rpre; returns their tuples
+    auto r_batch = [&](uint32_t rd0, uint32_t nrd) {
+        __syncthreads();  // previous descriptors consumed
+        uint32_t c = 0;
+        if ((uint32_t) tid < nrd) {
+            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
+            c          = P.r_cnt[r];
+            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
+        }
+        uint32_t       rtot;
+        const uint32_t rx = mat_block_scan(c, wsum, rtot);
+        if ((uint32_t) tid < nrd) rpre[tid] = rx;
+        if (tid == 0) rpre[nrd] = rtot;
+        __syncthreads();
+        return rtot;
+    };
+    // the job's survivors, kMatPiece at a time: fn(address, word, valid mask) of this thread's kMatU
+    auto for_surv = [&](auto&& fn) {
+        for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {
+            const uint32_t nsd = min(kMatDesc, qi1 - sd0);
+            __syncthreads();  // table complete; previous descriptors consumed
+            uint32_t sc = 0;
+            if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
+            uint32_t       stot;
+            const uint32_t sx = mat_block_scan(sc, wsum, stot);
+            if ((uint32_t) tid < nsd) spre[tid] = sx;
+            if (tid == 0) spre[nsd] = stot;
+            __syncthreads();
+            for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {
+                uint64_t a[kMatU];
+                uint32_t c[kMatU], valid = 0;
+#pragma unroll
+                for (int k = 0; k < kMatU; k++) {
+                    const uint32_t e = e0 + tid + k * kMatThreads;
+                    a[k] = 0;
+                    c[k] = 0;
+                    if (e < stot) {
+                        const uint32_t d = mat_find(spre, nsd, e);
+                        a[k] = sbase[d] + (e - spre[d]);
+                        c[k] = P.surv[a[k]];
+                        valid |= 1u << k;
+                    }
+                }
+                fn(a, c, valid);
+            }
+        }
+    };
+    // rows of the survivors in `sel`: one output atomic per batch (contains barriers)
+    auto emit = [&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t sel) {
+        uint32_t pos[kMatU], sp[kMatU];
+#pragma unroll
+        for (int k = 0; k < kMatU; k++) pos[k] = (sel >> k) & 1u ? P.surv_pos[a[k]] : 0u;  // (in flight over the scan)
+        uint32_t       tot;
+        const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), wsum, tot);
+        if (tot == 0) return;  // (uniform)
+        if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
+#pragma unroll
+        for (int k = 0; k < kMatU; k++) sp[k] = (sel >> k) & 1u ? P.s_pay[pos[k]] : 0u;
+        __syncthreads();
+        uint64_t o = obase + off;
+#pragma unroll
+        for (int k = 0; k < kMatU; k++) {
+            if (!((sel >> k) & 1u)) continue;
+            const uint32_t key = P.basic ? bunmix(c[k]) : code_key(inv, c[k]);
+            if (o < P.cap) P.out[o] = make_uint2(key, sp[k]);
+            o++;
+        }
+    };
+    auto mark = [&](const uint64_t (&a)[kMatU], uint32_t sel) {
+#pragma unroll
+        for (int k = 0; k < kMatU; k++)
+            if ((sel >> k) & 1u) {
+                const uint32_t pos = P.surv_pos[a[k]];
+                atomicOr(&P.mark[pos >> 5], 1u << (pos & 31u));
+            }
+    };
+    if (P.bm) {  // (uniform) ---- bitmap path
+        for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) tk[i] = 0;
+        for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {
+            const uint32_t nrd  = min(kMatDesc, r1 - rd0);
+            const uint32_t rtot = r_batch(rd0, nrd);  // (its barriers: bitmap cleared)
+            for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
+                uint32_t rc[kMatU];
+#pragma unroll
+                for (int k = 0; k < kMatU; k++) {
+                    const uint32_t e = pb + tid + k * kMatThreads;
+                    rc[k] = 0;
+                    if (e < rtot) {
+                        const uint32_t d = mat_find(rpre, nrd, e);
+                        rc[k] = P.r_codes[rbase[d] + (e - rpre[d])];
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < kMatU; k++)
+                    if (pb + tid + k * kMatThreads < rtot) atomicOr(&tk[(rc[k] >> hs) >> 5], 1u << ((rc[k] >> hs) & 31u));
+            }
+        }
+        for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t valid) {
+            uint32_t hit = 0;
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                const uint32_t v = c[k] >> hs;
+                hit |= ((tk[v >> 5] >> (v & 31u)) & 1u) << k;
+            }
+            hit &= valid;
+            if (P.anti) mark(a, hit);
+            else emit(a, c, hit);
+        });
+        return;
+    }
+    // ---- hash-set path: R descriptor batches x R pieces x survivor batches
+    bool direct = false;  // the job's only piece wrote its rows itself (SEMI)
+    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {
+        const uint32_t nrd  = min(kMatDesc, r1 - rd0);
+        const uint32_t rtot = r_batch(rd0, nrd);
+        const bool     only = r1 - r0 <= kMatDesc && rtot <= kMatPiece;  // (uniform)
+        for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
+            const uint32_t pe = min(rtot, pb + kMatPiece);
+            __syncthreads();  // the previous piece's survivors are done with the set
+            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+            uint32_t rc[kMatU];
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                const uint32_t e = pb + tid + k * kMatThreads;
+                rc[k] = 0;
+                if (e < pe) {
+                    const uint32_t d = mat_find(rpre, nrd, e);
+                    rc[k] = P.r_codes[rbase[d] + (e - rpre[d])];
+                }
+            }
+            __syncthreads();  // set cleared
+#pragma unroll
+            for (int k = 0; k < kMatU; k++)
+                if (pb + tid + k * kMatThreads < pe) semi_insert(tk, rc[k] >> hs);
+            for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t valid) {
+                uint32_t hit = 0;
+#pragma unroll
+                for (int k = 0; k < kMatU; k++)
+                    if ((valid >> k) & 1u) hit |= semi_find(tk, c[k] >> hs) << k;
+                if (only && !P.anti) emit(a, c, hit);
+                else mark(a, hit);
+            });
+            direct = only;
+        }
+    }
+    if (P.anti || direct) return;  // (uniform)
+    // SEMI over several pieces: every piece has been seen, the marked survivors are the rows
+    __threadfence();
+    for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t valid) {
+        uint32_t hit = 0;
+#pragma unroll
+        for (int k = 0; k < kMatU; k++)
+            if ((valid >> k) & 1u) {
+                const uint32_t pos = P.surv_pos[a[k]];
+                // (the marks were set by atomics at the L2: read there, past this CU's vector cache)
+                const uint32_t w = __hip_atomic_load(&P.mark[pos >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                hit |= ((w >> (pos & 31u)) & 1u) << k;
+            }
+        emit(a, c, hit);
+    });
+}
+
+void launch_join_semi(const SemiJoinParams& p0, uint32_t jobs, hipStream_t st) {
+    SemiJoinParams p = p0;
+    p.xcd8           = ((jobs >> p.log2NSUB) % 8 == 0) ? 1u : 0u;
+    k_join_semi<<<jobs, kMatThreads, 0, st>>>(p);
+}
+
+// ANTI's emission pass. Workgroups take contiguous ranges of the S chunk lists, 256 chunks a batch
+// (8 threads per chunk, two chunks per thread, 16-byte loads); a tuple is written when its
+// position's mark bit is clear: {key recovered from its word, its payload}, one output atomic per
+// batch. The batch's rows are compacted in an LDS stage and copied out in order, so a store
+// instruction writes 512 contiguous bytes (a thread's own rows lie 64 bytes from its neighbour's).
+// The partition of a list position (packed words hold only the code's high part) comes from
+// list_start in LDS.
+constexpr int      kSeU     = 2;                 // chunks per thread per batch
+constexpr uint32_t kSeBatch = 128u * kSeU;       // chunks per batch (1024 threads)
+__global__ __launch_bounds__(1024) void k_semi_emit(SemiEmitParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint2* stage = (uint2*) lds;  // [kSeBatch * 32] rows of a batch
+    __shared__ uint32_t inv[128];
+    __shared__ uint32_t ls[(1u << kMaxLog2F) + 1];
+    __shared__ uint32_t wsum[16];
+    __shared__ unsigned long long obase;
+    const Geometry& g   = P.g;
+    const uint32_t  F   = 1u << g.log2F;
+    const uint32_t  tid = threadIdx.x, l8 = tid & 7u, cslot = tid >> 3;
+    load_tab(inv, &P.tabs->inv[0][0]);
+    for (uint32_t i = tid; i <= F; i += 1024) ls[i] = P.list_start[i];
+    __syncthreads();
+    const uint32_t L  = ls[F];
+    const uint32_t nb = (L + kSeBatch - 1) / kSeBatch;
+    const uint32_t b0 = (uint32_t) ((uint64_t) blockIdx.x * nb / gridDim.x);
+    const uint32_t b1 = (uint32_t) ((uint64_t) (blockIdx.x + 1) * nb / gridDim.x);
+    const bool     basic = g.mode == MODE_SLICE_BASIC;
+    const bool     packed = g.mode == MODE_SLICE_BLOCK && g.s_format == FMT_PACKED;
+    for (uint32_t b = b0; b < b1; b++) {
+        uint32_t ent[kSeU], sel[kSeU], lpos[kSeU];
+        uint4    w[kSeU], py[kSeU];
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) {
+            lpos[j] = b * kSeBatch + cslot + (uint32_t) j * 128u;
+            ent[j]  = lpos[j] < L ? P.list[lpos[j]] : kNoEntry;
+        }
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) {
+            sel[j] = 0;
+            w[j]   = make_uint4(0, 0, 0, 0);
+            py[j]  = make_uint4(0, 0, 0, 0);
+            if (lpos[j] < L) {
+                const uint32_t id = ent[j] & kListIdMask, cnt = list_count(ent[j]), first = l8 * 4u;
+                const uint32_t n  = cnt > first ? min(cnt - first, 4u) : 0u;
+                if (n) {  // (the payloads with the words: nearly every tuple is a row)
+                    w[j]   = *(const uint4*) &P.pool[(uint64_t) id * 32 + first];
+                    py[j]  = *(const uint4*) &P.ppool[(uint64_t) id * 32 + first];
+                    sel[j] = ((1u << n) - 1u) & ~(P.mark[id] >> first);
+                }
+            }
+        }
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) cnt += (uint32_t) __builtin_popcount(sel[j]);
+        uint32_t       tot;
+        const uint32_t off = block_excl_scan(cnt, wsum, tot);
+        if (tot == 0) continue;  // (uniform)
+        if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
+        uint32_t o = off;
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) {
+            if (!sel[j]) continue;
+            const uint32_t q = packed ? find_q(ls, F, lpos[j]) : 0u;
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (!((sel[j] >> t) & 1u)) continue;
+                const uint32_t x   = t == 0 ? w[j].x : t == 1 ? w[j].y : t == 2 ? w[j].z : w[j].w;
+                const uint32_t pay = t == 0 ? py[j].x : t == 1 ? py[j].y : t == 2 ? py[j].z : py[j].w;
+                const uint32_t key = basic ? bunmix(x)
+                                           : code_key(inv, packed ? ((x >> g.log2B) << g.log2F) | q : x);
+                stage[o++] = make_uint2(key, pay);
+            }
+        }
+        __syncthreads();  // the batch's rows staged, obase set
+        const uint64_t ob = obase;
+        for (uint32_t i = tid; i < tot; i += 1024)
+            if (ob + i < P.cap) P.out[ob + i] = stage[i];
+        __syncthreads();  // stage and obase reusable
+    }
+}
+
+void launch_semi_emit(const SemiEmitParams& p, uint32_t grid, hipStream_t st) {
+    const size_t lds = (size_t) kSeBatch * 32 * sizeof(uint2);
+    (void) hipFuncSetAttribute((const void*) &k_semi_emit, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    k_semi_emit<<<grid, 1024, lds, st>>>(p);
+}
+
+// The side pass of the global-bitmap mode (k_mat_probe's existence form): the walk of R's table
+// stops at the first hit; a tuple the filter rejects is a certain miss. Rows are staged in LDS and
+// appended with one atomic per flush (the stage always has room for a round of the workgroup).
+__global__ __launch_bounds__(256) void k_semi_probe(const uint2* __restrict__ S, uint64_t n,
+                                                     const unsigned long long* __restrict__ tab,
+                                                     uint64_t mask, uint32_t anti, uint2* __restrict__ out,
+                                                     uint64_t cap, unsigned long long* __restrict__ count,
+                                                     Geometry g, const uint32_t* __restrict__ slices,
+                                                     const uint32_t* __restrict__ bm,
+                                                     const CrcTables* __restrict__ tabs) {
+    __shared__ uint2              buf[kMatBuf];
+    __shared__ uint32_t           nbuf;
+    __shared__ unsigned long long obase;
+    const uint64_t e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
+    if (threadIdx.x == 0) nbuf = 0;
+    __syncthreads();
+    auto flush = [&]() {
+        const uint32_t c = nbuf;
+        if (threadIdx.x == 0) obase = c ? atomicAdd(count, (unsigned long long) c) : 0ull;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
+            if (obase + i < cap) out[obase + i] = buf[i];
+        __syncthreads();
+        if (threadIdx.x == 0) nbuf = 0;
+        __syncthreads();
+    };
+    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
+        const uint64_t i = t0 + threadIdx.x;
+        if (i < e1) {
+            const uint2 st  = S[i];
+            uint32_t    hit = 0;
+            if (mat_filter(st.x, g, slices, bm, tabs))
+                for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
+                    const unsigned long long e = tab[h];
+                    if (e == 0ull) break;
+                    if ((uint32_t) e == st.x) {
+                        hit = 1;
+                        break;
+                    }
+                }
+            if (hit != anti) buf[atomicAdd(&nbuf, 1u)] = st;  // (nbuf + 256 <= kMatBuf: the flush below)
+        }
+        __syncthreads();
+        if (nbuf > kMatBuf - 256) flush();  // uniform (read after the barrier)
+    }
+    flush();
+}
+
+void launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask, uint32_t anti,
+                       uint2* out, uint64_t cap, unsigned long long* count, const Geometry& g,
+                       const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
+    k_semi_probe<<<2048, 256, 0, st>>>(S, n, tab, mask, anti, out, cap, count, g, slices, bm, tabs);
+}
+
 // ===================================================================== launch wrappers
 void launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                 hipStream_t st) {

@@ -194,6 +194,28 @@ int hwbrj_join_materialize_device(const tuple_t * d_R, uint64_t nR, const tuple_
                                   uint64_t nS, const bloom_filter_args_t * args, tuple_t * d_out,
                                   uint64_t capacity, uint64_t * n_out, void * stream,
                                   hwbrj_stats_t * stats, double * ms_materialize);
+/* The existence joins of S against R: d_out receives whole S tuples {key, payload}, in no
+ * particular order. HWBRJ_JOIN_SEMI: every S row whose key occurs in R, each exactly once however
+ * many R rows share the key. HWBRJ_JOIN_ANTI: every S row whose key does not occur in R (NOT
+ * EXISTS). S rows that are equal as tuples are each written, so the output is a sub-multiset of S
+ * and SEMI and ANTI together are S. args == NULL runs without a filter; every filter
+ * configuration of hwbrj_join_materialize_device is accepted (the global-bitmap ones run the
+ * counting join and a side pass). The pipeline is the materializing join's with S's payloads only
+ * (R needs none); under ANTI the S tuples the filter rejects never enter sub-partitioning or the
+ * join: the join marks the survivors that have a partner and one pass over the partitioned S
+ * writes every unmarked tuple ("Existence joins").
+ * capacity is in rows: rows beyond it are not written, *n_out always holds the full row count and
+ * 7 is returned when it exceeds capacity; capacity 0 with d_out NULL is the count-only form.
+ * stats->filtered is "S-tuples after filter" as the counting join of the same arguments reports it
+ * (under ANTI too), stats->matches the row count. ms (optional) receives the device time. An
+ * unknown kind returns 2 before any device call. Synchronous and single-GPU; it collects pending
+ * async joins like the other synchronous entries, and hwbrj_tables_info / hwbrj_tables_read answer
+ * 13 after it. */
+enum { HWBRJ_JOIN_SEMI = 0, HWBRJ_JOIN_ANTI = 1 };
+int hwbrj_join_semi_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_S, uint64_t nS,
+                           const bloom_filter_args_t * args, int kind, tuple_t * d_out,
+                           uint64_t capacity, uint64_t * n_out, void * stream,
+                           hwbrj_stats_t * stats, double * ms);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
