@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -126,6 +126,12 @@ def lib() -> ctypes.CDLL:
             ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(_Stats),
             ctypes.POINTER(ctypes.c_double)]
+        L.hwbrj_join_outer_device.restype = ctypes.c_int
+        L.hwbrj_join_outer_device.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
         L.hwbrj_set_materialize.restype = None
         L.hwbrj_set_materialize.argtypes = [ctypes.c_int]
         L.hwbrj_set_gpus.restype = ctypes.c_int
@@ -554,6 +560,51 @@ def semi_join_device(R, S, args: Optional[BloomFilterArgs] = None, anti: bool = 
     _err(rc, "hwbrj_join_semi_device")
     stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
     return stats, out[: n.value], ms.value
+
+
+OUTER_S, OUTER_R, OUTER_FULL = 0, 1, 2  # include/hwbrj.h HWBRJ_OUTER_S / _R / _FULL
+
+
+def outer_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = OUTER_S,
+                      null_payload: int = -2**31, stream=None, capacity: Optional[int] = None):
+    """(Stats, rows, (n_inner, n_s_only, n_r_only), ms): the outer join of device tensors R and S
+    (hwbrj_join_outer_device) as a (n, 2) int32 GPU tensor of rows {R.payload, S.payload}, unordered:
+    every matching pair (join_materialize_device's multiset) and, under OUTER_S, a row
+    {null_payload, S.payload} for every S row whose key is not in R; under OUTER_R, a row
+    {R.payload, null_payload} for every R row whose key is not in S; under OUTER_FULL, both.
+    null_payload is the caller's marker and is not checked against the payloads. Stats.filtered is
+    the counting join's "S-tuples after filter", Stats.matches the row count; ms the device time.
+    capacity: output rows to allocate (None: one count-only call first; too small: the pipeline runs
+    again at the exact size)."""
+    import torch
+    _check_rel(R, S)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n = ctypes.c_uint64()
+    cls = (ctypes.c_uint64 * 3)()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_outer_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, int(kind),
+                                             int(null_payload), out, cap, ctypes.byref(n), cls, sp,
+                                             ctypes.byref(st), ctypes.byref(ms))
+
+    if capacity is None:
+        rc = call(None, 0)  # count only
+        if rc not in (0, 7):
+            _err(rc, "hwbrj_join_outer_device")
+        capacity = n.value
+    for _ in range(2):
+        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=R.device)
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, "hwbrj_join_outer_device")
+    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    return stats, out[: n.value], (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
 
 
 def copy_bandwidth(nbytes: int = 4 << 30, reps: int = 5) -> float:

@@ -315,6 +315,51 @@ int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, 
     return 0;
 }
 
+// The outer join: the materializing pipeline with marks over S and matched flags over R
+// (Engine::run_outer); the global-bitmap mode runs the counting join (its filter and its "S-tuples
+// after filter") and the outer side pass.
+int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                            const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
+                            uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
+                            hwbrj_stats_t* stats, double* ms) {
+    if (kind != HWBRJ_OUTER_S && kind != HWBRJ_OUTER_R && kind != HWBRJ_OUTER_FULL) {  // (before any device call)
+        set_last_error("unknown outer join kind (HWBRJ_OUTER_S, HWBRJ_OUTER_R, HWBRJ_OUTER_FULL)");
+        return 2;
+    }
+    if (capacity > 0 && !d_out) {
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;  // (last error set by engine_for_current_device)
+    const OuterReq req{(uint2*) d_out, capacity, kind != HWBRJ_OUTER_R, kind != HWBRJ_OUTER_S,
+                       (uint32_t) null_payload};
+    hwbrj_stats_t st;
+    uint64_t      n = 0, cls[3] = {0, 0, 0};
+    int rc = e->run_outer((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, req, &st, cls);
+    if (rc == 0) {
+        n = (uint64_t) st.matches;
+        if (ms) *ms = st.ms_total;
+    } else if (rc == kRcMatGlobal) {
+        rc = e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, &st);
+        if (rc) return rc;
+        rc = e->outer_side((const uint2*) d_R, nR, (const uint2*) d_S, nS, req, &n, cls, (hipStream_t) stream, ms);
+        if (rc) return rc;
+        st.matches = (int64_t) n;
+    } else {
+        return rc;
+    }
+    if (stats) *stats = st;
+    if (n_out) *n_out = n;
+    if (n_class)
+        for (int i = 0; i < 3; i++) n_class[i] = cls[i];
+    if (n > capacity) {
+        set_last_error("output capacity below the row count (*n_out holds the count)");
+        return 7;
+    }
+    return 0;
+}
+
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE
 static int g_gpus        = 0;   // shards of a host BPRO/PRO (0: from HWBRJ_GPUS, default 1)
 void hwbrj_set_materialize(int on) { g_materialize = on ? 1 : 0; }

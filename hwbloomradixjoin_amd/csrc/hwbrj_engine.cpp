@@ -366,11 +366,28 @@ int Engine::run_semi(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     return rc ? rc : wait(st);
 }
 
-// mat / semi: the payload-carrying pipeline (pl below). mat carries both relations' payloads; semi
-// only S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
+int Engine::run_outer(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+                      const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
+                      hwbrj_stats_t* st, uint64_t cls[3]) {
+    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, &outer);
+    if (rc == 0) rc = wait(st);
+    if (rc) return rc;
+    uint64_t c[2];  // (the join has completed; its ring slot is taken again by the next enqueue only)
+    HWBRJ_CHECK(hipMemcpy(c, outer_cls_, sizeof(c), hipMemcpyDeviceToHost));
+    cls[0] = (uint64_t) st->matches - c[0] - c[1];
+    cls[1] = c[1];
+    cls[2] = c[0];
+    return 0;
+}
+
+// mat / semi / outer: the payload-carrying pipeline (pl below). mat carries both relations' payloads,
+// and so does outer (from the join on it has kernels of its own); semi only S's: its R side runs the
+// counting join's scatter and build (32-bit codes, no payloads).
 int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                    const MatReq* mat, const SemiReq* semi) {
+                    const MatReq* mat, const SemiReq* semi, const OuterReq* outer) {
+    const MatReq omat{outer ? outer->out : nullptr, outer ? outer->cap : 0};
+    if (outer) mat = &omat;  // (the materializing pipeline up to the join)
     if (jkind < 0 || jkind > 2) {
         set_last_error("unknown per-partition join algorithm");
         return 2;
@@ -453,7 +470,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     // of several R pieces
     const bool semi_bm   = g.sub_shift > 0 && 32 - g.hash_shift <= 17;  // (k_join_mat's bitmap condition)
     const bool semi_mark = semi && (semi->anti || !semi_bm);
-    if (semi_mark) ok &= smark.ensure(LS * 4);
+    if (semi_mark || (outer && outer->keep_s)) ok &= smark.ensure(LS * 4);
     if (!ok) {
         set_last_error("hipMalloc failed (device memory)");
         return pre(4);
@@ -663,6 +680,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     if (mat) {
         // (k_join_split, which leaves job_surv zero for the next join, does not run here)
         HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));
+        if (outer && outer->keep_s) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
         MatJoinParams mp{};
         mp.r_codes         = jp.r_codes;
         mp.r_pay           = rpay.as<uint32_t>();
@@ -686,7 +704,36 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         mp.out             = mat->out;
         mp.cap             = mat->cap;
         mp.count           = (unsigned long long*) d_result;
-        launch_join_mat(mp, NJ, stream);
+        if (outer) {
+            // the class counters: u64 words 6 (R-only) and 7 (S-only) of the slot, zeroed with the
+            // counts by the R scatter and not read by ring_collect; inner = rows - both
+            unsigned long long* cls = (unsigned long long*) sm + 6;
+            outer_cls_ = (const uint64_t*) cls;
+            OuterJoinParams op{};
+            op.m        = mp;
+            op.keep_s   = outer->keep_s ? 1u : 0u;
+            op.keep_r   = outer->keep_r ? 1u : 0u;
+            op.null_pay = outer->null_pay;
+            op.mark     = outer->keep_s ? smark.as<uint32_t>() : nullptr;
+            op.n_r_only = cls;
+            launch_join_outer(op, NJ, stream);
+            if (outer->keep_s) {  // every unmarked S tuple: the filter's rejects and the unmatched survivors
+                OuterEmitParams oe{};
+                oe.ppool      = ppoolS.as<uint32_t>();
+                oe.list       = S_.list.as<uint32_t>();
+                oe.list_start = S_.lstart.as<uint32_t>();
+                oe.mark       = smark.as<uint32_t>();
+                oe.log2F      = g.log2F;
+                oe.null_pay   = outer->null_pay;
+                oe.out        = outer->out;
+                oe.cap        = outer->cap;
+                oe.count      = (unsigned long long*) d_result;
+                oe.n_s_only   = cls + 1;
+                launch_outer_emit(oe, (uint32_t) cus_ * 2, stream);
+            }
+        } else {
+            launch_join_mat(mp, NJ, stream);
+        }
     } else if (semi) {
         HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));  // (as above)
         if (semi_mark) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
@@ -748,7 +795,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     have_filter_  = args != nullptr;
     last_g_       = g;
     {  // the shape of this join's tables (tables_info / tables_read)
-        tab_.state = semi ? kTabOther : kTabJoin;  // (the existence join's tables: not read back)
+        tab_.state = semi || outer ? kTabOther : kTabJoin;  // (the existence / outer join's tables: not read back)
         tab_.sync  = phase_ev_;
         tab_.mat   = mat != nullptr;
         tab_.g     = g;
@@ -1372,6 +1419,51 @@ int Engine::materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t 
     HWBRJ_CHECK(hipGetLastError());
     HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
     HWBRJ_CHECK(hipMemcpy(n, mcount.p, 8, hipMemcpyDeviceToHost));
+    if (ms) {
+        float f = 0;
+        HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
+        *ms = f;
+    }
+    return 0;
+}
+
+int Engine::outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const OuterReq& outer,
+                       uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    uint64_t T = 2;
+    while (T < 2 * nR) T <<= 1;
+    tab_.state = kTabOther;  // (an outer join's tables are not read back, in this mode either)
+    const size_t fbytes = (size_t) std::max<uint64_t>(T / 8, 4);  // one bit per table slot
+    if (!mtab.ensure(T * 8) || !mcount.ensure(24) || (outer.keep_r && !smark.ensure(fbytes))) {
+        set_last_error("hipMalloc failed (outer join table)");
+        return 4;
+    }
+    HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
+    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 24, stream));
+    if (outer.keep_r) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, fbytes, stream));
+    HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
+    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    uint32_t* rflag = outer.keep_r ? smark.as<uint32_t>() : nullptr;
+    if (nS) {
+        Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
+        if (!have_filter_) g.mode = MODE_NOBLOOM;
+        launch_outer_probe(dS, nS, dR, mtab.as<unsigned long long>(), T - 1, outer.keep_s ? 1u : 0u,
+                           outer.null_pay, rflag, outer.out, outer.cap, mcount.as<unsigned long long>(), g,
+                           slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_, stream);
+    }
+    if (outer.keep_r && nR)
+        launch_outer_rtab(dR, mtab.as<unsigned long long>(), T, rflag, outer.null_pay, outer.out, outer.cap,
+                          mcount.as<unsigned long long>(), stream);
+    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
+    HWBRJ_CHECK(hipGetLastError());
+    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
+    uint64_t c[3];
+    HWBRJ_CHECK(hipMemcpy(c, mcount.p, sizeof(c), hipMemcpyDeviceToHost));
+    *n     = c[0];
+    cls[0] = c[0] - c[1] - c[2];
+    cls[1] = c[1];
+    cls[2] = c[2];
     if (ms) {
         float f = 0;
         HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));

@@ -35,6 +35,14 @@ struct SemiReq {
     uint64_t cap;
     bool     anti;
 };
+// An outer join's output: rows {R.payload | null, S.payload | null} into out[0, cap). keep_s: the S
+// rows without a partner in R are rows too; keep_r: the R rows without a partner in S.
+struct OuterReq {
+    uint2*   out;
+    uint64_t cap;
+    bool     keep_s, keep_r;
+    uint32_t null_pay;
+};
 
 struct DevBuf {
     void*  p     = nullptr;
@@ -118,6 +126,15 @@ class Engine {
     int  run_semi(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                   const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
                   hwbrj_stats_t* st);
+    // The outer join on the materializing pipeline (both payloads; k_join_outer, and k_outer_emit
+    // when S is preserved). st->matches = rows (all of them, also beyond cap); cls = {inner, S-only,
+    // R-only} rows. kRcMatGlobal: not for the global-bitmap mode.
+    int  run_outer(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+                   const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
+                   hwbrj_stats_t* st, uint64_t cls[3]);
+    // Its side pass after a counting join (global-bitmap mode): *n = rows, cls as above.
+    int  outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const OuterReq& outer,
+                    uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms);
     // Its side pass after a counting join (global-bitmap mode): *n = number of rows.
     int  semi_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const SemiReq& semi,
                    uint64_t* n, hipStream_t stream, double* ms);
@@ -284,7 +301,8 @@ class Engine {
     bool         alloc_only_   = false;  // reserve(): enqueue returns after its allocations
     int          enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                          const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                         const MatReq* mat = nullptr, const SemiReq* semi = nullptr);
+                         const MatReq* mat = nullptr, const SemiReq* semi = nullptr,
+                         const OuterReq* outer = nullptr);
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                                   const Geometry& g, hipStream_t stream, int jkind);
@@ -310,7 +328,9 @@ class Engine {
     // materializing pipeline: payload pools (chunk layout of R_.pool / S_.pool), R payloads of the
     // build sweeps, survivors' chunk positions
     DevBuf ppoolR, ppoolS, rpay, survpos;
-    DevBuf smark;  // existence join: one bit per S chunk position (matched survivors)
+    DevBuf smark;  // existence / outer join: one bit per S chunk position (matched survivors); the
+                   // outer side pass: one bit per slot of its table of R (outer_side)
+    const uint64_t* outer_cls_ = nullptr;  // the last outer join's {R-only, S-only} counters (its ring slot)
     DevBuf dense2, kkcnt;  // basic k >= 2: the second dense candidate buffer, per-pass counts
     DevBuf jtask, jparts;  // join task table; parts per job (+ the task count)
     // partitioned join: owned partitions' lists, tables and received survivor descriptors

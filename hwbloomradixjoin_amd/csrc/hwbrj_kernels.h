@@ -219,6 +219,47 @@ void   launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* t
                          const Geometry& g, const uint32_t* slices, const uint32_t* bm,
                          const CrcTables* tabs, hipStream_t st);
 
+// The outer join (k_join_outer): the materializing join's inputs and pairs (m), and
+//  - keep_s: every survivor with a partner marks its chunk position in `mark` (one bit per S chunk
+//    position, zero on entry); k_outer_emit then writes {null_pay, S.payload} of every unmarked one;
+//  - keep_r: {R.payload, null_pay} of every R tuple of the job that no survivor matched, appended to
+//    m.out through m.count like the pairs; *n_r_only += those rows.
+struct OuterJoinParams {
+    MatJoinParams       m;
+    uint32_t            keep_s, keep_r;
+    uint32_t            null_pay;
+    uint32_t*           mark;      // [S chunks], or nullptr (!keep_s)
+    unsigned long long* n_r_only;  // zero on entry
+};
+void   launch_join_outer(const OuterJoinParams& p, uint32_t jobs, hipStream_t st);
+// The outer join's S-only rows (k_outer_emit): {null_pay, payload} of every S tuple of the chunk
+// lists whose position is not marked, appended to out (up to cap; *count and *n_s_only += rows).
+// Reads the lists (for the chunks' counts), the payloads and the marks: not the words.
+struct OuterEmitParams {
+    const uint32_t*     ppool;       // S payloads
+    const uint32_t*     list;        // S chunk lists
+    const uint32_t*     list_start;  // [F + 1]
+    const uint32_t*     mark;
+    uint32_t            log2F;
+    uint32_t            null_pay;
+    uint2*              out;
+    uint64_t            cap;
+    unsigned long long* count;
+    unsigned long long* n_s_only;
+};
+void   launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st);
+// The outer join's side pass (global-bitmap mode) over launch_mat_build's table of R: the pairs of
+// every S tuple (k_mat_probe's walk, the filter as a pre-test), {null_pay, S.payload} for an S tuple
+// without a partner (keep_s), and a bit per table slot that was hit (rflag, or nullptr);
+// cnt[0] += rows, cnt[1] += S-only rows. launch_outer_rtab then writes {R.payload, null_pay} of the
+// table's unflagged entries; cnt[0] and cnt[2] += those rows.
+void   launch_outer_probe(const uint2* S, uint64_t n, const uint2* R, const unsigned long long* tab,
+                          uint64_t mask, uint32_t keep_s, uint32_t null_pay, uint32_t* rflag, uint2* out,
+                          uint64_t cap, unsigned long long* cnt, const Geometry& g, const uint32_t* slices,
+                          const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
+void   launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
+                         uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st);
+
 void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                   hipStream_t st);
 void   launch_zipf(const int32_t* rnd, uint64_t cnt, uint64_t row0, const double* lut,

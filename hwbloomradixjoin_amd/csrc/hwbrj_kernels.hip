@@ -4196,6 +4196,558 @@ void launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* tab
     k_semi_probe<<<2048, 256, 0, st>>>(S, n, tab, mask, anti, out, cap, count, g, slices, bm, tabs);
 }
 
+// ================================================================= K10o: the outer join
+// k_join_mat's job layout, XCD-aware order and three forms (single-shot bitmap + rank, single-shot
+// hash table, descriptor batches x R pieces x survivor batches), writing the same pairs, and:
+//  - keep_s: a survivor with at least one partner sets its chunk position's bit in `mark` (on every
+//    path; a survivor that matches in several pieces sets it again, which changes nothing). No
+//    survivor is judged unmatched here, since that needs all of the job's R: k_outer_emit writes the
+//    unmarked S tuples, so a job without R has nothing to do;
+//  - keep_r: one matched bit per R tuple in LDS (rflag), by rank on the bitmap path, by table slot
+//    on the hash forms (mat_insert1 gives every R tuple a slot of its own, and the walk that writes
+//    a survivor's pairs visits every copy of its key). A piece sees all of the job's survivors
+//    before the next piece is loaded, so its flags are final at its end: the unflagged tuples are
+//    then written as {R.payload, null} rows, a workgroup scan and one output atomic per piece. A job
+//    without probe items, or without survivors, therefore still loads its R and writes all of it.
+// KR = keep_r at compile time. Without it the kernel is k_join_mat plus the marks and keeps its
+// register budget (64 VGPRs: 8 waves per SIMD, the four workgroups per CU the LDS admits). With it
+// that budget spills 27 VGPRs; 80 VGPRs at 6 waves per SIMD spill 2, outside the survivor loops
+// ("Outer joins").
+constexpr uint32_t kOutFlagWords = kMatT / 32;
+static_assert(kMatRCap <= kMatT && kMatT == kMatThreads * kMatUB, "one flag per rank / slot, kMatUB per thread");
+
+template <bool KR>
+__global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(KR ? 6 : 8))) void k_join_outer(OuterJoinParams O) {
+    const MatJoinParams& P = O.m;
+    // LDS union as in k_join_mat
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kMatBmWords + kMatBmWords / 4 + kMatRCap];
+    uint32_t* tk = smem;
+    uint32_t* tp = smem + kMatT;
+    __shared__ uint32_t rflag[kOutFlagWords];
+    __shared__ uint32_t dupf;
+    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
+    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
+    __shared__ uint32_t wsum[kMatThreads / 64];
+    __shared__ unsigned long long obase;
+    const int      tid  = threadIdx.x;
+    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
+    uint32_t job = blockIdx.x;
+    if (P.xcd8) {  // (k_join_mat's XCD-aware job order)
+        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
+        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
+    }
+    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
+    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
+    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
+    // (uniform) no R in q: no pair, no R-only row, and q's survivors stay unmarked. No probe items
+    // in q: nothing unless R is preserved (then every R tuple of the job is an R-only row)
+    if (r0 == r1 || (qi0 == qi1 && !KR)) return;
+    const uint32_t lq0 = P.list_start[q];
+    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment (0: s_desc is not called)
+    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
+        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
+        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
+        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
+               P.surv_off[(uint64_t) it * NSUB + s];
+    };
+    auto set_mark = [&](uint32_t pos) { atomicOr(&O.mark[pos >> 5], 1u << (pos & 31u)); };
+    auto set_flag = [&](uint32_t i) { atomicOr(&rflag[i >> 5], 1u << (i & 31u)); };
+    // {R.payload, null} of the unflagged R tuples among entries [0, n) (n <= kMatT): entry i holds a
+    // tuple when keys is nullptr (ranks) or keys[i] != kEmpty (slots), pay[i] is its payload.
+    // Contains barriers; the first one completes the flags.
+    auto r_only = [&](uint32_t n, const uint32_t* keys, const uint32_t* pay) {
+        __syncthreads();
+        uint32_t sel = 0;
+#pragma unroll
+        for (int k = 0; k < kMatUB; k++) {
+            const uint32_t i = tid + k * kMatThreads;
+            if (i < n && (!keys || keys[i] != kEmpty) && !((rflag[i >> 5] >> (i & 31u)) & 1u)) sel |= 1u << k;
+        }
+        uint32_t       tot;
+        const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), wsum, tot);
+        if (tot == 0) return;  // (uniform)
+        if (tid == 0) {
+            obase = atomicAdd(P.count, (unsigned long long) tot);
+            atomicAdd(O.n_r_only, (unsigned long long) tot);
+        }
+        __syncthreads();
+        uint64_t o = obase + off;
+#pragma unroll
+        for (int k = 0; k < kMatUB; k++) {
+            if (!((sel >> k) & 1u)) continue;
+            if (o < P.cap) P.out[o] = make_uint2(pay[tid + k * kMatThreads], O.null_pay);
+            o++;
+        }
+    };
+    // ---- single-shot form
+    if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
+        const uint32_t nrd = r1 - r0, nsd = qi1 - qi0;
+        uint32_t       rcn = 0, scn = 0;
+        if ((uint32_t) tid < nrd) {
+            const uint64_t r = (uint64_t) (r0 + tid) * NSUB + s;
+            rcn        = P.r_cnt[r];
+            rbase[tid] = (uint64_t) (r0 + tid) * P.slot + P.r_off[r];
+        }
+        if ((uint32_t) tid < nsd) s_desc(qi0 + tid, scn, sbase[tid]);
+        uint32_t       rtot, stot;
+        const uint32_t rx = mat_block_scan(rcn, wsum, rtot);
+        const uint32_t sx = mat_block_scan(scn, wsum, stot);
+        if (rtot == 0 || (stot == 0 && !KR)) return;  // (uniform) as above, for this sub
+        if ((uint32_t) tid < nrd) rpre[tid] = rx;
+        if ((uint32_t) tid < nsd) spre[tid] = sx;
+        if (tid == 0) {
+            rpre[nrd] = rtot;
+            spre[nsd] = stot;
+            dupf      = 0;
+        }
+        if ((uint32_t) tid < kOutFlagWords) rflag[tid] = 0;
+        if (P.bm && rtot <= kMatRCap) {  // (uniform) ---- bitmap path
+            uint32_t*       bmw = smem;
+            uint16_t*       pfx = (uint16_t*) (smem + kMatBmWords);
+            uint32_t*       rpy = smem + kMatBmWords + kMatBmWords / 4;
+            const uint64_t* bm64 = (const uint64_t*) smem;
+            for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) bmw[i] = 0;
+            __syncthreads();  // descriptors visible, bitmap and flags cleared
+            uint32_t rv[kMatUB], rp[kMatUB];
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++) {
+                const uint32_t e = tid + k * kMatThreads;
+                rv[k] = kEmpty;
+                if (e < rtot) {
+                    const uint32_t d  = mat_find(rpre, nrd, e);
+                    const uint64_t ra = rbase[d] + (e - rpre[d]);
+                    rv[k] = P.r_codes[ra] >> hs;
+                    rp[k] = P.r_pay[ra];
+                }
+            }
+            uint32_t dup = 0;
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++)
+                if (rv[k] != kEmpty) dup |= (atomicOr(&bmw[rv[k] >> 5], 1u << (rv[k] & 31u)) >> (rv[k] & 31u)) & 1u;
+            if (dup) dupf = 1;
+            __syncthreads();
+            if (!dupf) {  // (uniform)
+                uint32_t c4[4], c = 0;  // rank prefix: thread t owns 64-bit words 4t .. 4t + 3
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    c4[j] = (uint32_t) __builtin_popcountll(bm64[tid * 4 + j]);
+                    c += c4[j];
+                }
+                uint32_t       ntot;
+                uint32_t       run = mat_block_scan(c, wsum, ntot);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    pfx[tid * 4 + j] = (uint16_t) run;
+                    run += c4[j];
+                }
+                __syncthreads();
+                auto rank = [&](uint32_t v) {
+                    const uint64_t w = bm64[v >> 6];
+                    return (uint32_t) pfx[v >> 6] + (uint32_t) __builtin_popcountll(w & ((1ull << (v & 63u)) - 1ull));
+                };
+#pragma unroll
+                for (int k = 0; k < kMatUB; k++)
+                    if (rv[k] != kEmpty) rpy[rank(rv[k])] = rp[k];
+                __syncthreads();  // payloads by rank complete
+                for (uint32_t e0 = 0; e0 < stot; e0 += kMatRCap) {  // survivors, batch by batch
+                    uint64_t a[kMatUB];
+                    uint32_t v[kMatUB], hit = 0;
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) {
+                        const uint32_t e = e0 + tid + k * kMatThreads;
+                        v[k] = kEmpty;
+                        a[k] = 0;
+                        if (e < stot) {
+                            const uint32_t d = mat_find(spre, nsd, e);
+                            a[k] = sbase[d] + (e - spre[d]);
+                            v[k] = P.surv[a[k]] >> hs;
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++)
+                        if (v[k] != kEmpty) hit |= ((bmw[v[k] >> 5] >> (v[k] & 31u)) & 1u) << k;
+                    uint32_t pos[kMatUB], sp[kMatUB];
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) pos[k] = (hit >> k) & 1u ? P.surv_pos[a[k]] : 0u;
+                    uint32_t       tot;
+                    const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(hit), wsum, tot);
+                    if (tot == 0) continue;  // (uniform)
+                    if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) sp[k] = (hit >> k) & 1u ? P.s_pay[pos[k]] : 0u;
+                    if (O.keep_s) {
+#pragma unroll
+                        for (int k = 0; k < kMatUB; k++)
+                            if ((hit >> k) & 1u) set_mark(pos[k]);
+                    }
+                    __syncthreads();
+                    uint64_t o = obase + off;
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) {
+                        if (!((hit >> k) & 1u)) continue;
+                        const uint32_t rk = rank(v[k]);
+                        if (KR) set_flag(rk);
+                        if (o < P.cap) P.out[o] = make_uint2(rpy[rk], sp[k]);
+                        o++;
+                    }
+                }
+                if (KR) r_only(rtot, nullptr, rpy);  // (unique keys: ranks [0, rtot))
+                return;
+            }
+            // duplicate R keys: the hash table (over the same LDS)
+        }
+        if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform)
+            __syncthreads();  // descriptors visible; the bitmap path is done with the LDS
+            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+            __syncthreads();
+            uint32_t rc[kMatU], rp[kMatU], v[kMatU], m[kMatU];
+            uint64_t a[kMatU];
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                const uint32_t e = tid + k * kMatThreads;
+                if (e < rtot) {
+                    const uint32_t d  = mat_find(rpre, nrd, e);
+                    const uint64_t ra = rbase[d] + (e - rpre[d]);
+                    rc[k] = P.r_codes[ra];
+                    rp[k] = P.r_pay[ra];
+                }
+                v[k] = kEmpty;
+                a[k] = 0;
+                if (e < stot) {
+                    const uint32_t d = mat_find(spre, nsd, e);
+                    a[k] = sbase[d] + (e - spre[d]);
+                    v[k] = P.surv[a[k]] >> hs;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kMatU; k++)
+                if (tid + k * kMatThreads < rtot) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
+            __syncthreads();  // table complete
+            mat_count(tk, v, m);
+            uint32_t cnt = 0;
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) cnt += m[k];
+            uint32_t pos[kMatU], sp[kMatU];
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;  // (in flight over the scan)
+            uint32_t       tot;
+            const uint32_t off = mat_block_scan(cnt, wsum, tot);
+            if (tot) {  // (uniform)
+                if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
+#pragma unroll
+                for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
+                if (O.keep_s) {
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++)
+                        if (m[k]) set_mark(pos[k]);
+                }
+                __syncthreads();
+                uint64_t o = obase + off;
+#pragma unroll
+                for (int k = 0; k < kMatU; k++) {
+                    if (!m[k]) continue;
+                    for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
+                        const uint32_t x = tk[h];
+                        if (x == kEmpty) break;
+                        if (x == v[k]) {
+                            if (KR) set_flag(h);
+                            if (o < P.cap) P.out[o] = make_uint2(tp[h], sp[k]);
+                            o++;
+                        }
+                    }
+                }
+            }
+            if (KR) r_only(kMatT, tk, tp);
+            return;
+        }
+    }
+    // ---- general form: R descriptor batches x R pieces x survivor batches
+    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {  // R run descriptors, batch by batch
+        const uint32_t nrd = min(kMatDesc, r1 - rd0);
+        __syncthreads();  // previous descriptors consumed
+        uint32_t c = 0;
+        if ((uint32_t) tid < nrd) {
+            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
+            c          = P.r_cnt[r];
+            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
+        }
+        uint32_t       rtot;
+        const uint32_t rx = mat_block_scan(c, wsum, rtot);
+        if ((uint32_t) tid < nrd) rpre[tid] = rx;
+        if (tid == 0) rpre[nrd] = rtot;
+        __syncthreads();
+        for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
+            const uint32_t pe = min(rtot, pb + kMatPiece);
+            __syncthreads();  // the previous piece's survivors and R-only rows are done with the table
+            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+            if ((uint32_t) tid < kOutFlagWords) rflag[tid] = 0;
+            uint32_t rc[kMatU], rp[kMatU];  // this thread's R tuples of the piece (loads in flight)
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                const uint32_t e = pb + tid + k * kMatThreads;
+                rc[k] = kEmpty;
+                if (e < pe) {
+                    const uint32_t d = mat_find(rpre, nrd, e);
+                    const uint64_t a = rbase[d] + (e - rpre[d]);
+                    rc[k] = P.r_codes[a];
+                    rp[k] = P.r_pay[a];
+                }
+            }
+            __syncthreads();  // table and flags cleared
+#pragma unroll
+            for (int k = 0; k < kMatU; k++)
+                if (pb + tid + k * kMatThreads < pe) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
+            for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {  // survivor runs of the job
+                const uint32_t nsd = min(kMatDesc, qi1 - sd0);
+                __syncthreads();  // table complete; previous descriptors consumed
+                uint32_t sc = 0;
+                if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
+                uint32_t       stot;
+                const uint32_t sx = mat_block_scan(sc, wsum, stot);
+                if ((uint32_t) tid < nsd) spre[tid] = sx;
+                if (tid == 0) spre[nsd] = stot;
+                __syncthreads();
+                for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {
+                    uint64_t a[kMatU];
+                    uint32_t v[kMatU], m[kMatU];
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) {
+                        const uint32_t e = e0 + tid + k * kMatThreads;
+                        a[k] = ~0ull;
+                        v[k] = kEmpty;
+                        if (e < stot) {
+                            const uint32_t d = mat_find(spre, nsd, e);
+                            a[k] = sbase[d] + (e - spre[d]);
+                            v[k] = P.surv[a[k]] >> hs;
+                        }
+                    }
+                    mat_count(tk, v, m);
+                    uint32_t cnt = 0;
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) cnt += m[k];
+                    uint32_t       tot;
+                    const uint32_t off = mat_block_scan(cnt, wsum, tot);
+                    if (tot == 0) continue;  // (uniform)
+                    if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
+                    __syncthreads();
+                    uint64_t o = obase + off;
+                    uint32_t pos[kMatU], sp[kMatU];
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) {
+                        if (!m[k]) continue;
+                        if (O.keep_s) set_mark(pos[k]);
+                        for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
+                            const uint32_t x = tk[h];
+                            if (x == kEmpty) break;
+                            if (x == v[k]) {
+                                if (KR) set_flag(h);
+                                if (o < P.cap) P.out[o] = make_uint2(tp[h], sp[k]);
+                                o++;
+                            }
+                        }
+                    }
+                }
+            }
+            if (KR) r_only(kMatT, tk, tp);  // (its first barrier: the table complete, the flags final)
+        }
+    }
+}
+
+void launch_join_outer(const OuterJoinParams& p0, uint32_t jobs, hipStream_t st) {
+    OuterJoinParams p = p0;
+    p.m.xcd8          = ((jobs >> p.m.log2NSUB) % 8 == 0) ? 1u : 0u;
+    if (p.keep_r) k_join_outer<true><<<jobs, kMatThreads, 0, st>>>(p);
+    else k_join_outer<false><<<jobs, kMatThreads, 0, st>>>(p);
+}
+
+// The outer join's S-only rows: k_semi_emit's batch shape (256 chunks a batch, 8 threads per chunk
+// and two chunks per thread, the rows compacted in the LDS stage and copied out in order, one output
+// atomic per batch) over the lists, the payloads and the marks only. The words are not read: a row
+// is {null, payload}, and a chunk's tuple count is in its list entry.
+__global__ __launch_bounds__(1024) void k_outer_emit(OuterEmitParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint2* stage = (uint2*) lds;  // [kSeBatch * 32] rows of a batch
+    __shared__ uint32_t wsum[16];
+    __shared__ unsigned long long obase;
+    const uint32_t tid = threadIdx.x, l8 = tid & 7u, cslot = tid >> 3;
+    const uint32_t L   = P.list_start[1u << P.log2F];
+    const uint32_t nb  = (L + kSeBatch - 1) / kSeBatch;
+    const uint32_t b0  = (uint32_t) ((uint64_t) blockIdx.x * nb / gridDim.x);
+    const uint32_t b1  = (uint32_t) ((uint64_t) (blockIdx.x + 1) * nb / gridDim.x);
+    for (uint32_t b = b0; b < b1; b++) {
+        uint32_t ent[kSeU], sel[kSeU];
+        uint4    py[kSeU];
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) {
+            const uint32_t lpos = b * kSeBatch + cslot + (uint32_t) j * 128u;
+            ent[j] = lpos < L ? P.list[lpos] : kNoEntry;
+        }
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) {
+            sel[j] = 0;
+            py[j]  = make_uint4(0, 0, 0, 0);
+            if (ent[j] != kNoEntry) {
+                const uint32_t id = ent[j] & kListIdMask, cnt = list_count(ent[j]), first = l8 * 4u;
+                const uint32_t n  = cnt > first ? min(cnt - first, 4u) : 0u;
+                if (n) {
+                    py[j]  = *(const uint4*) &P.ppool[(uint64_t) id * 32 + first];
+                    sel[j] = ((1u << n) - 1u) & ~(P.mark[id] >> first);
+                }
+            }
+        }
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) cnt += (uint32_t) __builtin_popcount(sel[j]);
+        uint32_t       tot;
+        const uint32_t off = block_excl_scan(cnt, wsum, tot);
+        if (tot == 0) continue;  // (uniform)
+        if (tid == 0) {
+            obase = atomicAdd(P.count, (unsigned long long) tot);
+            atomicAdd(P.n_s_only, (unsigned long long) tot);
+        }
+        uint32_t o = off;
+#pragma unroll
+        for (int j = 0; j < kSeU; j++) {
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                if (!((sel[j] >> t) & 1u)) continue;
+                const uint32_t pay = t == 0 ? py[j].x : t == 1 ? py[j].y : t == 2 ? py[j].z : py[j].w;
+                stage[o++] = make_uint2(P.null_pay, pay);
+            }
+        }
+        __syncthreads();  // the batch's rows staged, obase set
+        const uint64_t ob = obase;
+        for (uint32_t i = tid; i < tot; i += 1024)
+            if (ob + i < P.cap) P.out[ob + i] = stage[i];
+        __syncthreads();  // stage and obase reusable
+    }
+}
+
+void launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st) {
+    const size_t lds = (size_t) kSeBatch * 32 * sizeof(uint2);
+    (void) hipFuncSetAttribute((const void*) &k_outer_emit, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    k_outer_emit<<<grid, 1024, lds, st>>>(p);
+}
+
+// The outer join's side pass (global-bitmap mode), k_mat_probe's outer form: the rows of an S tuple
+// are its pairs, or {null, S.payload} when it has none (a tuple the filter rejects has none); a hit
+// table slot gets its bit in rflag. Rows are staged in LDS as in k_mat_probe.
+__global__ __launch_bounds__(256) void k_outer_probe(const uint2* __restrict__ S, uint64_t n,
+                                                      const uint2* __restrict__ R,
+                                                      const unsigned long long* __restrict__ tab,
+                                                      uint64_t mask, uint32_t keep_s, uint32_t null_pay,
+                                                      uint32_t* __restrict__ rflag, uint2* __restrict__ out,
+                                                      uint64_t cap, unsigned long long* __restrict__ cnt,
+                                                      Geometry g, const uint32_t* __restrict__ slices,
+                                                      const uint32_t* __restrict__ bm,
+                                                      const CrcTables* __restrict__ tabs) {
+    __shared__ uint2              buf[kMatBuf];
+    __shared__ uint32_t           nbuf, nso;
+    __shared__ unsigned long long obase;
+    const uint64_t e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
+    if (threadIdx.x == 0) nbuf = nso = 0;
+    __syncthreads();
+    auto flush = [&]() {
+        const uint32_t c = min(nbuf, kMatBuf);
+        if (threadIdx.x == 0) obase = c ? atomicAdd(&cnt[0], (unsigned long long) c) : 0ull;
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
+            if (obase + i < cap) out[obase + i] = buf[i];
+        __syncthreads();
+        if (threadIdx.x == 0) nbuf = 0;
+        __syncthreads();
+    };
+    auto push = [&](uint2 row) {
+        const uint32_t slot = atomicAdd(&nbuf, 1u);
+        if (slot < kMatBuf) {
+            buf[slot] = row;
+        } else {  // burst beyond the stage
+            const unsigned long long o = atomicAdd(&cnt[0], 1ull);
+            if (o < cap) out[o] = row;
+        }
+    };
+    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
+        const uint64_t i = t0 + threadIdx.x;
+        if (i < e1) {
+            const uint2 st  = S[i];
+            bool        any = false;
+            if (mat_filter(st.x, g, slices, bm, tabs)) {
+                for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
+                    const unsigned long long e = tab[h];
+                    if (e == 0ull) break;
+                    if ((uint32_t) e != st.x) continue;
+                    any = true;
+                    if (rflag) atomicOr(&rflag[h >> 5], 1u << (h & 31u));
+                    push(make_uint2(R[(e >> 32) - 1].y, st.y));
+                }
+            }
+            if (!any && keep_s) {
+                atomicAdd(&nso, 1u);
+                push(make_uint2(null_pay, st.y));
+            }
+        }
+        __syncthreads();
+        if (nbuf >= kMatBuf / 2) flush();  // uniform (read after the barrier)
+    }
+    flush();
+    if (threadIdx.x == 0 && nso) atomicAdd(&cnt[1], (unsigned long long) nso);
+}
+
+// {R.payload, null} of the table's entries whose slot no S tuple hit, staged like k_semi_probe's rows
+__global__ __launch_bounds__(256) void k_outer_rtab(const uint2* __restrict__ R,
+                                                     const unsigned long long* __restrict__ tab, uint64_t slots,
+                                                     const uint32_t* __restrict__ rflag, uint32_t null_pay,
+                                                     uint2* __restrict__ out, uint64_t cap,
+                                                     unsigned long long* __restrict__ cnt) {
+    __shared__ uint2              buf[kMatBuf];
+    __shared__ uint32_t           nbuf;
+    __shared__ unsigned long long obase;
+    const uint64_t e0 = slots * blockIdx.x / gridDim.x, e1 = slots * (blockIdx.x + 1) / gridDim.x;
+    if (threadIdx.x == 0) nbuf = 0;
+    __syncthreads();
+    auto flush = [&]() {
+        const uint32_t c = nbuf;
+        if (threadIdx.x == 0) {
+            obase = c ? atomicAdd(&cnt[0], (unsigned long long) c) : 0ull;
+            if (c) atomicAdd(&cnt[2], (unsigned long long) c);
+        }
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
+            if (obase + i < cap) out[obase + i] = buf[i];
+        __syncthreads();
+        if (threadIdx.x == 0) nbuf = 0;
+        __syncthreads();
+    };
+    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
+        const uint64_t h = t0 + threadIdx.x;
+        if (h < e1) {
+            const unsigned long long e = tab[h];
+            if (e != 0ull && !((rflag[h >> 5] >> (h & 31u)) & 1u))
+                buf[atomicAdd(&nbuf, 1u)] = make_uint2(R[(e >> 32) - 1].y, null_pay);  // (nbuf + 256 <= kMatBuf)
+        }
+        __syncthreads();
+        if (nbuf > kMatBuf - 256) flush();  // uniform (read after the barrier)
+    }
+    flush();
+}
+
+void launch_outer_probe(const uint2* S, uint64_t n, const uint2* R, const unsigned long long* tab, uint64_t mask,
+                        uint32_t keep_s, uint32_t null_pay, uint32_t* rflag, uint2* out, uint64_t cap,
+                        unsigned long long* cnt, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
+                        const CrcTables* tabs, hipStream_t st) {
+    k_outer_probe<<<2048, 256, 0, st>>>(S, n, R, tab, mask, keep_s, null_pay, rflag, out, cap, cnt, g, slices, bm,
+                                        tabs);
+}
+
+void launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
+                       uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st) {
+    k_outer_rtab<<<2048, 256, 0, st>>>(R, tab, slots, rflag, null_pay, out, cap, cnt);
+}
+
 // ===================================================================== launch wrappers
 void launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                 hipStream_t st) {

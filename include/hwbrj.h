@@ -216,6 +216,34 @@ int hwbrj_join_semi_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_S
                            const bloom_filter_args_t * args, int kind, tuple_t * d_out,
                            uint64_t capacity, uint64_t * n_out, void * stream,
                            hwbrj_stats_t * stats, double * ms);
+/* The outer joins of R and S: d_out receives rows {R.payload, S.payload}, in no particular order.
+ * Inner rows: every matching pair, exactly the multiset hwbrj_join_materialize_device returns
+ * (duplicate R keys and duplicate S keys give the product). HWBRJ_OUTER_S: also one row
+ * {null_payload, S.payload} for every S row whose key does not occur in R (the rows the filter
+ * rejects, the survivors that are false positives and the rows of partitions without R alike), each
+ * exactly once. HWBRJ_OUTER_R: instead one row {R.payload, null_payload} for every R row whose key
+ * does not occur in S; every R tuple gets its own row, so three R rows sharing an unmatched key give
+ * three rows. HWBRJ_OUTER_FULL: both. null_payload is the caller's marker: the library does not
+ * check that it is absent from the payloads and never reads it back.
+ * n_class (optional) receives {inner rows, S-only rows (0 under OUTER_R), R-only rows (0 under
+ * OUTER_S)}. args == NULL runs without a filter; every filter configuration of
+ * hwbrj_join_materialize_device is accepted (the global-bitmap ones run the counting join and a
+ * side pass). One pass of the materializing pipeline: the join marks the S positions that have a
+ * partner and flags the R tuples that have one, writes the unflagged R tuples itself, and one pass
+ * over the partitioned S payloads writes the unmarked S rows ("Outer joins").
+ * capacity is in rows: rows beyond it are not written, *n_out always holds the full row count and
+ * 7 is returned when it exceeds capacity; capacity 0 with d_out NULL is the count-only form.
+ * stats->filtered is "S-tuples after filter" as the counting join of the same arguments reports
+ * it, stats->matches the row count. ms (optional) receives the device time. An unknown kind returns
+ * 2 before any device call and without writing *n_out. Synchronous and single-GPU; it collects
+ * pending async joins like the other synchronous entries, and hwbrj_tables_info /
+ * hwbrj_tables_read answer 13 after it. */
+enum { HWBRJ_OUTER_S = 0, HWBRJ_OUTER_R = 1, HWBRJ_OUTER_FULL = 2 };
+int hwbrj_join_outer_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_S, uint64_t nS,
+                            const bloom_filter_args_t * args, int kind, int32_t null_payload,
+                            tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
+                            uint64_t * n_class /* [3], optional */, void * stream,
+                            hwbrj_stats_t * stats, double * ms);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
