@@ -12,13 +12,13 @@ import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -130,6 +130,12 @@ def lib() -> ctypes.CDLL:
         L.hwbrj_join_outer_device.argtypes = [
             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
+        L.hwbrj_join_group_device.restype = ctypes.c_int
+        L.hwbrj_join_group_device.argtypes = [
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
             ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
         L.hwbrj_set_materialize.restype = None
@@ -605,6 +611,69 @@ def outer_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = 
     _err(rc, "hwbrj_join_outer_device")
     stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
     return stats, out[: n.value], (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
+
+
+GROUP_MATCHED, GROUP_ALL = 0, 1  # include/hwbrj.h HWBRJ_GROUP_MATCHED / _ALL
+
+
+class _GroupRow(ctypes.Structure):  # include/hwbrj.h hwbrj_group_row_t
+    _fields_ = [("r_payload", ctypes.c_int32), ("count", ctypes.c_uint32), ("sum", ctypes.c_int64)]
+
+
+class GroupRows(NamedTuple):
+    """The rows of a group join as GPU tensors of one length: r_payload (int32, a view of raw),
+    count (int64, the 32-bit count zero-extended), sum (int64, a view of raw) and raw, the (n, 2)
+    int64 buffer of hwbrj_group_row_t rows they come from."""
+    r_payload: object
+    count: object
+    sum: object
+    raw: object
+
+
+def group_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED, stream=None,
+                      capacity: Optional[int] = None):
+    """(Stats, GroupRows, n_pairs, ms): the group join of device tensors R and S
+    (hwbrj_join_group_device), one row per R row (not per key), unordered: the R row's payload, the
+    number of S rows with its key and the sum of their payloads (each sign-extended from int32, exact
+    in int64; 0 if there are none). R rows sharing a key each carry the full count and sum.
+    GROUP_ALL returns every R row (len(R) rows, count 0 and sum 0 without a partner), GROUP_MATCHED
+    only the rows with count > 0. n_pairs is the sum of the counts: join_device's `matches`.
+    Stats.filtered is the counting join's "S-tuples after filter", Stats.matches the row count; ms the
+    device time. capacity: output rows to allocate (None: one count-only call first, or len(R) rows
+    under GROUP_ALL without that call; too small: the pipeline runs again at the exact size)."""
+    import torch
+    _check_rel(R, S)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n, pairs = ctypes.c_uint64(), ctypes.c_uint64()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_group_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, int(kind), out, cap,
+                                             ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st),
+                                             ctypes.byref(ms))
+
+    if capacity is None:
+        if int(kind) == GROUP_ALL:
+            capacity = R.shape[0]
+        else:
+            rc = call(None, 0)  # count only
+            if rc not in (0, 7):
+                _err(rc, "hwbrj_join_group_device")
+            capacity = n.value
+    for _ in range(2):
+        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=R.device)
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, "hwbrj_join_group_device")
+    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    raw = out[: n.value]
+    rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
+    return stats, rows, int(pairs.value), ms.value
 
 
 def copy_bandwidth(nbytes: int = 4 << 30, reps: int = 5) -> float:

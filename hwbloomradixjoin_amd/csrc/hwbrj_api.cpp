@@ -360,6 +360,58 @@ int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
     return 0;
 }
 
+// The group join: the materializing pipeline up to the join, then per-R-tuple accumulators instead of
+// pairs (Engine::run_group); the global-bitmap mode runs the counting join (its filter and its
+// "S-tuples after filter") and the group side pass.
+int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                            const bloom_filter_args_t* args, int kind, hwbrj_group_row_t* d_out,
+                            uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
+                            hwbrj_stats_t* stats, double* ms) {
+    static_assert(sizeof(hwbrj_group_row_t) == 16, "a row is one 16-byte store");
+    if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {  // (before any device call)
+        set_last_error("unknown group join kind (HWBRJ_GROUP_MATCHED, HWBRJ_GROUP_ALL)");
+        return 2;
+    }
+    if (capacity > 0 && !d_out) {
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    if (((uintptr_t) d_out & 15u) != 0) {
+        set_last_error("d_out must be 16-byte aligned (a row is written as one 16-byte store)");
+        return 2;
+    }
+    if (nS >= (1ull << 32)) {  // a count is 32 bits wide, and 2^32 payloads keep |sum| < 2^63
+        set_last_error("group join: |S| must be below 2^32 rows (32-bit counts)");
+        return 3;
+    }
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;  // (last error set by engine_for_current_device)
+    const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL};
+    hwbrj_stats_t  st;
+    uint64_t       n = 0, pairs = 0;
+    int rc = e->run_group((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, req, &st, &pairs);
+    if (rc == 0) {
+        n = (uint64_t) st.matches;
+        if (ms) *ms = st.ms_total;
+    } else if (rc == kRcMatGlobal) {
+        rc = e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, &st);
+        if (rc) return rc;
+        rc = e->group_side((const uint2*) d_R, nR, (const uint2*) d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms);
+        if (rc) return rc;
+        st.matches = (int64_t) n;
+    } else {
+        return rc;
+    }
+    if (stats) *stats = st;
+    if (n_out) *n_out = n;
+    if (n_pairs) *n_pairs = pairs;
+    if (n > capacity) {
+        set_last_error("output capacity below the row count (*n_out holds the count)");
+        return 7;
+    }
+    return 0;
+}
+
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE
 static int g_gpus        = 0;   // shards of a host BPRO/PRO (0: from HWBRJ_GPUS, default 1)
 void hwbrj_set_materialize(int on) { g_materialize = on ? 1 : 0; }

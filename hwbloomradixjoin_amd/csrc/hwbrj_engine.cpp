@@ -301,7 +301,7 @@ void Engine::release() {
     for (DevBuf* b : {&slices, &bitmap, &rjoin, &rrun, &surv, &survcnt, &survoff,
                       &dense, &small, &bpos, &mtab, &mcount, &jtask, &jparts, &pjList,
                       &pjLstart, &pjSweep, &pjTab, &pjRegion, &pjTot, &pjSoff, &pjIbase, &pjCnt, &pjOff,
-                      &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &smark, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
+                      &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &smark, &gcnt, &gsum, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
         b->release();
     for (DevBuf& b : xslot_) b.release();
     if (pending_) (void) hipEventSynchronize(ev_[8]);  // (the ring's joins end before it is freed)
@@ -380,14 +380,25 @@ int Engine::run_outer(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS
     return 0;
 }
 
-// mat / semi / outer: the payload-carrying pipeline (pl below). mat carries both relations' payloads,
-// and so does outer (from the join on it has kernels of its own); semi only S's: its R side runs the
-// counting join's scatter and build (32-bit codes, no payloads).
+int Engine::run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+                      const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
+                      hwbrj_stats_t* st, uint64_t* pairs) {
+    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, nullptr, &group);
+    if (rc == 0) rc = wait(st);
+    if (rc) return rc;
+    // (the join has completed; its ring slot is taken again by the next enqueue only)
+    HWBRJ_CHECK(hipMemcpy(pairs, group_pairs_, sizeof(*pairs), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// mat / semi / outer / group: the payload-carrying pipeline (pl below). mat carries both relations'
+// payloads, and so do outer and group (from the join on they have kernels of their own); semi only
+// S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
 int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                    const MatReq* mat, const SemiReq* semi, const OuterReq* outer) {
-    const MatReq omat{outer ? outer->out : nullptr, outer ? outer->cap : 0};
-    if (outer) mat = &omat;  // (the materializing pipeline up to the join)
+                    const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group) {
+    const MatReq omat{outer ? outer->out : nullptr, outer ? outer->cap : group ? group->cap : 0};
+    if (outer || group) mat = &omat;  // (the materializing pipeline up to the join)
     if (jkind < 0 || jkind > 2) {
         set_last_error("unknown per-partition join algorithm");
         return 2;
@@ -731,6 +742,16 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                 oe.n_s_only   = cls + 1;
                 launch_outer_emit(oe, (uint32_t) cus_ * 2, stream);
             }
+        } else if (group) {
+            // the pair counter: u64 word 6 of the slot (as the outer join's class counters)
+            unsigned long long* pairs = (unsigned long long*) sm + 6;
+            group_pairs_ = (const uint64_t*) pairs;
+            GroupJoinParams gp{};
+            gp.m       = mp;
+            gp.all     = group->all ? 1u : 0u;
+            gp.out     = group->out;
+            gp.n_pairs = pairs;
+            launch_join_group(gp, NJ, stream);
         } else {
             launch_join_mat(mp, NJ, stream);
         }
@@ -795,7 +816,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     have_filter_  = args != nullptr;
     last_g_       = g;
     {  // the shape of this join's tables (tables_info / tables_read)
-        tab_.state = semi || outer ? kTabOther : kTabJoin;  // (the existence / outer join's tables: not read back)
+        tab_.state = semi || outer || group ? kTabOther : kTabJoin;  // (the existence / outer / group join's tables: not read back)
         tab_.sync  = phase_ev_;
         tab_.mat   = mat != nullptr;
         tab_.g     = g;
@@ -1464,6 +1485,49 @@ int Engine::outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t n
     cls[0] = c[0] - c[1] - c[2];
     cls[1] = c[1];
     cls[2] = c[2];
+    if (ms) {
+        float f = 0;
+        HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
+        *ms = f;
+    }
+    return 0;
+}
+
+int Engine::group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const GroupReq& group,
+                       uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    uint64_t T = 2;
+    while (T < 2 * nR) T <<= 1;
+    tab_.state = kTabOther;  // (a group join's tables are not read back, in this mode either)
+    const size_t rows = (size_t) std::max<uint64_t>(nR, 1);  // one count and one sum per R row
+    if (!mtab.ensure(T * 8) || !mcount.ensure(16) || !gcnt.ensure(rows * 4) || !gsum.ensure(rows * 8)) {
+        set_last_error("hipMalloc failed (group join table)");
+        return 4;
+    }
+    HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
+    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 16, stream));
+    HWBRJ_CHECK(hipMemsetAsync(gcnt.p, 0, rows * 4, stream));
+    HWBRJ_CHECK(hipMemsetAsync(gsum.p, 0, rows * 8, stream));
+    HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
+    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nR && nS) {
+        Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
+        if (!have_filter_) g.mode = MODE_NOBLOOM;
+        launch_group_probe(dS, nS, mtab.as<unsigned long long>(), T - 1, gcnt.as<uint32_t>(),
+                           gsum.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_,
+                           stream);
+    }
+    if (nR)
+        launch_group_rows(dR, nR, gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), group.all ? 1u : 0u, group.out,
+                          group.cap, mcount.as<unsigned long long>(), stream);
+    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
+    HWBRJ_CHECK(hipGetLastError());
+    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
+    uint64_t c[2];
+    HWBRJ_CHECK(hipMemcpy(c, mcount.p, sizeof(c), hipMemcpyDeviceToHost));
+    *n     = c[0];
+    *pairs = c[1];
     if (ms) {
         float f = 0;
         HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));

@@ -43,6 +43,13 @@ struct OuterReq {
     bool     keep_s, keep_r;
     uint32_t null_pay;
 };
+// A group join's output: rows {R.payload, count, sum} (hwbrj_group_row_t, 16 bytes) into
+// out[0, cap). all: every R row is a row; otherwise those with count > 0.
+struct GroupReq {
+    uint4*   out;
+    uint64_t cap;
+    bool     all;
+};
 
 struct DevBuf {
     void*  p     = nullptr;
@@ -132,6 +139,15 @@ class Engine {
     int  run_outer(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
                    hwbrj_stats_t* st, uint64_t cls[3]);
+    // The group join on the materializing pipeline up to the join, then k_join_group. st->matches =
+    // rows (all of them, also beyond cap); *pairs = the sum of their counts. kRcMatGlobal: not for the
+    // global-bitmap mode.
+    int  run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+                   const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
+                   hwbrj_stats_t* st, uint64_t* pairs);
+    // Its side pass after a counting join (global-bitmap mode): *n = rows, *pairs as above.
+    int  group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const GroupReq& group,
+                    uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms);
     // Its side pass after a counting join (global-bitmap mode): *n = rows, cls as above.
     int  outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const OuterReq& outer,
                     uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms);
@@ -302,7 +318,7 @@ class Engine {
     int          enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                          const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                          const MatReq* mat = nullptr, const SemiReq* semi = nullptr,
-                         const OuterReq* outer = nullptr);
+                         const OuterReq* outer = nullptr, const GroupReq* group = nullptr);
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                                   const Geometry& g, hipStream_t stream, int jkind);
@@ -331,6 +347,8 @@ class Engine {
     DevBuf smark;  // existence / outer join: one bit per S chunk position (matched survivors); the
                    // outer side pass: one bit per slot of its table of R (outer_side)
     const uint64_t* outer_cls_ = nullptr;  // the last outer join's {R-only, S-only} counters (its ring slot)
+    const uint64_t* group_pairs_ = nullptr;  // the last group join's pair counter (its ring slot)
+    DevBuf gcnt, gsum;  // the group join's side pass: count and sum per R row (group_side)
     DevBuf dense2, kkcnt;  // basic k >= 2: the second dense candidate buffer, per-pass counts
     DevBuf jtask, jparts;  // join task table; parts per job (+ the task count)
     // partitioned join: owned partitions' lists, tables and received survivor descriptors

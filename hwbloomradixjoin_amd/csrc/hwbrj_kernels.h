@@ -260,6 +260,29 @@ void   launch_outer_probe(const uint2* S, uint64_t n, const uint2* R, const unsi
 void   launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
                          uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st);
 
+// The group join (k_join_group): the materializing join's inputs (m; m.out is not used), no pairs.
+// Every R tuple of a job accumulates, in LDS, the number of the job's survivors with its key and the
+// sum of their payloads (each sign-extended from int32); after the survivors of a piece its row
+// {R.payload, count, sum} (hwbrj_group_row_t as one uint4) is appended to out through m.count, up to
+// m.cap rows: every R tuple (all), or those with count > 0. *n_pairs += the counts.
+struct GroupJoinParams {
+    MatJoinParams       m;
+    uint32_t            all;
+    uint4*              out;
+    unsigned long long* n_pairs;  // zero on entry
+};
+void   launch_join_group(const GroupJoinParams& p, uint32_t jobs, hipStream_t st);
+// The group join's side pass (global-bitmap mode) over launch_mat_build's table of R: every S tuple
+// (the filter as a pre-test) adds 1 to cnt[row] and its sign-extended payload to sum[row] of every
+// table entry with its key (cnt, sum: one element per R row, zero on entry). launch_group_rows then
+// writes the rows of R[0, n) (all of them, or those with cnt > 0) to out, up to cap;
+// res[0] += rows, res[1] += their counts.
+void   launch_group_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
+                          uint32_t* cnt, unsigned long long* sum, const Geometry& g, const uint32_t* slices,
+                          const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
+void   launch_group_rows(const uint2* R, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
+                         uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st);
+
 void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                   hipStream_t st);
 void   launch_zipf(const int32_t* rnd, uint64_t cnt, uint64_t row0, const double* lut,

@@ -4748,6 +4748,428 @@ void launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t s
     k_outer_rtab<<<2048, 256, 0, st>>>(R, tab, slots, rflag, null_pay, out, cap, cnt);
 }
 
+// ================================================================= K10g: the group join
+// k_join_mat's job layout, XCD-aware order and three forms (single-shot bitmap + rank, single-shot
+// hash table, descriptor batches x R pieces x survivor batches) and k_join_outer<true>'s early
+// returns, but no pairs: every R tuple of the job owns an accumulator {count (u32), sum (u64)} in
+// LDS, and a survivor adds 1 and its sign-extended payload to the accumulator of every R tuple with
+// its key (LDS atomics, ds_add_u32 and ds_add_u64). A survivor batch is the codes, the table test
+// and the surv_pos -> s_pay gather: no scan, no output atomic, no barrier. A piece sees all of the
+// job's survivors before the next piece is loaded, so its accumulators are final at its end; then
+// one workgroup scan and one output atomic place the rows {R.payload, count, sum}, 16 bytes each.
+// Accumulators are indexed by rank on the bitmap path (up to kMatRCap) and, on the hash forms, by
+// the tuple's ordinal in its piece (up to kMatPiece), which the table stores where k_join_mat's
+// stores the payload; the payloads stay in the registers of the threads that loaded them, which
+// write the rows. So the bitmap path needs no payloads-by-rank array and the table no payloads, and
+// the LDS is 20 KiB + 48 KiB (bitmap, rank prefix, 4096 accumulators) or 32 KiB + 24 KiB (table,
+// 2048 accumulators): two workgroups per CU ("Group joins").
+constexpr uint32_t kGrpWords = kMatBmWords + kMatBmWords / 4 + 3 * kMatRCap;
+static_assert(kGrpWords >= 2 * kMatT + 3 * kMatPiece, "LDS union (hash forms)");
+static_assert(kMatRCap == kMatThreads * kMatUB && kMatPiece == kMatThreads * kMatU, "one entry per (thread, k)");
+
+// The rows of this thread's NK tuples (idx[k]: the tuple's accumulator, kEmpty: none; pay[k]: its
+// payload). Contains barriers; the first one completes the accumulators. ptot is zero on entry and
+// on return.
+template <bool ALL, int NK>
+__device__ __forceinline__ void group_rows(const GroupJoinParams& G, const uint32_t (&idx)[NK],
+                                           const uint32_t (&pay)[NK], const uint32_t* gc,
+                                           const unsigned long long* gs, uint32_t* wsum,
+                                           unsigned long long* ptot, unsigned long long* obase) {
+    __syncthreads();
+    uint32_t           sel = 0, c[NK];
+    unsigned long long pairs = 0;
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        c[k] = idx[k] != kEmpty ? gc[idx[k]] : 0u;
+        if (idx[k] != kEmpty && (ALL || c[k])) sel |= 1u << k;
+        pairs += c[k];
+    }
+    if (pairs) atomicAdd(ptot, pairs);
+    uint32_t       tot;
+    const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), wsum, tot);
+    if (tot == 0) return;  // (uniform; no row, so no pair either)
+    if (threadIdx.x == 0) {
+        *obase = atomicAdd(G.m.count, (unsigned long long) tot);
+        if (*ptot) atomicAdd(G.n_pairs, *ptot);
+        *ptot = 0;
+    }
+    __syncthreads();
+    uint64_t o = *obase + off;
+#pragma unroll
+    for (int k = 0; k < NK; k++) {
+        if (!((sel >> k) & 1u)) continue;
+        if (o < G.m.cap) {
+            const unsigned long long sm = gs[idx[k]];
+            G.out[o] = make_uint4(pay[k], c[k], (uint32_t) sm, (uint32_t) (sm >> 32));
+        }
+        o++;
+    }
+}
+
+template <bool ALL>
+__global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_join_group(GroupJoinParams G) {
+    const MatJoinParams& P = G.m;
+    // LDS union: bitmap path {bitmap [kMatBmWords], rank prefix (u16) [kMatBmWords / 2], sums (u64)
+    // [kMatRCap], counts [kMatRCap]}, or hash forms {keys [kMatT], ordinals [kMatT], sums (u64)
+    // [kMatPiece], counts [kMatPiece]}
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kGrpWords];
+    uint32_t* tk = smem;
+    uint32_t* to = smem + kMatT;
+    unsigned long long* hsum = (unsigned long long*) (smem + 2 * kMatT);
+    uint32_t*           hcnt = smem + 2 * kMatT + 2 * kMatPiece;
+    __shared__ uint32_t dupf;
+    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
+    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
+    __shared__ uint32_t wsum[kMatThreads / 64];
+    __shared__ unsigned long long obase, ptot;
+    const int      tid  = threadIdx.x;
+    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
+    uint32_t job = blockIdx.x;
+    if (P.xcd8) {  // (k_join_mat's XCD-aware job order)
+        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
+        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
+    }
+    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
+    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
+    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
+    // (uniform) no R in q: no row. No probe items in q: no row with count > 0; under ALL every R
+    // tuple of the job is a row with count 0 (k_join_outer<true>'s rule)
+    if (r0 == r1 || (qi0 == qi1 && !ALL)) return;
+    const uint32_t lq0 = P.list_start[q];
+    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment (0: s_desc is not called)
+    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
+        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
+        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
+        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
+               P.surv_off[(uint64_t) it * NSUB + s];
+    };
+    auto add = [&](uint32_t* gc, unsigned long long* gs, uint32_t i, uint32_t sp) {
+        atomicAdd(&gc[i], 1u);
+        atomicAdd(&gs[i], (unsigned long long) (long long) (int32_t) sp);
+    };
+    if (tid == 0) ptot = 0;  // (first added to after a barrier)
+    // ---- single-shot form
+    if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
+        const uint32_t nrd = r1 - r0, nsd = qi1 - qi0;
+        uint32_t       rcn = 0, scn = 0;
+        if ((uint32_t) tid < nrd) {
+            const uint64_t r = (uint64_t) (r0 + tid) * NSUB + s;
+            rcn        = P.r_cnt[r];
+            rbase[tid] = (uint64_t) (r0 + tid) * P.slot + P.r_off[r];
+        }
+        if ((uint32_t) tid < nsd) s_desc(qi0 + tid, scn, sbase[tid]);
+        uint32_t       rtot, stot;
+        const uint32_t rx = mat_block_scan(rcn, wsum, rtot);
+        const uint32_t sx = mat_block_scan(scn, wsum, stot);
+        if (rtot == 0 || (stot == 0 && !ALL)) return;  // (uniform) as above, for this sub
+        if ((uint32_t) tid < nrd) rpre[tid] = rx;
+        if ((uint32_t) tid < nsd) spre[tid] = sx;
+        if (tid == 0) {
+            rpre[nrd] = rtot;
+            spre[nsd] = stot;
+            dupf      = 0;
+        }
+        if (P.bm && rtot <= kMatRCap) {  // (uniform) ---- bitmap path
+            uint32_t*           bmw  = smem;
+            uint16_t*           pfx  = (uint16_t*) (smem + kMatBmWords);
+            unsigned long long* bsum = (unsigned long long*) (smem + kMatBmWords + kMatBmWords / 4);
+            uint32_t*           bcnt = smem + kMatBmWords + kMatBmWords / 4 + 2 * kMatRCap;
+            const uint64_t*     bm64 = (const uint64_t*) smem;
+            for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) bmw[i] = 0;
+            for (uint32_t i = tid; i < rtot; i += kMatThreads) {
+                bsum[i] = 0;
+                bcnt[i] = 0;
+            }
+            __syncthreads();  // descriptors visible, bitmap and accumulators cleared
+            uint32_t rv[kMatUB], rp[kMatUB];
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++) {
+                const uint32_t e = tid + k * kMatThreads;
+                rv[k] = kEmpty;
+                rp[k] = 0;
+                if (e < rtot) {
+                    const uint32_t d  = mat_find(rpre, nrd, e);
+                    const uint64_t ra = rbase[d] + (e - rpre[d]);
+                    rv[k] = P.r_codes[ra] >> hs;
+                    rp[k] = P.r_pay[ra];
+                }
+            }
+            uint32_t dup = 0;
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++)
+                if (rv[k] != kEmpty) dup |= (atomicOr(&bmw[rv[k] >> 5], 1u << (rv[k] & 31u)) >> (rv[k] & 31u)) & 1u;
+            if (dup) dupf = 1;
+            __syncthreads();
+            if (!dupf) {  // (uniform)
+                uint32_t c4[4], c = 0;  // rank prefix: thread t owns 64-bit words 4t .. 4t + 3
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    c4[j] = (uint32_t) __builtin_popcountll(bm64[tid * 4 + j]);
+                    c += c4[j];
+                }
+                uint32_t       ntot;
+                uint32_t       run = mat_block_scan(c, wsum, ntot);
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    pfx[tid * 4 + j] = (uint16_t) run;
+                    run += c4[j];
+                }
+                __syncthreads();
+                auto rank = [&](uint32_t v) {
+                    const uint64_t w = bm64[v >> 6];
+                    return (uint32_t) pfx[v >> 6] + (uint32_t) __builtin_popcountll(w & ((1ull << (v & 63u)) - 1ull));
+                };
+                for (uint32_t e0 = 0; e0 < stot; e0 += kMatRCap) {  // survivors, batch by batch: no barrier
+                    uint64_t a[kMatUB];
+                    uint32_t v[kMatUB], hit = 0;
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) {
+                        const uint32_t e = e0 + tid + k * kMatThreads;
+                        v[k] = kEmpty;
+                        a[k] = 0;
+                        if (e < stot) {
+                            const uint32_t d = mat_find(spre, nsd, e);
+                            a[k] = sbase[d] + (e - spre[d]);
+                            v[k] = P.surv[a[k]] >> hs;
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++)
+                        if (v[k] != kEmpty) hit |= ((bmw[v[k] >> 5] >> (v[k] & 31u)) & 1u) << k;
+                    uint32_t pos[kMatUB], sp[kMatUB];
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) pos[k] = (hit >> k) & 1u ? P.surv_pos[a[k]] : 0u;
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++) sp[k] = (hit >> k) & 1u ? P.s_pay[pos[k]] : 0u;
+#pragma unroll
+                    for (int k = 0; k < kMatUB; k++)
+                        if ((hit >> k) & 1u) add(bcnt, bsum, rank(v[k]), sp[k]);
+                }
+                uint32_t idx[kMatUB];
+#pragma unroll
+                for (int k = 0; k < kMatUB; k++) idx[k] = rv[k] != kEmpty ? rank(rv[k]) : kEmpty;
+                group_rows<ALL, kMatUB>(G, idx, rp, bcnt, bsum, wsum, &ptot, &obase);
+                return;
+            }
+            // duplicate R keys: the hash table (over the same LDS)
+        }
+        if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform)
+            __syncthreads();  // descriptors visible; the bitmap path is done with the LDS
+            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+            for (uint32_t i = tid; i < rtot; i += kMatThreads) {
+                hsum[i] = 0;
+                hcnt[i] = 0;
+            }
+            __syncthreads();
+            uint32_t rc[kMatU], rp[kMatU], v[kMatU], m[kMatU], idx[kMatU];
+            uint64_t a[kMatU];
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                const uint32_t e = tid + k * kMatThreads;
+                idx[k] = kEmpty;
+                rc[k]  = 0;
+                rp[k]  = 0;
+                if (e < rtot) {
+                    const uint32_t d  = mat_find(rpre, nrd, e);
+                    const uint64_t ra = rbase[d] + (e - rpre[d]);
+                    idx[k] = e;
+                    rc[k]  = P.r_codes[ra];
+                    rp[k]  = P.r_pay[ra];
+                }
+                v[k] = kEmpty;
+                a[k] = 0;
+                if (e < stot) {
+                    const uint32_t d = mat_find(spre, nsd, e);
+                    a[k] = sbase[d] + (e - spre[d]);
+                    v[k] = P.surv[a[k]] >> hs;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kMatU; k++)
+                if (idx[k] != kEmpty) mat_insert1(tk, to, rc[k] >> hs, idx[k]);
+            __syncthreads();  // table complete
+            mat_count(tk, v, m);
+            uint32_t pos[kMatU], sp[kMatU];
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                if (!m[k]) continue;
+                for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
+                    const uint32_t x = tk[h];
+                    if (x == kEmpty) break;
+                    if (x == v[k]) add(hcnt, hsum, to[h], sp[k]);
+                }
+            }
+            group_rows<ALL, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
+            return;
+        }
+    }
+    // ---- general form: R descriptor batches x R pieces x survivor batches
+    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {  // R run descriptors, batch by batch
+        const uint32_t nrd = min(kMatDesc, r1 - rd0);
+        __syncthreads();  // previous descriptors consumed
+        uint32_t c = 0;
+        if ((uint32_t) tid < nrd) {
+            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
+            c          = P.r_cnt[r];
+            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
+        }
+        uint32_t       rtot;
+        const uint32_t rx = mat_block_scan(c, wsum, rtot);
+        if ((uint32_t) tid < nrd) rpre[tid] = rx;
+        if (tid == 0) rpre[nrd] = rtot;
+        __syncthreads();
+        for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
+            const uint32_t pe = min(rtot, pb + kMatPiece);
+            __syncthreads();  // the previous piece's survivors and rows are done with the table
+            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+            for (uint32_t i = tid; i < kMatPiece; i += kMatThreads) {
+                hsum[i] = 0;
+                hcnt[i] = 0;
+            }
+            uint32_t rc[kMatU], rp[kMatU], idx[kMatU];  // this thread's R tuples of the piece
+#pragma unroll
+            for (int k = 0; k < kMatU; k++) {
+                const uint32_t e = pb + tid + k * kMatThreads;
+                idx[k] = kEmpty;
+                rc[k]  = 0;
+                rp[k]  = 0;
+                if (e < pe) {
+                    const uint32_t d = mat_find(rpre, nrd, e);
+                    const uint64_t a = rbase[d] + (e - rpre[d]);
+                    idx[k] = e - pb;
+                    rc[k]  = P.r_codes[a];
+                    rp[k]  = P.r_pay[a];
+                }
+            }
+            __syncthreads();  // table and accumulators cleared
+#pragma unroll
+            for (int k = 0; k < kMatU; k++)
+                if (idx[k] != kEmpty) mat_insert1(tk, to, rc[k] >> hs, idx[k]);
+            for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {  // survivor runs of the job
+                const uint32_t nsd = min(kMatDesc, qi1 - sd0);
+                __syncthreads();  // table complete; previous descriptors consumed
+                uint32_t sc = 0;
+                if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
+                uint32_t       stot;
+                const uint32_t sx = mat_block_scan(sc, wsum, stot);
+                if ((uint32_t) tid < nsd) spre[tid] = sx;
+                if (tid == 0) spre[nsd] = stot;
+                __syncthreads();
+                for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {  // (no barrier in a batch)
+                    uint64_t a[kMatU];
+                    uint32_t v[kMatU], m[kMatU];
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) {
+                        const uint32_t e = e0 + tid + k * kMatThreads;
+                        a[k] = 0;
+                        v[k] = kEmpty;
+                        if (e < stot) {
+                            const uint32_t d = mat_find(spre, nsd, e);
+                            a[k] = sbase[d] + (e - spre[d]);
+                            v[k] = P.surv[a[k]] >> hs;
+                        }
+                    }
+                    mat_count(tk, v, m);
+                    uint32_t pos[kMatU], sp[kMatU];
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
+#pragma unroll
+                    for (int k = 0; k < kMatU; k++) {
+                        if (!m[k]) continue;
+                        for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
+                            const uint32_t x = tk[h];
+                            if (x == kEmpty) break;
+                            if (x == v[k]) add(hcnt, hsum, to[h], sp[k]);
+                        }
+                    }
+                }
+            }
+            // (its first barrier: the accumulators final; under ALL a job without probe items skips
+            // the survivor loop, and the barrier also completes the table it does not read)
+            group_rows<ALL, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
+        }
+    }
+}
+
+void launch_join_group(const GroupJoinParams& p0, uint32_t jobs, hipStream_t st) {
+    GroupJoinParams p = p0;
+    p.m.xcd8          = ((jobs >> p.m.log2NSUB) % 8 == 0) ? 1u : 0u;
+    if (p.all) k_join_group<true><<<jobs, kMatThreads, 0, st>>>(p);
+    else k_join_group<false><<<jobs, kMatThreads, 0, st>>>(p);
+}
+
+// The group join's side pass (global-bitmap mode): k_mat_probe's walk with the filter as a pre-test;
+// a matching entry's R row gets the S tuple in its two accumulators (device-scope atomics).
+__global__ __launch_bounds__(256) void k_group_probe(const uint2* __restrict__ S, uint64_t n,
+                                                      const unsigned long long* __restrict__ tab,
+                                                      uint64_t mask, uint32_t* __restrict__ cnt,
+                                                      unsigned long long* __restrict__ sum, Geometry g,
+                                                      const uint32_t* __restrict__ slices,
+                                                      const uint32_t* __restrict__ bm,
+                                                      const CrcTables* __restrict__ tabs) {
+    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const uint2 st = S[i];
+        if (!mat_filter(st.x, g, slices, bm, tabs)) continue;
+        for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
+            const unsigned long long e = tab[h];
+            if (e == 0ull) break;
+            if ((uint32_t) e != st.x) continue;
+            const uint64_t row = (e >> 32) - 1;
+            atomicAdd(&cnt[row], 1u);
+            atomicAdd(&sum[row], (unsigned long long) (long long) (int32_t) st.y);
+        }
+    }
+}
+
+// One pass over R writes the rows; a wave takes its output range with one atomic (and adds its
+// counts to the pair total with it).
+__global__ __launch_bounds__(256) void k_group_rows(const uint2* __restrict__ R, uint64_t n,
+                                                     const uint32_t* __restrict__ cnt,
+                                                     const unsigned long long* __restrict__ sum, uint32_t all,
+                                                     uint4* __restrict__ out, uint64_t cap,
+                                                     unsigned long long* __restrict__ res) {
+    const int      lane   = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x; i0 < n; i0 += stride) {  // (wave-uniform trip count)
+        const uint64_t i = i0 + threadIdx.x;
+        const uint32_t c = i < n ? cnt[i] : 0u;
+        const bool     w = i < n && (all || c);
+        const uint64_t b = __ballot(w);
+        const uint64_t pairs = wave_sum_u64((uint64_t) c);
+        if (b == 0) continue;  // (wave-uniform; no row, so no pair either)
+        unsigned long long base = 0;
+        if (lane == 0) {
+            base = atomicAdd(&res[0], (unsigned long long) __builtin_popcountll(b));
+            if (pairs) atomicAdd(&res[1], (unsigned long long) pairs);
+        }
+        base = __shfl(base, 0, 64);
+        const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (w && o < cap) {
+            const unsigned long long sm = sum[i];
+            out[o] = make_uint4(R[i].y, c, (uint32_t) sm, (uint32_t) (sm >> 32));
+        }
+    }
+}
+
+void launch_group_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask, uint32_t* cnt,
+                        unsigned long long* sum, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
+                        const CrcTables* tabs, hipStream_t st) {
+    k_group_probe<<<2048, 256, 0, st>>>(S, n, tab, mask, cnt, sum, g, slices, bm, tabs);
+}
+
+void launch_group_rows(const uint2* R, uint64_t n, const uint32_t* cnt, const unsigned long long* sum, uint32_t all,
+                       uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
+    k_group_rows<<<2048, 256, 0, st>>>(R, n, cnt, sum, all, out, cap, res);
+}
+
 // ===================================================================== launch wrappers
 void launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                 hipStream_t st) {

@@ -244,6 +244,37 @@ int hwbrj_join_outer_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_
                             tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
                             uint64_t * n_class /* [3], optional */, void * stream,
                             hwbrj_stats_t * stats, double * ms);
+/* The group join of R and S (join and aggregate per build-side row: SELECT R.payload, COUNT(*),
+ * SUM(S.payload) ... GROUP BY R-row): d_out receives one row per R row, not per key, in no
+ * particular order. count is the number of S rows whose key equals the R row's key, sum the sum of
+ * their payloads, each sign-extended from int32 (0 if there are none); three R rows sharing a key
+ * give three rows, each with the full count and sum. HWBRJ_GROUP_ALL writes every R row, so the row
+ * count is nR and the rows without a partner carry count = 0, sum = 0; HWBRJ_GROUP_MATCHED writes
+ * only the rows with count > 0. The sum is exact: nS must be below 2^32 (3 is returned otherwise),
+ * so |sum| < 2^63. n_pairs (optional) receives the sum of the counts, which is `matches` of the
+ * counting join with the same arguments. args == NULL runs without a filter; every filter
+ * configuration of hwbrj_join_materialize_device is accepted (the global-bitmap ones run the
+ * counting join and a side pass). It is the materializing pipeline up to the join; the join then
+ * accumulates per R tuple on chip and writes no pair ("Group joins"), so the output is
+ * bounded by nR whatever the skew.
+ * capacity is in rows: rows beyond it are not written, *n_out always holds the full row count and
+ * 7 is returned when it exceeds capacity; capacity 0 with d_out NULL is the count-only form. d_out
+ * must be 16-byte aligned. stats->filtered is "S-tuples after filter" as the counting join of the
+ * same arguments reports it, stats->matches the row count. ms (optional) receives the device time.
+ * An unknown kind returns 2 before any device call and without writing *n_out. Synchronous and
+ * single-GPU; it collects pending async joins like the other synchronous entries, and
+ * hwbrj_tables_info / hwbrj_tables_read answer 13 after it. */
+typedef struct hwbrj_group_row_t {   /* 16 bytes */
+    int32_t  r_payload;
+    uint32_t count;                  /* S rows whose key equals this R row's key */
+    int64_t  sum;                    /* sum of their payloads, each sign-extended from int32; 0 if none */
+} hwbrj_group_row_t;
+enum { HWBRJ_GROUP_MATCHED = 0, HWBRJ_GROUP_ALL = 1 };
+int hwbrj_join_group_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_S, uint64_t nS,
+                            const bloom_filter_args_t * args, int kind,
+                            hwbrj_group_row_t * d_out, uint64_t capacity, uint64_t * n_out,
+                            uint64_t * n_pairs /* optional */, void * stream,
+                            hwbrj_stats_t * stats, double * ms);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
