@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -138,6 +138,8 @@ def lib() -> ctypes.CDLL:
             ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
             ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
+        L.hwbrj_join_group_minmax_device.restype = ctypes.c_int
+        L.hwbrj_join_group_minmax_device.argtypes = L.hwbrj_join_group_device.argtypes
         L.hwbrj_set_materialize.restype = None
         L.hwbrj_set_materialize.argtypes = [ctypes.c_int]
         L.hwbrj_set_gpus.restype = ctypes.c_int
@@ -673,6 +675,67 @@ def group_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = 
     stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
     raw = out[: n.value]
     rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
+    return stats, rows, int(pairs.value), ms.value
+
+
+class _GroupMinMaxRow(ctypes.Structure):  # include/hwbrj.h hwbrj_group_minmax_row_t
+    _fields_ = [("r_payload", ctypes.c_int32), ("count", ctypes.c_uint32), ("min", ctypes.c_int32),
+                ("max", ctypes.c_int32)]
+
+
+class GroupMinMaxRows(NamedTuple):
+    """The rows of a min/max group join as GPU tensors of one length: r_payload, min and max (int32,
+    views of raw), count (int64, the 32-bit count zero-extended) and raw, the (n, 4) int32 buffer of
+    hwbrj_group_minmax_row_t rows they come from."""
+    r_payload: object
+    count: object
+    min: object
+    max: object
+    raw: object
+
+
+def group_minmax_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED, stream=None,
+                             capacity: Optional[int] = None):
+    """(Stats, GroupMinMaxRows, n_pairs, ms): the group join's MIN / MAX form
+    (hwbrj_join_group_minmax_device), one row per R row (not per key), unordered: the R row's payload,
+    the number of S rows with its key and the smallest and the largest of their payloads, compared as
+    signed int32. R rows sharing a key each carry the full count, min and max. GROUP_ALL returns every
+    R row (len(R) rows; without a partner count 0 and the identities min = 2**31 - 1, max = -2**31, so
+    min > max marks an empty group and partial rows over batches of S combine with a plain min and
+    max), GROUP_MATCHED only the rows with count > 0. n_pairs, Stats, ms and capacity are
+    group_join_device's."""
+    import torch
+    _check_rel(R, S)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n, pairs = ctypes.c_uint64(), ctypes.c_uint64()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_group_minmax_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, int(kind), out,
+                                                    cap, ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st),
+                                                    ctypes.byref(ms))
+
+    if capacity is None:
+        if int(kind) == GROUP_ALL:
+            capacity = R.shape[0]
+        else:
+            rc = call(None, 0)  # count only
+            if rc not in (0, 7):
+                _err(rc, "hwbrj_join_group_minmax_device")
+            capacity = n.value
+    for _ in range(2):
+        out = torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=R.device)
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, "hwbrj_join_group_minmax_device")
+    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    raw = out[: n.value]
+    rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
     return stats, rows, int(pairs.value), ms.value
 
 

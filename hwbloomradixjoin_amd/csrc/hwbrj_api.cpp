@@ -362,12 +362,13 @@ int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
 
 // The group join: the materializing pipeline up to the join, then per-R-tuple accumulators instead of
 // pairs (Engine::run_group); the global-bitmap mode runs the counting join (its filter and its
-// "S-tuples after filter") and the group side pass.
-int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
-                            const bloom_filter_args_t* args, int kind, hwbrj_group_row_t* d_out,
-                            uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
-                            hwbrj_stats_t* stats, double* ms) {
-    static_assert(sizeof(hwbrj_group_row_t) == 16, "a row is one 16-byte store");
+// "S-tuples after filter") and the group side pass. Both aggregate sets (agg: GroupAgg) share it:
+// their rows are 16 bytes and every clause of the contract is the same.
+static int join_group(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                      const bloom_filter_args_t* args, int kind, uint32_t agg, void* d_out, uint64_t capacity,
+                      uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms) {
+    static_assert(sizeof(hwbrj_group_row_t) == 16 && sizeof(hwbrj_group_minmax_row_t) == 16,
+                  "a row is one 16-byte store");
     if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {  // (before any device call)
         set_last_error("unknown group join kind (HWBRJ_GROUP_MATCHED, HWBRJ_GROUP_ALL)");
         return 2;
@@ -386,7 +387,7 @@ int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
     }
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
-    const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL};
+    const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL, agg};
     hwbrj_stats_t  st;
     uint64_t       n = 0, pairs = 0;
     int rc = e->run_group((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, req, &st, &pairs);
@@ -410,6 +411,23 @@ int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
         return 7;
     }
     return 0;
+}
+
+int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                            const bloom_filter_args_t* args, int kind, hwbrj_group_row_t* d_out,
+                            uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
+                            hwbrj_stats_t* stats, double* ms) {
+    return join_group(d_R, nR, d_S, nS, args, kind, GRP_COUNT_SUM, d_out, capacity, n_out, n_pairs, stream, stats, ms);
+}
+
+// The group join's MIN / MAX form: k_join_group's {count, min, max} accumulators ("Group
+// joins: MIN/MAX").
+int hwbrj_join_group_minmax_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                                   const bloom_filter_args_t* args, int kind, hwbrj_group_minmax_row_t* d_out,
+                                   uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
+                                   hwbrj_stats_t* stats, double* ms) {
+    return join_group(d_R, nR, d_S, nS, args, kind, GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs, stream, stats,
+                      ms);
 }
 
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE

@@ -301,7 +301,7 @@ void Engine::release() {
     for (DevBuf* b : {&slices, &bitmap, &rjoin, &rrun, &surv, &survcnt, &survoff,
                       &dense, &small, &bpos, &mtab, &mcount, &jtask, &jparts, &pjList,
                       &pjLstart, &pjSweep, &pjTab, &pjRegion, &pjTot, &pjSoff, &pjIbase, &pjCnt, &pjOff,
-                      &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &smark, &gcnt, &gsum, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
+                      &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &smark, &gcnt, &gsum, &gmin, &gmax, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
         b->release();
     for (DevBuf& b : xslot_) b.release();
     if (pending_) (void) hipEventSynchronize(ev_[8]);  // (the ring's joins end before it is freed)
@@ -749,6 +749,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
             GroupJoinParams gp{};
             gp.m       = mp;
             gp.all     = group->all ? 1u : 0u;
+            gp.agg     = group->agg;
             gp.out     = group->out;
             gp.n_pairs = pairs;
             launch_join_group(gp, NJ, stream);
@@ -1500,25 +1501,36 @@ int Engine::group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t n
     uint64_t T = 2;
     while (T < 2 * nR) T <<= 1;
     tab_.state = kTabOther;  // (a group join's tables are not read back, in this mode either)
-    const size_t rows = (size_t) std::max<uint64_t>(nR, 1);  // one count and one sum per R row
-    if (!mtab.ensure(T * 8) || !mcount.ensure(16) || !gcnt.ensure(rows * 4) || !gsum.ensure(rows * 8)) {
+    const size_t rows = (size_t) std::max<uint64_t>(nR, 1);  // one count and one sum (or min and max) per R row
+    const bool   minmax = group.agg == GRP_COUNT_MINMAX;
+    if (!mtab.ensure(T * 8) || !mcount.ensure(16) || !gcnt.ensure(rows * 4) ||
+        (minmax ? !gmin.ensure(rows * 4) || !gmax.ensure(rows * 4) : !gsum.ensure(rows * 8))) {
         set_last_error("hipMalloc failed (group join table)");
         return 4;
     }
     HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
     HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 16, stream));
     HWBRJ_CHECK(hipMemsetAsync(gcnt.p, 0, rows * 4, stream));
-    HWBRJ_CHECK(hipMemsetAsync(gsum.p, 0, rows * 8, stream));
+    if (minmax) launch_group_minmax_init(gmin.as<int32_t>(), gmax.as<int32_t>(), rows, stream);
+    else HWBRJ_CHECK(hipMemsetAsync(gsum.p, 0, rows * 8, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
     if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
     if (nR && nS) {
         Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
         if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_group_probe(dS, nS, mtab.as<unsigned long long>(), T - 1, gcnt.as<uint32_t>(),
-                           gsum.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_,
-                           stream);
+        if (minmax)
+            launch_group_probe_minmax(dS, nS, mtab.as<unsigned long long>(), T - 1, gcnt.as<uint32_t>(),
+                                      gmin.as<int32_t>(), gmax.as<int32_t>(), g, slices.as<uint32_t>(),
+                                      bitmap.as<uint32_t>(), d_tabs_, stream);
+        else
+            launch_group_probe(dS, nS, mtab.as<unsigned long long>(), T - 1, gcnt.as<uint32_t>(),
+                               gsum.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_,
+                               stream);
     }
-    if (nR)
+    if (nR && minmax)
+        launch_group_rows_minmax(dR, nR, gcnt.as<uint32_t>(), gmin.as<int32_t>(), gmax.as<int32_t>(),
+                                 group.all ? 1u : 0u, group.out, group.cap, mcount.as<unsigned long long>(), stream);
+    else if (nR)
         launch_group_rows(dR, nR, gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), group.all ? 1u : 0u, group.out,
                           group.cap, mcount.as<unsigned long long>(), stream);
     HWBRJ_CHECK(hipEventRecord(ev_[8], stream));

@@ -44,11 +44,13 @@ struct OuterReq {
     uint32_t null_pay;
 };
 // A group join's output: rows {R.payload, count, sum} (hwbrj_group_row_t, 16 bytes) into
-// out[0, cap). all: every R row is a row; otherwise those with count > 0.
+// out[0, cap). all: every R row is a row; otherwise those with count > 0. agg (GroupAgg):
+// GRP_COUNT_MINMAX gives rows {R.payload, count, min, max} (hwbrj_group_minmax_row_t) instead.
 struct GroupReq {
     uint4*   out;
     uint64_t cap;
     bool     all;
+    uint32_t agg = GRP_COUNT_SUM;
 };
 
 struct DevBuf {
@@ -349,6 +351,7 @@ class Engine {
     const uint64_t* outer_cls_ = nullptr;  // the last outer join's {R-only, S-only} counters (its ring slot)
     const uint64_t* group_pairs_ = nullptr;  // the last group join's pair counter (its ring slot)
     DevBuf gcnt, gsum;  // the group join's side pass: count and sum per R row (group_side)
+    DevBuf gmin, gmax;  // its min/max form: min and max per R row
     DevBuf dense2, kkcnt;  // basic k >= 2: the second dense candidate buffer, per-pass counts
     DevBuf jtask, jparts;  // join task table; parts per job (+ the task count)
     // partitioned join: owned partitions' lists, tables and received survivor descriptors

@@ -265,9 +265,14 @@ void   launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t
 // sum of their payloads (each sign-extended from int32); after the survivors of a piece its row
 // {R.payload, count, sum} (hwbrj_group_row_t as one uint4) is appended to out through m.count, up to
 // m.cap rows: every R tuple (all), or those with count > 0. *n_pairs += the counts.
+// agg = GRP_COUNT_MINMAX: the accumulator is {count, min, max} of the payloads as int32 (the identities
+// INT32_MAX and INT32_MIN where count is 0) and the row {R.payload, count, min, max}
+// (hwbrj_group_minmax_row_t as one uint4); everything else is the same.
+enum GroupAgg : uint32_t { GRP_COUNT_SUM = 0, GRP_COUNT_MINMAX = 1 };
 struct GroupJoinParams {
     MatJoinParams       m;
     uint32_t            all;
+    uint32_t            agg;      // GroupAgg
     uint4*              out;
     unsigned long long* n_pairs;  // zero on entry
 };
@@ -282,6 +287,16 @@ void   launch_group_probe(const uint2* S, uint64_t n, const unsigned long long* 
                           const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
 void   launch_group_rows(const uint2* R, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
                          uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st);
+// The side pass's min/max form: mn[row] and mx[row] (one int32 per R row, INT32_MAX and INT32_MIN
+// on entry: launch_group_minmax_init) take the payload of every matching S tuple.
+void   launch_group_minmax_init(int32_t* mn, int32_t* mx, uint64_t n, hipStream_t st);
+void   launch_group_probe_minmax(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
+                                 uint32_t* cnt, int32_t* mn, int32_t* mx, const Geometry& g,
+                                 const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs,
+                                 hipStream_t st);
+void   launch_group_rows_minmax(const uint2* R, uint64_t n, const uint32_t* cnt, const int32_t* mn,
+                                const int32_t* mx, uint32_t all, uint4* out, uint64_t cap,
+                                unsigned long long* res, hipStream_t st);
 
 void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                   hipStream_t st);

@@ -4767,10 +4767,37 @@ constexpr uint32_t kGrpWords = kMatBmWords + kMatBmWords / 4 + 3 * kMatRCap;
 static_assert(kGrpWords >= 2 * kMatT + 3 * kMatPiece, "LDS union (hash forms)");
 static_assert(kMatRCap == kMatThreads * kMatUB && kMatPiece == kMatThreads * kMatU, "one entry per (thread, k)");
 
+// AGG = GRP_COUNT_MINMAX overlays {count (u32), min (i32), max (i32)} on the same 12 bytes per tuple:
+// the 8 N bytes that hold N sums (gs) hold N minima and then N maxima, three arrays of words like
+// count and sum. Cleared to {0, INT32_MAX, INT32_MIN}; a survivor does one add and a signed min and
+// max (ds_add_u32, ds_min_i32, ds_max_i32). Both are idempotent, so the exactly-once argument is the
+// sum form's. N is the accumulators of the form: kMatRCap (bitmap path) or kMatPiece (hash forms).
+template <uint32_t AGG, uint32_t N>
+__device__ __forceinline__ void group_clear(uint32_t* gc, unsigned long long* gs, uint32_t i) {
+    if constexpr (AGG == GRP_COUNT_SUM) {
+        gs[i] = 0;
+    } else {
+        ((uint32_t*) gs)[i]     = 0x7FFFFFFFu;  // INT32_MAX
+        ((uint32_t*) gs)[N + i] = 0x80000000u;  // INT32_MIN
+    }
+    gc[i] = 0;
+}
+
+template <uint32_t AGG, uint32_t N>
+__device__ __forceinline__ void group_add(uint32_t* gc, unsigned long long* gs, uint32_t i, uint32_t sp) {
+    atomicAdd(&gc[i], 1u);
+    if constexpr (AGG == GRP_COUNT_SUM) {
+        atomicAdd(&gs[i], (unsigned long long) (long long) (int32_t) sp);
+    } else {
+        atomicMin((int*) gs + i, (int) sp);
+        atomicMax((int*) gs + N + i, (int) sp);
+    }
+}
+
 // The rows of this thread's NK tuples (idx[k]: the tuple's accumulator, kEmpty: none; pay[k]: its
 // payload). Contains barriers; the first one completes the accumulators. ptot is zero on entry and
 // on return.
-template <bool ALL, int NK>
+template <bool ALL, uint32_t AGG, uint32_t N, int NK>
 __device__ __forceinline__ void group_rows(const GroupJoinParams& G, const uint32_t (&idx)[NK],
                                            const uint32_t (&pay)[NK], const uint32_t* gc,
                                            const unsigned long long* gs, uint32_t* wsum,
@@ -4799,19 +4826,24 @@ __device__ __forceinline__ void group_rows(const GroupJoinParams& G, const uint3
     for (int k = 0; k < NK; k++) {
         if (!((sel >> k) & 1u)) continue;
         if (o < G.m.cap) {
-            const unsigned long long sm = gs[idx[k]];
-            G.out[o] = make_uint4(pay[k], c[k], (uint32_t) sm, (uint32_t) (sm >> 32));
+            if constexpr (AGG == GRP_COUNT_SUM) {
+                const unsigned long long sm = gs[idx[k]];
+                G.out[o] = make_uint4(pay[k], c[k], (uint32_t) sm, (uint32_t) (sm >> 32));
+            } else {
+                const uint32_t* gm = (const uint32_t*) gs;
+                G.out[o] = make_uint4(pay[k], c[k], gm[idx[k]], gm[N + idx[k]]);
+            }
         }
         o++;
     }
 }
 
-template <bool ALL>
+template <bool ALL, uint32_t AGG>
 __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_join_group(GroupJoinParams G) {
     const MatJoinParams& P = G.m;
     // LDS union: bitmap path {bitmap [kMatBmWords], rank prefix (u16) [kMatBmWords / 2], sums (u64)
     // [kMatRCap], counts [kMatRCap]}, or hash forms {keys [kMatT], ordinals [kMatT], sums (u64)
-    // [kMatPiece], counts [kMatPiece]}
+    // [kMatPiece], counts [kMatPiece]}; GRP_COUNT_MINMAX: minima and maxima (i32) where the sums are
     __shared__ __attribute__((aligned(16))) uint32_t smem[kGrpWords];
     uint32_t* tk = smem;
     uint32_t* to = smem + kMatT;
@@ -4843,10 +4875,6 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
         base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
                P.surv_off[(uint64_t) it * NSUB + s];
     };
-    auto add = [&](uint32_t* gc, unsigned long long* gs, uint32_t i, uint32_t sp) {
-        atomicAdd(&gc[i], 1u);
-        atomicAdd(&gs[i], (unsigned long long) (long long) (int32_t) sp);
-    };
     if (tid == 0) ptot = 0;  // (first added to after a barrier)
     // ---- single-shot form
     if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
@@ -4876,10 +4904,7 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
             uint32_t*           bcnt = smem + kMatBmWords + kMatBmWords / 4 + 2 * kMatRCap;
             const uint64_t*     bm64 = (const uint64_t*) smem;
             for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) bmw[i] = 0;
-            for (uint32_t i = tid; i < rtot; i += kMatThreads) {
-                bsum[i] = 0;
-                bcnt[i] = 0;
-            }
+            for (uint32_t i = tid; i < rtot; i += kMatThreads) group_clear<AGG, kMatRCap>(bcnt, bsum, i);
             __syncthreads();  // descriptors visible, bitmap and accumulators cleared
             uint32_t rv[kMatUB], rp[kMatUB];
 #pragma unroll
@@ -4943,12 +4968,12 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
                     for (int k = 0; k < kMatUB; k++) sp[k] = (hit >> k) & 1u ? P.s_pay[pos[k]] : 0u;
 #pragma unroll
                     for (int k = 0; k < kMatUB; k++)
-                        if ((hit >> k) & 1u) add(bcnt, bsum, rank(v[k]), sp[k]);
+                        if ((hit >> k) & 1u) group_add<AGG, kMatRCap>(bcnt, bsum, rank(v[k]), sp[k]);
                 }
                 uint32_t idx[kMatUB];
 #pragma unroll
                 for (int k = 0; k < kMatUB; k++) idx[k] = rv[k] != kEmpty ? rank(rv[k]) : kEmpty;
-                group_rows<ALL, kMatUB>(G, idx, rp, bcnt, bsum, wsum, &ptot, &obase);
+                group_rows<ALL, AGG, kMatRCap, kMatUB>(G, idx, rp, bcnt, bsum, wsum, &ptot, &obase);
                 return;
             }
             // duplicate R keys: the hash table (over the same LDS)
@@ -4956,10 +4981,7 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
         if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform)
             __syncthreads();  // descriptors visible; the bitmap path is done with the LDS
             for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            for (uint32_t i = tid; i < rtot; i += kMatThreads) {
-                hsum[i] = 0;
-                hcnt[i] = 0;
-            }
+            for (uint32_t i = tid; i < rtot; i += kMatThreads) group_clear<AGG, kMatPiece>(hcnt, hsum, i);
             __syncthreads();
             uint32_t rc[kMatU], rp[kMatU], v[kMatU], m[kMatU], idx[kMatU];
             uint64_t a[kMatU];
@@ -5000,10 +5022,10 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
                 for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
                     const uint32_t x = tk[h];
                     if (x == kEmpty) break;
-                    if (x == v[k]) add(hcnt, hsum, to[h], sp[k]);
+                    if (x == v[k]) group_add<AGG, kMatPiece>(hcnt, hsum, to[h], sp[k]);
                 }
             }
-            group_rows<ALL, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
+            group_rows<ALL, AGG, kMatPiece, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
             return;
         }
     }
@@ -5026,10 +5048,7 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
             const uint32_t pe = min(rtot, pb + kMatPiece);
             __syncthreads();  // the previous piece's survivors and rows are done with the table
             for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            for (uint32_t i = tid; i < kMatPiece; i += kMatThreads) {
-                hsum[i] = 0;
-                hcnt[i] = 0;
-            }
+            for (uint32_t i = tid; i < kMatPiece; i += kMatThreads) group_clear<AGG, kMatPiece>(hcnt, hsum, i);
             uint32_t rc[kMatU], rp[kMatU], idx[kMatU];  // this thread's R tuples of the piece
 #pragma unroll
             for (int k = 0; k < kMatU; k++) {
@@ -5085,14 +5104,14 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
                         for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
                             const uint32_t x = tk[h];
                             if (x == kEmpty) break;
-                            if (x == v[k]) add(hcnt, hsum, to[h], sp[k]);
+                            if (x == v[k]) group_add<AGG, kMatPiece>(hcnt, hsum, to[h], sp[k]);
                         }
                     }
                 }
             }
             // (its first barrier: the accumulators final; under ALL a job without probe items skips
             // the survivor loop, and the barrier also completes the table it does not read)
-            group_rows<ALL, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
+            group_rows<ALL, AGG, kMatPiece, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
         }
     }
 }
@@ -5100,8 +5119,13 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))
 void launch_join_group(const GroupJoinParams& p0, uint32_t jobs, hipStream_t st) {
     GroupJoinParams p = p0;
     p.m.xcd8          = ((jobs >> p.m.log2NSUB) % 8 == 0) ? 1u : 0u;
-    if (p.all) k_join_group<true><<<jobs, kMatThreads, 0, st>>>(p);
-    else k_join_group<false><<<jobs, kMatThreads, 0, st>>>(p);
+    if (p.agg == GRP_COUNT_MINMAX) {
+        if (p.all) k_join_group<true, GRP_COUNT_MINMAX><<<jobs, kMatThreads, 0, st>>>(p);
+        else k_join_group<false, GRP_COUNT_MINMAX><<<jobs, kMatThreads, 0, st>>>(p);
+    } else {
+        if (p.all) k_join_group<true, GRP_COUNT_SUM><<<jobs, kMatThreads, 0, st>>>(p);
+        else k_join_group<false, GRP_COUNT_SUM><<<jobs, kMatThreads, 0, st>>>(p);
+    }
 }
 
 // The group join's side pass (global-bitmap mode): k_mat_probe's walk with the filter as a pre-test;
@@ -5168,6 +5192,83 @@ void launch_group_probe(const uint2* S, uint64_t n, const unsigned long long* ta
 void launch_group_rows(const uint2* R, uint64_t n, const uint32_t* cnt, const unsigned long long* sum, uint32_t all,
                        uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
     k_group_rows<<<2048, 256, 0, st>>>(R, n, cnt, sum, all, out, cap, res);
+}
+
+// The side pass's min/max form: the same walk and the same row pass over {cnt, mn, mx}; mn and mx
+// start at the identities (a byte memset cannot write INT32_MAX).
+__global__ __launch_bounds__(256) void k_group_minmax_init(int32_t* __restrict__ mn, int32_t* __restrict__ mx,
+                                                            uint64_t n) {
+    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        mn[i] = INT32_MAX;
+        mx[i] = INT32_MIN;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_group_probe_minmax(const uint2* __restrict__ S, uint64_t n,
+                                                             const unsigned long long* __restrict__ tab,
+                                                             uint64_t mask, uint32_t* __restrict__ cnt,
+                                                             int32_t* __restrict__ mn, int32_t* __restrict__ mx,
+                                                             Geometry g, const uint32_t* __restrict__ slices,
+                                                             const uint32_t* __restrict__ bm,
+                                                             const CrcTables* __restrict__ tabs) {
+    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const uint2 st = S[i];
+        if (!mat_filter(st.x, g, slices, bm, tabs)) continue;
+        for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
+            const unsigned long long e = tab[h];
+            if (e == 0ull) break;
+            if ((uint32_t) e != st.x) continue;
+            const uint64_t row = (e >> 32) - 1;
+            atomicAdd(&cnt[row], 1u);
+            atomicMin(&mn[row], (int32_t) st.y);
+            atomicMax(&mx[row], (int32_t) st.y);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_group_rows_minmax(const uint2* __restrict__ R, uint64_t n,
+                                                            const uint32_t* __restrict__ cnt,
+                                                            const int32_t* __restrict__ mn,
+                                                            const int32_t* __restrict__ mx, uint32_t all,
+                                                            uint4* __restrict__ out, uint64_t cap,
+                                                            unsigned long long* __restrict__ res) {
+    const int      lane   = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x; i0 < n; i0 += stride) {  // (wave-uniform trip count)
+        const uint64_t i = i0 + threadIdx.x;
+        const uint32_t c = i < n ? cnt[i] : 0u;
+        const bool     w = i < n && (all || c);
+        const uint64_t b = __ballot(w);
+        const uint64_t pairs = wave_sum_u64((uint64_t) c);
+        if (b == 0) continue;  // (wave-uniform; no row, so no pair either)
+        unsigned long long base = 0;
+        if (lane == 0) {
+            base = atomicAdd(&res[0], (unsigned long long) __builtin_popcountll(b));
+            if (pairs) atomicAdd(&res[1], (unsigned long long) pairs);
+        }
+        base = __shfl(base, 0, 64);
+        const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (w && o < cap) out[o] = make_uint4(R[i].y, c, (uint32_t) mn[i], (uint32_t) mx[i]);
+    }
+}
+
+void launch_group_minmax_init(int32_t* mn, int32_t* mx, uint64_t n, hipStream_t st) {
+    k_group_minmax_init<<<2048, 256, 0, st>>>(mn, mx, n);
+}
+
+void launch_group_probe_minmax(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
+                               uint32_t* cnt, int32_t* mn, int32_t* mx, const Geometry& g, const uint32_t* slices,
+                               const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
+    k_group_probe_minmax<<<2048, 256, 0, st>>>(S, n, tab, mask, cnt, mn, mx, g, slices, bm, tabs);
+}
+
+void launch_group_rows_minmax(const uint2* R, uint64_t n, const uint32_t* cnt, const int32_t* mn, const int32_t* mx,
+                              uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
+    k_group_rows_minmax<<<2048, 256, 0, st>>>(R, n, cnt, mn, mx, all, out, cap, res);
 }
 
 // ===================================================================== launch wrappers

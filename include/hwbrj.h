@@ -275,6 +275,34 @@ int hwbrj_join_group_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_
                             hwbrj_group_row_t * d_out, uint64_t capacity, uint64_t * n_out,
                             uint64_t * n_pairs /* optional */, void * stream,
                             hwbrj_stats_t * stats, double * ms);
+/* The group join's MIN / MAX form (SELECT R.payload, COUNT(*), MIN(S.payload), MAX(S.payload) ...
+ * GROUP BY R-row): hwbrj_join_group_device with another row. count is the number of S rows whose
+ * key equals the R row's key, min and max the smallest and the largest of their payloads, compared
+ * as signed int32. A row without a partner (only under HWBRJ_GROUP_ALL) carries the identities of
+ * the two operations, min = INT32_MAX and max = INT32_MIN, so min > max marks an empty group. No
+ * null marker of the caller's is taken: count == 0 already says that the group is empty, and a
+ * caller who streams S in batches combines the partial rows of an R row with a plain min and max
+ * (and a sum of the counts), without a special case. Every other clause is
+ * hwbrj_join_group_device's: kind (an unknown one returns 2 before any device call and without
+ * writing *n_out), one row per R row in no particular order, R rows sharing a key each carrying the
+ * full count, min and max; capacity in rows, *n_out the full row count, 7 when it exceeds capacity,
+ * capacity 0 with d_out NULL as the count-only form; d_out 16-byte aligned (2 otherwise: a row is
+ * one 16-byte store); nS below 2^32 (3 otherwise: the count is 32 bits); n_pairs (optional) the sum
+ * of the counts; stats->filtered the counting join's value and stats->matches the row count; args
+ * == NULL and every filter configuration of hwbrj_join_materialize_device; synchronous, single-GPU,
+ * collects pending async joins, and hwbrj_tables_info / hwbrj_tables_read answer 13 after it.
+ * COUNT, SUM, MIN and MAX together take both entries ("Group joins: MIN/MAX"). */
+typedef struct hwbrj_group_minmax_row_t {   /* 16 bytes */
+    int32_t  r_payload;
+    uint32_t count;                  /* S rows whose key equals this R row's key */
+    int32_t  min;                    /* smallest of their payloads (signed); INT32_MAX if count == 0 */
+    int32_t  max;                    /* largest of their payloads (signed);  INT32_MIN if count == 0 */
+} hwbrj_group_minmax_row_t;
+int hwbrj_join_group_minmax_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_S, uint64_t nS,
+                                   const bloom_filter_args_t * args, int kind,
+                                   hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
+                                   uint64_t * n_out, uint64_t * n_pairs /* optional */,
+                                   void * stream, hwbrj_stats_t * stats, double * ms);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
