@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_keys_device", "join_keys_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -105,6 +105,10 @@ def lib() -> ctypes.CDLL:
         L.hwbrj_join_device_algo.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                              ctypes.c_uint64, ctypes.POINTER(_BloomArgs),
                                              ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(_Stats)]
+        L.hwbrj_join_keys_device.restype = ctypes.c_int
+        L.hwbrj_join_keys_device.argtypes = L.hwbrj_join_device_algo.argtypes
+        L.hwbrj_join_keys_device_async.restype = ctypes.c_int
+        L.hwbrj_join_keys_device_async.argtypes = L.hwbrj_join_device_async.argtypes
         L.hwbrj_join_wait.restype = ctypes.c_int
         L.hwbrj_join_wait.argtypes = [ctypes.c_void_p]
         L.hwbrj_set_async_timing.restype = ctypes.c_int
@@ -499,6 +503,60 @@ def join_device(R, S, args: Optional[BloomFilterArgs] = None, stream=None,
                                       sp, ctypes.byref(st))
     _err(rc, "hwbrj_join_device_algo")
     return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
+
+
+def _check_keys(Rk, Sk, stream):
+    """Both key columns: contiguous 1-D torch.int32 tensors on one GPU, each (when non-empty)
+    starting at a 16-byte boundary. Switches the library's HIP device as _check_rel does. Without
+    a stream of the caller's, waits for torch's current stream (the columns' producer)."""
+    import torch
+    for name, t in (("Rk", Rk), ("Sk", Sk)):
+        if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-D torch.int32 tensor on the GPU "
+                             "(a strided view such as T[:, 0]: call .contiguous() first)")
+        if t.numel() and t.data_ptr() % 16:
+            raise ValueError(f"{name} must start at a 16-byte boundary (a slice of a column: cut at "
+                             "multiples of 4 keys)")
+    if Rk.device != Sk.device:
+        raise ValueError(f"Rk is on {Rk.device} but Sk is on {Sk.device}")
+    _err(lib().hwbrj_set_device(Rk.device.index or 0), "hwbrj_set_device")
+    if stream is None:
+        # a column is typically cut by a torch kernel (.contiguous()) that may still be running on
+        # torch's current stream, and the library's own stream does not wait for that stream
+        torch.cuda.current_stream(Rk.device).synchronize()
+
+
+def join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None,
+                     algorithm: int = ALGO_PRO) -> Stats:
+    """The counting join of join_device on key columns (hwbrj_join_keys_device): Rk, Sk are
+    contiguous 1-D torch.int32 GPU tensors of keys, 16-byte aligned. No payloads are read, so a
+    columnar caller needs no (N, 2) interleaving pass. A strided view such as T[:, 0] of a tuple
+    tensor is refused: call .contiguous() first. args, stream, algorithm and the returned Stats
+    are join_device's. With stream=None the join runs on the library's own stream after torch's
+    current stream has finished (the kernel that cut the columns may still be running there); a
+    caller who passes a stream orders the columns' producers before the join on it."""
+    _check_keys(Rk, Sk, stream)
+    st = _Stats()
+    a = args._c() if args is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    rc = lib().hwbrj_join_keys_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0],
+                                      ctypes.byref(a) if a is not None else None, int(algorithm),
+                                      sp, ctypes.byref(st))
+    _err(rc, "hwbrj_join_keys_device")
+    return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
+
+
+def join_keys_device_async(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None) -> None:
+    """Enqueue join_keys_device without waiting (hwbrj_join_keys_device_async); collected by
+    join_wait / join_wait_all, in any mix with join_device_async. A strided view such as T[:, 0]
+    is refused: call .contiguous() first. The stream rule is join_keys_device's: a stream of the
+    caller's must already order whatever wrote the columns."""
+    _check_keys(Rk, Sk, stream)
+    a = args._c() if args is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    _err(lib().hwbrj_join_keys_device_async(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0],
+                                            ctypes.byref(a) if a is not None else None, sp),
+         "hwbrj_join_keys_device_async")
 
 
 def join_materialize_device(R, S, args: Optional[BloomFilterArgs] = None, stream=None,

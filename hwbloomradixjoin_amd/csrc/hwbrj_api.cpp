@@ -190,6 +190,33 @@ int hwbrj_join_device_async(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
     return e->run_async((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream);
 }
 
+// Key columns: a non-empty column starts at a 16-byte boundary (the scatter's 16-byte loads and its
+// workgroup ranges in units of 4 keys). Checked before any device call.
+static bool keys_aligned(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, uint64_t nS) {
+    const bool bad_r = nR && ((uintptr_t) d_Rkeys & 15u), bad_s = nS && ((uintptr_t) d_Skeys & 15u);
+    if (!bad_r && !bad_s) return true;
+    set_last_error(std::string("key column ") + (bad_r ? "R" : "S") +
+                   " is not 16-byte aligned (shard a column at multiples of 4 keys)");
+    return false;
+}
+
+int hwbrj_join_keys_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, uint64_t nS,
+                           const bloom_filter_args_t* args, int algorithm, void* stream,
+                           hwbrj_stats_t* stats) {
+    if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;
+    return e->run(d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream, stats, algorithm, SRC_KEYS);
+}
+
+int hwbrj_join_keys_device_async(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys,
+                                 uint64_t nS, const bloom_filter_args_t* args, void* stream) {
+    if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;
+    return e->run_async(d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream, 0, SRC_KEYS);
+}
+
 int hwbrj_join_partitioned(const hwbrj_exchange_t* x, int rank, int world, const tuple_t* d_R,
                            uint64_t nR, uint64_t nR_total, const tuple_t* d_S, uint64_t nS,
                            const bloom_filter_args_t* args, hwbrj_stats_t* stats) {

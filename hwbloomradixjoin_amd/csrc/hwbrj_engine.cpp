@@ -320,18 +320,19 @@ uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
     return (per + 31) / 32 + F + 1;
 }
 
-int Engine::run(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind);
+int Engine::run(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
+                const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind,
+                int layout) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind, nullptr, nullptr, nullptr, nullptr, layout);
     return rc ? rc : wait(st);
 }
 
-int Engine::run_async(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                      const bloom_filter_args_t* args, hipStream_t stream, int jkind) {
+int Engine::run_async(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
+                      const bloom_filter_args_t* args, hipStream_t stream, int jkind, int layout) {
     // back-to-back joins: no phase events (each marker idles the GPU ~6 us between the kernels
     // around it, profiles/r03/gaps_*), so hwbrj_join_wait reports counts only
     phase_ev_    = false;
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind);
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind, nullptr, nullptr, nullptr, nullptr, layout);
     phase_ev_    = true;
     return rc;
 }
@@ -394,9 +395,13 @@ int Engine::run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS
 // mat / semi / outer / group: the payload-carrying pipeline (pl below). mat carries both relations'
 // payloads, and so do outer and group (from the join on they have kernels of their own); semi only
 // S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
-int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+// layout: what dR and dS point to, SRC_TUPLES or SRC_KEYS (key columns: the counting join only).
+// It selects the kernels that read the relations; the partition words, and so everything from the
+// pools on, do not depend on it.
+int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                    const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group) {
+                    const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group,
+                    int layout) {
     const MatReq omat{outer ? outer->out : nullptr, outer ? outer->cap : group ? group->cap : 0};
     if (outer || group) mat = &omat;  // (the materializing pipeline up to the join)
     if (jkind < 0 || jkind > 2) {
@@ -408,6 +413,10 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     Geometry    g;
     std::string err;
     const bool  pl = mat || semi;  // S payloads beside the words, the materializing geometry
+    if (layout != SRC_TUPLES && (layout != SRC_KEYS || pl)) {
+        set_last_error("key columns: the counting join only");
+        return 2;
+    }
     if (!plan_geometry(args, nR, &g, &err, pl)) {
         set_last_error(err);
         return 2;
@@ -419,7 +428,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     if (!pl && g.mode == MODE_SLICE_BASIC && g.k > 1 && (uint64_t) g.k * nR <= (1ull << 31)) {
         if (!stream) stream = own_stream_;
         if (pending_ && stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(stream, ev_[8], 0));
-        return enqueue_basic_kk(dR, nR, dS, nS, g, stream, jkind);
+        return enqueue_basic_kk(dR, nR, dS, nS, g, stream, jkind, layout);
     }
     if (!stream) stream = own_stream_;
     // Every join on this device shares this Engine's scratch (pools, lists, slices, counters):
@@ -515,7 +524,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         ss.zero_small    = nullptr;
         ss.zero_word     = nullptr;
         if (g.mode == MODE_GLOBAL) {
-            launch_probe_global(dS, nS, g, d_tabs_, bitmap.as<uint32_t>(), dense.as<uint32_t>(),
+            launch_probe_global(dS, layout, nS, g, d_tabs_, bitmap.as<uint32_t>(), dense.as<uint32_t>(),
                                 d_dcount, st);
             ss.src   = dense.p;
             ss.n     = nS;
@@ -528,7 +537,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         S_.bind(&ss, capS);
         ss.ppool = pl ? ppoolS.as<uint32_t>() : nullptr;
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
-        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : SRC_TUPLES, SIDE_S, G, st);
+        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : layout, SIDE_S, G, st);
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
         if (marks) HWBRJ_CHECK(mark(4, st));
         index_side(S_, capS, g.log2F, CH, nseg, G, st);
@@ -567,13 +576,13 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
         if (const int rc = s_pass(stream, true)) return rc;
     // ---------------------------------------------------------------- R: pass-1 (+ filter)
     if (g.mode == MODE_GLOBAL)
-        launch_build_global(dR, nR, g, d_tabs_, bitmap.as<uint32_t>(), stream);
+        launch_build_global(dR, layout, nR, g, d_tabs_, bitmap.as<uint32_t>(), stream);
     sp.src        = dR;
     sp.n          = nR;
     sp.n_dev      = nullptr;
     sp.ppool      = mat ? ppoolR.as<uint32_t>() : nullptr;
     R_.bind(&sp, capR);
-    launch_scatter(sp, SRC_TUPLES, SIDE_R, G, stream);
+    launch_scatter(sp, layout, SIDE_R, G, stream);
     HWBRJ_CHECK(mark(1, stream));
     index_side(R_, capR, g.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
@@ -621,7 +630,7 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     if (basic_kk) {
         // basic k >= 2: the k bit positions of every R key, partitioned by slice with the S-side
         // scatter buffers (free until the S pass), then one LDS slice build per partition
-        launch_bitpos(dR, nR, g, bpos.as<uint32_t>(), stream);
+        launch_bitpos(dR, layout, nR, g, bpos.as<uint32_t>(), stream);
         sp.src        = bpos.p;
         sp.n          = nRk;
         sp.n_dev      = nullptr;
@@ -856,8 +865,8 @@ int Engine::enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
 // the last pass are re-partitioned by code (MODE_CODE_OF_KEY), the join's layout, so the join
 // takes its bitmap path like the blocked filter's: R is partitioned by code for the join, and the
 // slices are built from R's partitioned bit positions (k_bitpos, k_slice_fill).
-int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                             const Geometry& g, hipStream_t stream, int jkind) {
+int Engine::enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
+                             const Geometry& g, hipStream_t stream, int jkind, int layout) {
     Geometry    gj;  // the join layout: R and the survivors partitioned by code
     std::string err;
     if (!plan_geometry(nullptr, nR, &gj, &err)) {
@@ -922,7 +931,7 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     sp.g   = gj;
     sp.src = dR;
     sp.n   = nR;
-    launch_scatter(sp, SRC_TUPLES, SIDE_R, G, stream);
+    launch_scatter(sp, layout, SIDE_R, G, stream);
     HWBRJ_CHECK(mark(1, stream));
     index_side(R_, capR, gj.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
@@ -947,9 +956,9 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
         sp.src      = dR;
         sp.n        = nRk;
         sp.vn       = nR;
-        launch_scatter(sp, SRC_TUPLES, SIDE_R, G, stream);
+        launch_scatter(sp, layout, SIDE_R, G, stream);
     } else {
-        launch_bitpos(dR, nR, g, bpos.as<uint32_t>(), stream);
+        launch_bitpos(dR, layout, nR, g, bpos.as<uint32_t>(), stream);
         sp.g   = g;
         sp.src = bpos.p;
         sp.n   = nRk;
@@ -964,7 +973,7 @@ int Engine::enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint
     sp.g   = g;
     sp.src = dS;
     sp.n   = nS;
-    launch_scatter(sp, SRC_TUPLES, SIDE_S, G, stream);
+    launch_scatter(sp, layout, SIDE_S, G, stream);
     HWBRJ_CHECK(mark(4, stream));
     index_side(S_, capS, g.log2F, CH, nseg, G, stream);
     HWBRJ_CHECK(mark(5, stream));

@@ -97,13 +97,17 @@ class Engine {
   public:
     explicit Engine(int device);
     ~Engine();
-    // Synchronous join of device-resident tuples. Returns 0 on success.
+    // Synchronous join of device-resident relations. Returns 0 on success.
     // jkind: the per-partition join (JoinParams::jkind: 0 PRO, 1 PRH, 2 PRHO).
-    int  run(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-             const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind = 0);
+    // layout: what dR and dS both point to: SRC_TUPLES (uint2 {key, payload}) or SRC_KEYS (one
+    // uint32 key per element, 16-byte aligned). Only the kernels that read the relations differ.
+    int  run(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
+             const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind = 0,
+             int layout = SRC_TUPLES);
     // Enqueue only (wait = false in run): wait() then waits for the last enqueued join.
-    int  run_async(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                   const bloom_filter_args_t* args, hipStream_t stream, int jkind = 0);
+    int  run_async(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
+                   const bloom_filter_args_t* args, hipStream_t stream, int jkind = 0,
+                   int layout = SRC_TUPLES);
     int  wait(hwbrj_stats_t* st);
     // Every join enqueued since the last wait / wait_all, oldest first, each with its own counts
     // (they stay on the device in a ring of kJoinRing result slots, one per join; an enqueue that
@@ -317,13 +321,14 @@ class Engine {
     void         ring_drop() { jr_.clear(); jdone_.clear(); }
     hipError_t   mark(int i, hipStream_t stream);  // ev_[i] when phase_ev_
     bool         alloc_only_   = false;  // reserve(): enqueue returns after its allocations
-    int          enqueue(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+    int          enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                          const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                          const MatReq* mat = nullptr, const SemiReq* semi = nullptr,
-                         const OuterReq* outer = nullptr, const GroupReq* group = nullptr);
+                         const OuterReq* outer = nullptr, const GroupReq* group = nullptr,
+                         int layout = SRC_TUPLES);
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
-    int          enqueue_basic_kk(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
-                                  const Geometry& g, hipStream_t stream, int jkind);
+    int          enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
+                                  const Geometry& g, hipStream_t stream, int jkind, int layout);
     // what tables_info / tables_read need of the last enqueued join: which pipeline left its tables
     // in the buffers below, and the shape they are indexed with
     enum { kTabNone = 0, kTabJoin = 1, kTabOther = 2 };  // kTabOther: a pipeline with other tables

@@ -12,10 +12,12 @@
 
 namespace hwbrj {
 
-enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1 };
+// What a scatter reads: {key, payload} tuples, 4-byte codes, or a column of 4-byte keys (hashed as
+// the tuples' keys are). SRC_KEYS is also the input layout of a whole counting join (Engine::run).
+enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2 };
 
 struct ScatterParams {
-    const void*      src;          // uint2 tuples {key, payload} or uint32 codes
+    const void*      src;          // uint2 tuples {key, payload}, uint32 codes or uint32 keys
     uint64_t         n;            // element count (ignored when n_dev != nullptr)
     const uint64_t*  n_dev;        // optional device-resident element count
     uint32_t*        pool;         // [G * cap][32] chunk words
@@ -27,7 +29,7 @@ struct ScatterParams {
     uint64_t         cap;          // chunk capacity of one workgroup region
     const uint32_t*  seg_cnt;      // SRC_CODES from per-workgroup segments: workgroup w partitions
     uint64_t         seg_stride;   // src + w * seg_stride (elements), seg_cnt[w] of them; or nullptr
-    uint64_t         vn;           // MODE_BASIC_POS: tuples of src (n = k * vn elements, k <= grid)
+    uint64_t         vn;           // MODE_BASIC_POS: tuples / keys of src (n = k * vn elements, k <= grid)
     // the join's per-call zeroing, done by workgroup 0 instead of memset dispatches: zero_small[0, 16)
     // (counts) and *zero_word (the join's extra-task count), each when not nullptr
     uint32_t*        zero_small;
@@ -303,13 +305,14 @@ void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_
 void   launch_zipf(const int32_t* rnd, uint64_t cnt, uint64_t row0, const double* lut,
                    const uint32_t* alphabet, uint32_t size, uint2* out, uint64_t n_above,
                    uint32_t above_base, const Perm& perm, hipStream_t st);
-void   launch_build_global(const uint2* R, uint64_t n, const Geometry& g, const CrcTables* tabs,
+// src (here and in launch_bitpos): SRC_TUPLES (uint2 {key, payload}) or SRC_KEYS (uint32 keys)
+void   launch_build_global(const void* R, int src, uint64_t n, const Geometry& g, const CrcTables* tabs,
                            uint32_t* bm, hipStream_t st);
-void   launch_probe_global(const uint2* S, uint64_t n, const Geometry& g, const CrcTables* tabs,
+void   launch_probe_global(const void* S, int src, uint64_t n, const Geometry& g, const CrcTables* tabs,
                            const uint32_t* bm, uint32_t* out, uint64_t* out_count, hipStream_t st);
 // basic k >= 2: every R key's k bit positions (element j * n + i), then the slices from their
 // partitioned chunk lists
-void   launch_bitpos(const uint2* R, uint64_t n, const Geometry& g, uint32_t* out, hipStream_t st);
+void   launch_bitpos(const void* R, int src, uint64_t n, const Geometry& g, uint32_t* out, hipStream_t st);
 void   launch_slice_fill(const uint32_t* pool, const uint32_t* list, const uint32_t* list_start,
                          const Geometry& g, uint32_t* slices, hipStream_t st);
 size_t scatter_lds_bytes(uint32_t log2F);

@@ -336,7 +336,13 @@ __device__ __forceinline__ bool global_contains(uint32_t key, uint32_t code, con
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_build_global(const uint2* R, uint64_t n, Geometry g,
+// T: the relation's element, uint2 ({key, payload} tuples) or uint32_t (a key column); k_build_global,
+// k_probe_global and k_bitpos are instantiated for both.
+__device__ __forceinline__ uint32_t elem_key(const uint2& t) { return t.x; }
+__device__ __forceinline__ uint32_t elem_key(uint32_t k) { return k; }
+
+template <class T>
+__global__ __launch_bounds__(256) void k_build_global(const T* R, uint64_t n, Geometry g,
                                                       const CrcTables* tabs, uint32_t* bm) {
     __shared__ uint32_t fwd[128];
     load_tab(fwd, &tabs->fwd[0][0]);
@@ -344,13 +350,14 @@ __global__ __launch_bounds__(256) void k_build_global(const uint2* R, uint64_t n
     uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        const uint32_t key = R[i].x;
+        const uint32_t key = elem_key(R[i]);
         global_positions_apply_add(key, key_code(fwd, key), g, bm);
     }
 }
 
 // Direct probe of the global bitmap; survivors' codes are appended densely (one atomic per block).
-__global__ __launch_bounds__(1024) void k_probe_global(const uint2* S, uint64_t n, Geometry g,
+template <class T>
+__global__ __launch_bounds__(1024) void k_probe_global(const T* S, uint64_t n, Geometry g,
                                                        const CrcTables* tabs, const uint32_t* bm,
                                                        uint32_t* out, uint64_t* out_count) {
     __shared__ uint32_t fwd[128];
@@ -364,7 +371,7 @@ __global__ __launch_bounds__(1024) void k_probe_global(const uint2* S, uint64_t 
         uint32_t       code = 0;
         uint32_t       pass = 0;
         if (i < n) {
-            const uint32_t key = S[i].x;
+            const uint32_t key = elem_key(S[i]);
             code               = key_code(fwd, key);
             pass               = global_contains(key, code, g, bm) ? 1u : 0u;
         }
@@ -429,6 +436,12 @@ constexpr int      kScPayThreads = 1024;  // the materializing scatter (scatter_
 #define HWBRJ_SC_SAUX_R HWBRJ_SC_SAUX  // (the R scatter's, A/B)
 #endif
 constexpr int      kScPre     = HWBRJ_SC_PRE;             // rounds of loads in flight (1 or 2)
+#ifndef HWBRJ_SC_PRE_KEYS
+// SRC_KEYS has half the bytes in flight per round that the tuples have: two rounds of loads in
+// flight measured 2 % faster than one at the north star (1.96 against 2.00 ms, DESIGN "Key columns")
+#define HWBRJ_SC_PRE_KEYS 2
+#endif
+constexpr int      kScPreKeys = HWBRJ_SC_PRE_KEYS;
 constexpr int      kScE       = HWBRJ_SC_E;                        // elements per thread per round
 constexpr uint32_t kScRound   = kScThreads * kScE;        // elements per workgroup round
 constexpr int      kScK       = HWBRJ_SC_K;                        // flush tasks per thread per round (fixed)
@@ -491,7 +504,7 @@ __device__ __forceinline__ void sc_word_lds0(uint32_t x, const Geometry& g, cons
         }
         return;
     }
-    const uint32_t key  = x;
+    const uint32_t key  = x;  // (SRC_TUPLES, SRC_KEYS)
     const uint32_t code = crc_nib(tab, key);
     if (MODE == MODE_SLICE_BASIC) {
         // the partition is the first filter bit's slice, not a code digit, so the word carries
@@ -508,13 +521,14 @@ __device__ __forceinline__ void sc_word_lds0(uint32_t x, const Geometry& g, cons
 }
 
 template <int SRC>
-struct ScRaw {  // one round's raw loads of this thread (tuples: keys only; codes: 4 per uint4)
-    uint32_t k[SRC == SRC_TUPLES ? kScE : 1];
-    uint4    v[SRC == SRC_TUPLES ? 1 : kScE / 4];
-    uint32_t jb[SRC == SRC_TUPLES ? kScE : 1];  // MODE_BASIC_POS: which bit of the key
+struct ScRaw {  // one round's raw loads of this thread (tuples, key columns: keys only; codes: 4 per uint4)
+    uint32_t k[SRC != SRC_CODES ? kScE : 1];
+    uint4    v[SRC != SRC_CODES ? 1 : kScE / 4];
+    uint32_t jb[SRC != SRC_CODES ? kScE : 1];  // MODE_BASIC_POS: which bit of the key
     // the payloads of a 16-byte tuple-pair load, unused but held until the keys are consumed: a
     // load's destination registers must not be reused while it is in flight, so a dead payload
     // register taken for a temporary costs an s_waitcnt vmcnt(0) right after the loads are issued
+    // (a key column's loads have no dead dwords: none held)
     uint32_t y[SRC == SRC_TUPLES && HWBRJ_SC_KEEPY ? kScE : 1];
 };
 
@@ -525,6 +539,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ uint32_t crc_tab[128];
     constexpr int NL = SRC == SRC_TUPLES ? kScE / 2 : kScE / 4;  // uint4 loads per thread per round
+    constexpr int PRE = SRC == SRC_KEYS ? kScPreKeys : kScPre;   // rounds of loads in flight
     const uint32_t F     = 1u << P.g.log2F;
     uint32_t*      stage = lds;                  // F * 32, then 64 per-lane dummy slots
     uint32_t*      fill  = stage + F * 32 + 64;  // F + 1 (entry F: invalid elements)
@@ -576,8 +591,9 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
     const uint64_t vn  = MODE == MODE_BASIC_POS && P.vn ? P.vn : 1;  // (P.vn = 0: no elements)
     const uint32_t jb0 = MODE == MODE_BASIC_POS ? (uint32_t) (e0 / vn) : 0u;
     const uint64_t vb  = (uint64_t) (jb0 + 1) * vn;
-    // Loads of the round at `base`: a full round of tuples takes the lane offset in voffset and the
-    // round offset in soffset (no per-element VALU); a partial round checks every index.
+    // Loads of the round at `base`: a full round of tuples (two per 16-byte load) or of a key column
+    // (four per load) takes the lane offset in voffset and the round offset in soffset (no
+    // per-element VALU); a partial round checks every index.
     auto load_round = [&](uint32_t base, ScRaw<SRC>& R) {
         if (MODE == MODE_BASIC_POS) {
 #pragma unroll
@@ -587,7 +603,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
                 uint32_t       jj = jb0;
                 for (uint64_t b = vb; ev >= b; b += vn) jj++;  // (ev < k vn: at most k steps)
                 const uint64_t t = ev - (uint64_t) jj * vn;
-                R.k[j]  = len ? ((const uint32_t*) P.src)[2 * t] : 0u;  // (len = 0: R may be empty)
+                R.k[j]  = len ? ((const uint32_t*) P.src)[(SRC == SRC_KEYS ? 1 : 2) * t] : 0u;  // (len = 0: R may be empty)
                 R.jb[j] = jj;
             }
         } else if (SRC == SRC_TUPLES && base + kScRound <= len) {  // two tuples per 16-byte load
@@ -608,6 +624,21 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
                 R.k[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, i < len ? i * EB : kOob, 0, 0);
                 if (HWBRJ_SC_KEEPY) R.y[j] = 0;
             }
+        } else if (SRC == SRC_KEYS && base + kScRound <= len) {  // four keys per 16-byte load
+#pragma unroll
+            for (int h = 0; h < kScE / 4; h++) {
+                const v4u x = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 4 * tid * EB, (base + h * 4 * kScThreads) * EB, HWBRJ_SC_LAUX);
+                R.k[4 * h]     = x.x;
+                R.k[4 * h + 1] = x.y;
+                R.k[4 * h + 2] = x.z;
+                R.k[4 * h + 3] = x.w;
+            }
+        } else if (SRC == SRC_KEYS) {
+#pragma unroll
+            for (int j = 0; j < kScE; j++) {
+                const uint32_t i = base + (j >> 2) * 4 * kScThreads + 4 * tid + (j & 3);
+                R.k[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, i < len ? i * EB : kOob, 0, 0);
+            }
         } else {
 #pragma unroll
             for (int h = 0; h < NL; h++) {
@@ -622,6 +653,9 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         if (SRC == SRC_TUPLES) {
             x   = R.k[j];
             idx = MODE == MODE_BASIC_POS ? base + j * kScThreads + tid : base + (j >> 1) * 2 * kScThreads + 2 * tid + (j & 1);
+        } else if (SRC == SRC_KEYS) {  // (the index shape of SRC_CODES)
+            x   = R.k[j];
+            idx = MODE == MODE_BASIC_POS ? base + j * kScThreads + tid : base + (j >> 2) * 4 * kScThreads + 4 * tid + (j & 3);
         } else {
             const int h = j >> 2, t = j & 3;
             x   = t == 0 ? R.v[h].x : t == 1 ? R.v[h].y : t == 2 ? R.v[h].z : R.v[h].w;
@@ -648,7 +682,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
 
     ScRaw<SRC> RA, RB;
     load_round(0, RA);
-    if (kScPre == 2) load_round(kScRound, RB);
+    if (PRE == 2) load_round(kScRound, RB);
     // Overflow words of the previous round (rank >= 32 in their partition's stage), written after
     // the flush copy-out freed the stage line. Usual form (no partition of that round reached 64):
     // stage index q * 32 + slot (the word goes to index - 32), or kNoPend. Skew form (pskew): the
@@ -716,7 +750,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         const bool full = base + kScRound <= len;  // uniform
         // ---- A: hash (consumes R), refill R, copy out the last plan, rank
         hash(base, R);
-        load_round(base + kScPre * kScRound, R);
+        load_round(base + PRE * kScRound, R);
         uint32_t slot[kScE];  // ranks issued first: their returns overlap the copy-out
 #pragma unroll
         for (int j = 0; j < kScE; j++) slot[j] = atomicAdd(&fill[q[j]], 1u);
@@ -778,7 +812,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         par ^= 1u;
     };
     uint32_t base = 0;
-    if (kScPre == 2) {
+    if (PRE == 2) {
         for (; base + kScRound < len; base += 2 * kScRound) {
             round(base, RA);
             round(base + kScRound, RB);
@@ -3141,11 +3175,12 @@ __global__ void k_export(const uint32_t* slices, Geometry g, uint32_t* out, uint
 // src/bloom_filter.c:73-89). Here every bit position becomes an element (k_bitpos), the SWWC
 // scatter partitions the positions by their low log2F bits (the slice they belong to, SRC_CODES),
 // and one workgroup per partition ORs its positions into the slice in LDS (k_slice_fill).
-__global__ void k_bitpos(const uint2* __restrict__ R, uint64_t n, Geometry g, uint32_t* __restrict__ out) {
+template <class T>  // (uint2 tuples or uint32_t keys: k_build_global)
+__global__ void k_bitpos(const T* __restrict__ R, uint64_t n, Geometry g, uint32_t* __restrict__ out) {
     const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
     const uint32_t msz    = (uint32_t) g.m;
     for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint32_t key = R[i].x;
+        const uint32_t key = elem_key(R[i]);
         uint32_t       h = mod_m(crapwow(kSeed, key), msz), y = mod_m(key + kSeed, msz);
         for (uint32_t j = 0; j < g.k; j++) {  // element j * n + i: coalesced per bit
             out[(uint64_t) j * n + i] = h;
@@ -3198,8 +3233,9 @@ __global__ __launch_bounds__(1024) void k_slice_fill(const uint32_t* __restrict_
     }
 }
 
-void launch_bitpos(const uint2* R, uint64_t n, const Geometry& g, uint32_t* out, hipStream_t st) {
-    k_bitpos<<<4096, 256, 0, st>>>(R, n, g, out);
+void launch_bitpos(const void* R, int src, uint64_t n, const Geometry& g, uint32_t* out, hipStream_t st) {
+    if (src == SRC_KEYS) k_bitpos<uint32_t><<<4096, 256, 0, st>>>((const uint32_t*) R, n, g, out);
+    else k_bitpos<uint2><<<4096, 256, 0, st>>>((const uint2*) R, n, g, out);
 }
 
 void launch_slice_fill(const uint32_t* pool, const uint32_t* list, const uint32_t* list_start,
@@ -5277,14 +5313,17 @@ void launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_pl
     k_gen<<<4096, 256, 0, st>>>(out, offset, count, d_plan, perm);
 }
 
-void launch_build_global(const uint2* R, uint64_t n, const Geometry& g, const CrcTables* tabs,
+void launch_build_global(const void* R, int src, uint64_t n, const Geometry& g, const CrcTables* tabs,
                          uint32_t* bm, hipStream_t st) {
-    k_build_global<<<4096, 256, 0, st>>>(R, n, g, tabs, bm);
+    if (src == SRC_KEYS) k_build_global<uint32_t><<<4096, 256, 0, st>>>((const uint32_t*) R, n, g, tabs, bm);
+    else k_build_global<uint2><<<4096, 256, 0, st>>>((const uint2*) R, n, g, tabs, bm);
 }
 
-void launch_probe_global(const uint2* S, uint64_t n, const Geometry& g, const CrcTables* tabs,
+void launch_probe_global(const void* S, int src, uint64_t n, const Geometry& g, const CrcTables* tabs,
                          const uint32_t* bm, uint32_t* out, uint64_t* out_count, hipStream_t st) {
-    k_probe_global<<<2048, 1024, 0, st>>>(S, n, g, tabs, bm, out, out_count);
+    if (src == SRC_KEYS)
+        k_probe_global<uint32_t><<<2048, 1024, 0, st>>>((const uint32_t*) S, n, g, tabs, bm, out, out_count);
+    else k_probe_global<uint2><<<2048, 1024, 0, st>>>((const uint2*) S, n, g, tabs, bm, out, out_count);
 }
 
 size_t scatter_lds_bytes(uint32_t log2F) {
@@ -5366,6 +5405,18 @@ void launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hi
         if (g.mode == MODE_BASIC_BITJ) return scatter_inst<SRC_CODES, MODE_BASIC_BITJ, FMT_CODE>(p, side, grid, st);
         if (g.mode == MODE_CODE_OF_KEY) return scatter_inst<SRC_CODES, MODE_CODE_OF_KEY, FMT_CODE>(p, side, grid, st);
         return scatter_inst<SRC_CODES, MODE_GLOBAL, FMT_CODE>(p, side, grid, st);
+    }
+    if (src == SRC_KEYS) {  // a key column: the modes and words of the tuples below
+        switch (g.mode) {
+            case MODE_SLICE_BLOCK:
+                if (g.format == FMT_PACKED)
+                    return scatter_inst<SRC_KEYS, MODE_SLICE_BLOCK, FMT_PACKED>(p, side, grid, st);
+                return scatter_inst<SRC_KEYS, MODE_SLICE_BLOCK, FMT_CODE>(p, side, grid, st);
+            case MODE_SLICE_BASIC:
+                return scatter_inst<SRC_KEYS, MODE_SLICE_BASIC, FMT_CODE>(p, side, grid, st);
+            case MODE_BASIC_POS: return scatter_inst<SRC_KEYS, MODE_BASIC_POS, FMT_CODE>(p, side, grid, st);
+            default: return scatter_inst<SRC_KEYS, MODE_NOBLOOM, FMT_CODE>(p, side, grid, st);
+        }
     }
     switch (g.mode) {
         case MODE_SLICE_BLOCK:
@@ -5545,6 +5596,7 @@ const char* kernel_build_knobs() {
         num("HWBRJ_SC_E", HWBRJ_SC_E, 8);
         num("HWBRJ_SC_K", HWBRJ_SC_K, 2);
         num("HWBRJ_SC_PRE", HWBRJ_SC_PRE, 1);
+        num("HWBRJ_SC_PRE_KEYS", HWBRJ_SC_PRE_KEYS, 2);
         num("HWBRJ_SC_KEEPY", HWBRJ_SC_KEEPY, 1);
         num("HWBRJ_SC_LAUX", HWBRJ_SC_LAUX, 2);
         num("HWBRJ_SC_SAUX", HWBRJ_SC_SAUX, 2);

@@ -183,6 +183,28 @@ int hwbrj_join_wait_all(hwbrj_stats_t * stats, int capacity, int * n_joins);
  * timed joins carry no markers. */
 int hwbrj_set_async_timing(int on);
 
+/* The counting join on key columns: d_Rkeys / d_Skeys are device arrays of nR / nS int32 keys, the
+ * layout a columnar caller already has (no {key, payload} interleaving pass; the counting join
+ * never reads payloads, and its scatters read 4 instead of 8 bytes per element). Both sides are
+ * columns. The contract is hwbrj_join_device_algo's / hwbrj_join_device_async's in every clause
+ * not named here: args == NULL runs PRO; every filter configuration; HWBRJ_ALGO_*; the stream;
+ * stats and phase times; the size limits and their codes. The async form is collected by
+ * hwbrj_join_wait / hwbrj_join_wait_all and shares the 64-slot result ring with the tuple joins,
+ * so the two kinds may be enqueued in any mix. After the synchronous form, hwbrj_tables_info /
+ * hwbrj_tables_read answer as after hwbrj_join_device_algo with the same arguments (the partition
+ * words do not depend on the input layout).
+ * Alignment: a non-empty column must start at a 16-byte boundary (the scatter reads four keys per
+ * 16-byte load). A misaligned pointer is refused before any device call: 2 is returned,
+ * hwbrj_last_error() says "align", and *stats is not written. A caller sharding a column must
+ * therefore cut it at multiples of 4 keys.
+ * Not offered on key columns: the materializing, existence, outer and group joins, the host BPRO
+ * family and the partitioned joins take tuples only. */
+int hwbrj_join_keys_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys, uint64_t nS,
+                           const bloom_filter_args_t * args, int algorithm, void * stream,
+                           hwbrj_stats_t * stats);
+int hwbrj_join_keys_device_async(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys,
+                                 uint64_t nS, const bloom_filter_args_t * args, void * stream);
+
 /* The join with result materialization (the reference's JOIN_RESULT_MATERIALIZE output,
  * src/parallel_radix_join_bloom.c:307-312): d_out[i] = {R.payload, S.payload} of every match, in
  * no particular order. One pass of the partitioned pipeline with every tuple's payload carried
