@@ -697,28 +697,32 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     jp.r_kbits         = kbits;
     jp.fmt_cnt         = pp.fmt_cnt;
     jp.timing          = phase_ev_ ? 1u : 0u;  // (back-to-back joins: counts only)
+    JobInputs ji{};  // what the jobs of the payload joins share (xcd8: the launch wrappers)
+    if (mat || semi) {
+        ji.r_codes         = jp.r_codes;
+        ji.r_sweep_start   = jp.r_sweep_start;
+        ji.r_cnt           = jp.r_cnt;
+        ji.r_off           = jp.r_off;
+        ji.slot            = jp.slot;
+        ji.surv            = jp.surv;
+        ji.surv_pos        = survpos.as<uint32_t>();
+        ji.surv_cnt        = jp.surv_cnt;
+        ji.surv_off        = jp.surv_off;
+        ji.item_start      = jp.item_start;
+        ji.list_start      = jp.list_start;
+        ji.surv_seg_stride = jp.surv_seg_stride;
+        ji.nseg            = nseg;
+        ji.CH              = CH;
+        ji.log2NSUB        = g.log2NSUB;
+        ji.hash_shift      = g.hash_shift;
+    }
     if (mat) {
         // (k_join_split, which leaves job_surv zero for the next join, does not run here)
         HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));
         if (outer && outer->keep_s) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
         MatJoinParams mp{};
-        mp.r_codes         = jp.r_codes;
+        mp.j               = ji;
         mp.r_pay           = rpay.as<uint32_t>();
-        mp.r_sweep_start   = jp.r_sweep_start;
-        mp.r_cnt           = jp.r_cnt;
-        mp.r_off           = jp.r_off;
-        mp.slot            = jp.slot;
-        mp.surv            = jp.surv;
-        mp.surv_pos        = survpos.as<uint32_t>();
-        mp.surv_cnt        = jp.surv_cnt;
-        mp.surv_off        = jp.surv_off;
-        mp.item_start      = jp.item_start;
-        mp.list_start      = jp.list_start;
-        mp.surv_seg_stride = jp.surv_seg_stride;
-        mp.nseg            = nseg;
-        mp.CH              = CH;
-        mp.log2NSUB        = g.log2NSUB;
-        mp.hash_shift      = g.hash_shift;
         mp.bm              = (g.sub_shift > 0 && 32 - g.hash_shift <= 17) ? 1u : 0u;
         mp.s_pay           = ppoolS.as<uint32_t>();
         mp.out             = mat->out;
@@ -769,22 +773,7 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));  // (as above)
         if (semi_mark) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
         SemiJoinParams sj{};
-        sj.r_codes         = jp.r_codes;
-        sj.r_sweep_start   = jp.r_sweep_start;
-        sj.r_cnt           = jp.r_cnt;
-        sj.r_off           = jp.r_off;
-        sj.slot            = jp.slot;
-        sj.surv            = jp.surv;
-        sj.surv_pos        = survpos.as<uint32_t>();
-        sj.surv_cnt        = jp.surv_cnt;
-        sj.surv_off        = jp.surv_off;
-        sj.item_start      = jp.item_start;
-        sj.list_start      = jp.list_start;
-        sj.surv_seg_stride = jp.surv_seg_stride;
-        sj.nseg            = nseg;
-        sj.CH              = CH;
-        sj.log2NSUB        = g.log2NSUB;
-        sj.hash_shift      = g.hash_shift;
+        sj.j               = ji;
         sj.bm              = semi_bm ? 1u : 0u;
         sj.anti            = semi->anti ? 1u : 0u;
         sj.basic           = g.mode == MODE_SLICE_BASIC ? 1u : 0u;

@@ -143,11 +143,11 @@ struct JoinParams {
                                   // ms_join_probe (synchronous joins; 0: one count add per workgroup)
 };
 
-// The materializing join (k_join_mat): R codes + payloads of the build sweeps, survivors + their
-// chunk positions, {R.payload, S.payload} pairs appended to out (up to cap; count = all pairs).
-struct MatJoinParams {
+// What every (q, sub) job of the payload joins reads (k_join_mat, k_join_semi, k_join_outer,
+// k_join_group): the R codes of the build sweeps and their run descriptors, the survivors with their
+// chunk positions and run descriptors, and the job geometry.
+struct JobInputs {
     const uint32_t* r_codes;
-    const uint32_t* r_pay;          // BuildParams::out_pay
     const uint32_t* r_sweep_start;  // [F + 1]
     const uint32_t* r_cnt;
     const uint32_t* r_off;
@@ -160,8 +160,15 @@ struct MatJoinParams {
     const uint32_t* list_start;
     uint64_t        surv_seg_stride;
     uint32_t        nseg, CH, log2NSUB, hash_shift;
+    uint32_t        xcd8;           // 1: XCD-aware job order (F a multiple of 8; set by the launch_join_* wrappers)
+};
+
+// The materializing join (k_join_mat): R codes + payloads of the build sweeps, survivors + their
+// chunk positions, {R.payload, S.payload} pairs appended to out (up to cap; count = all pairs).
+struct MatJoinParams {
+    JobInputs       j;
+    const uint32_t* r_pay;          // BuildParams::out_pay
     uint32_t        bm;             // 1: job keys v = code >> hash_shift < 2^17 (the bitmap path)
-    uint32_t        xcd8;           // 1: XCD-aware job order (F a multiple of 8; set by launch_join_mat)
     const uint32_t* s_pay;          // S payload pool (ScatterParams::ppool of the S pass)
     uint2*          out;
     uint64_t        cap;
@@ -173,21 +180,8 @@ struct MatJoinParams {
 // to cap; count = all rows). ANTI: the matching survivors' chunk positions marked in `mark` (one
 // bit per S chunk position), for k_semi_emit.
 struct SemiJoinParams {
-    const uint32_t* r_codes;
-    const uint32_t* r_sweep_start;  // [F + 1]
-    const uint32_t* r_cnt;
-    const uint32_t* r_off;
-    uint32_t        slot;
-    const uint32_t* surv;
-    const uint32_t* surv_pos;       // ProbeParams::surv_pos
-    const uint32_t* surv_cnt;
-    const uint32_t* surv_off;
-    const uint32_t* item_start;
-    const uint32_t* list_start;
-    uint64_t        surv_seg_stride;
-    uint32_t        nseg, CH, log2NSUB, hash_shift;
+    JobInputs       j;
     uint32_t        bm;             // 1: job keys v = code >> hash_shift < 2^17 (the bitmap path)
-    uint32_t        xcd8;           // 1: XCD-aware job order (set by launch_join_semi)
     uint32_t        anti;           // 1: mark only (k_semi_emit writes the rows)
     uint32_t        basic;          // 1: the words are bmix(key) (MODE_SLICE_BASIC), else codes
     const uint32_t* s_pay;          // S payload pool

@@ -2827,319 +2827,476 @@ __device__ __forceinline__ void mat_insert1(uint32_t* tk, uint32_t* tp, uint32_t
     tp[h] = pay;
 }
 
-// matches of kMatU survivor keys (v = kEmpty: none)
-__device__ __forceinline__ void mat_count(const uint32_t* tk, const uint32_t (&v)[kMatU], uint32_t (&m)[kMatU]) {
-#pragma unroll
-    for (int k = 0; k < kMatU; k++) {
-        m[k] = 0;
-        if (v[k] != kEmpty)
-            for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                const uint32_t x = tk[h];
-                if (x == kEmpty) break;
-                m[k] += x == v[k] ? 1u : 0u;
-            }
+// The walk of the table that mat_insert1 fills: fn(slot) for every slot that holds key v (the
+// probe sequence of v up to the first free slot; v != kEmpty). Counting, the pair writers, the
+// outer join's R flags and the group join's accumulators all go through it.
+template <class F>
+__device__ __forceinline__ void mat_walk(const uint32_t* tk, uint32_t v, F&& fn) {
+    for (uint32_t h = mat_jslot(v);; h = (h + 1) & (kMatT - 1)) {
+        const uint32_t x = tk[h];
+        if (x == kEmpty) break;
+        if (x == v) fn(h);
     }
+}
+
+// matches of U survivor keys (v = kEmpty: none)
+template <int U>
+__device__ __forceinline__ void mat_count(const uint32_t* tk, const uint32_t (&v)[U], uint32_t (&m)[U]) {
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+        m[k] = 0;
+        if (v[k] != kEmpty) mat_walk(tk, v[k], [&](uint32_t) { m[k]++; });
+    }
+}
+
+// ------------------------------------------------ the job skeleton of the payload joins
+// k_join_mat, k_join_semi, k_join_outer and k_join_group run one workgroup per (q, sub) job over the
+// same inputs (JobInputs). What a job is, how its run descriptors and elements are loaded, the
+// bitmap path's build, and the three forms' control flow (payload_job) are written here once; an
+// operator supplies a policy (PairPolicy below, GroupPolicy) with what is its own ("The
+// job skeleton").
+struct JobCtx {
+    uint32_t q, s;      // partition, sub
+    uint32_t r0, r1;    // q's build sweeps (R run descriptors)
+    uint32_t qi0, qi1;  // q's probe items (survivor run descriptors)
+    uint32_t lq0, npc;  // q's first list position; probe pieces of q per segment (0: no items)
+};
+
+// the small LDS arrays of a job (the kernel declares one __shared__ and passes it by reference)
+struct alignas(16) JobLds {
+    uint64_t           rbase[kMatDesc], sbase[kMatDesc];          // first element of a run
+    uint32_t           wsum[kMatThreads / 64];                    // mat_block_scan (16-byte aligned: read as two b128)
+    uint32_t           rpre[kMatDesc + 1], spre[kMatDesc + 1];    // exclusive prefix of the runs' counts
+    uint32_t           dupf;                                      // bitmap path: duplicate R keys seen
+    unsigned long long obase;                                     // output row of a batch
+    unsigned long long ptot;                                      // k_join_group: pairs of the piece
+};
+
+__device__ __forceinline__ JobCtx job_open(const JobInputs& J) {
+    const uint32_t NSUB = 1u << J.log2NSUB;
+    // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs, so the jobs of partition q
+    // (which read the same R sweeps and S payload lines) all go to XCD q mod 8 and share its L2
+    uint32_t job = blockIdx.x;
+    if (J.xcd8) {
+        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
+        job = ((((l >> J.log2NSUB) << 3) | x) << J.log2NSUB) | (l & (NSUB - 1u));
+    }
+    JobCtx c;
+    c.q   = job >> J.log2NSUB;
+    c.s   = job & (NSUB - 1u);
+    c.r0  = J.r_sweep_start[c.q];
+    c.r1  = J.r_sweep_start[c.q + 1];
+    c.qi0 = J.item_start[c.q];
+    c.qi1 = J.item_start[c.q + 1];
+    c.lq0 = c.npc = 0;
+    return c;
+}
+// what the survivor descriptors need beside that (after the caller's early return)
+__device__ __forceinline__ void job_open_survivors(const JobInputs& J, JobCtx& c) {
+    c.lq0 = J.list_start[c.q];
+    c.npc = (c.qi1 - c.qi0) / J.nseg;
+}
+
+// This thread's run descriptor of a batch of n at d0 (thread t: descriptor d0 + t): its first
+// element into L.rbase / L.sbase, its count returned (0 for t >= n).
+__device__ __forceinline__ uint32_t job_r_desc(const JobInputs& J, const JobCtx& c, JobLds& L, uint32_t rd0, uint32_t nrd) {
+    uint32_t cnt = 0;
+    if (threadIdx.x < nrd) {
+        const uint64_t r = (uint64_t) (rd0 + threadIdx.x) * (1u << J.log2NSUB) + c.s;
+        cnt                = J.r_cnt[r];
+        L.rbase[threadIdx.x] = (uint64_t) (rd0 + threadIdx.x) * J.slot + J.r_off[r];
+    }
+    return cnt;
+}
+__device__ __forceinline__ uint32_t job_s_desc(const JobInputs& J, const JobCtx& c, JobLds& L, uint32_t sd0, uint32_t nsd) {
+    uint32_t cnt = 0;
+    if (threadIdx.x < nsd) {  // the survivor run of item `it` for this sub
+        const uint32_t it = sd0 + threadIdx.x, local = it - c.qi0, seg = local / c.npc, piece = local - seg * c.npc;
+        const uint64_t i  = (uint64_t) it * (1u << J.log2NSUB) + c.s;
+        cnt                = J.surv_cnt[i];
+        L.sbase[threadIdx.x] = (uint64_t) seg * J.surv_seg_stride + (uint64_t) (c.lq0 + piece * J.CH) * 32 + J.surv_off[i];
+    }
+    return cnt;
+}
+// the counts' exclusive prefix into pre[0, n] (contains barriers; the caller's next one publishes pre)
+__device__ __forceinline__ uint32_t job_scan_pre(JobLds& L, uint32_t* pre, uint32_t n, uint32_t cnt) {
+    uint32_t       tot;
+    const uint32_t x = mat_block_scan(cnt, L.wsum, tot);
+    if (threadIdx.x < n) pre[threadIdx.x] = x;
+    if (threadIdx.x == 0) pre[n] = tot;
+    return tot;
+}
+
+// The descriptor loaders: R runs [rd0, rd0 + nrd) into rbase / rpre, survivor runs [sd0, sd0 + nsd)
+// into sbase / spre; they return the batch's elements and own their barriers (the first: the
+// previous descriptors are consumed -- for the survivors also: the table is complete).
+__device__ __forceinline__ uint32_t job_load_r(const JobInputs& J, const JobCtx& c, JobLds& L, uint32_t rd0, uint32_t nrd) {
+    __syncthreads();
+    const uint32_t rtot = job_scan_pre(L, L.rpre, nrd, job_r_desc(J, c, L, rd0, nrd));
+    __syncthreads();
+    return rtot;
+}
+__device__ __forceinline__ uint32_t job_load_s(const JobInputs& J, const JobCtx& c, JobLds& L, uint32_t sd0, uint32_t nsd) {
+    __syncthreads();
+    const uint32_t stot = job_scan_pre(L, L.spre, nsd, job_s_desc(J, c, L, sd0, nsd));
+    __syncthreads();
+    return stot;
+}
+// The single-shot form's fused loader: all of the job's R and survivor descriptors, both loaded
+// before either scan, so the descriptors cost one global round trip. Also clears dupf. The caller's
+// next barrier publishes them.
+__device__ __forceinline__ void job_load_both(const JobInputs& J, const JobCtx& c, JobLds& L, uint32_t& rtot, uint32_t& stot) {
+    const uint32_t nrd = c.r1 - c.r0, nsd = c.qi1 - c.qi0;
+    const uint32_t rcn = job_r_desc(J, c, L, c.r0, nrd), scn = job_s_desc(J, c, L, c.qi0, nsd);
+    rtot = job_scan_pre(L, L.rpre, nrd, rcn);
+    stot = job_scan_pre(L, L.spre, nsd, scn);
+    if (threadIdx.x == 0) L.dupf = 0;
+}
+
+// The element gathers, U per thread (thread t: elements base + t + k * kMatThreads); they return
+// the mask of the lanes that hold an element. One convention for a lane without one: job key
+// kEmpty, address 0, payload 0.
+// R: the codes of elements [base, end) of the loaded descriptors, and their payloads (PAY). The
+// loaded values are not touched here, so the loads stay in flight until job_keys, which turns the
+// codes into job keys in place.
+template <int U, bool PAY>
+__device__ __forceinline__ uint32_t job_gather_r(const JobInputs& J, const uint32_t* r_pay, const JobLds& L, uint32_t nrd,
+                                                 uint32_t base, uint32_t end, uint32_t (&rc)[U], uint32_t (&rp)[U]) {
+    uint32_t valid = 0;
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+        const uint32_t e = base + threadIdx.x + k * kMatThreads;
+        rc[k] = 0;
+        if constexpr (PAY) rp[k] = 0;
+        if (e < end) {
+            const uint32_t d  = mat_find(L.rpre, nrd, e);
+            const uint64_t ra = L.rbase[d] + (e - L.rpre[d]);
+            rc[k] = J.r_codes[ra];
+            if constexpr (PAY) rp[k] = r_pay[ra];
+            valid |= 1u << k;
+        }
+    }
+    return valid;
+}
+// (hash_shift >= 1 in every geometry the engine plans, so a job key is never kEmpty and kEmpty can
+// mark the lanes without a tuple, on the R side as it always did for the survivors)
+template <int U>
+__device__ __forceinline__ void job_keys(const JobInputs& J, uint32_t valid, uint32_t (&rc)[U]) {
+#pragma unroll
+    for (int k = 0; k < U; k++) rc[k] = (valid >> k) & 1u ? rc[k] >> J.hash_shift : kEmpty;
+}
+// Survivors: the addresses and the words >> sh of the batch at e0 of the loaded descriptors'
+// stot elements.
+template <int U>
+__device__ __forceinline__ uint32_t job_gather_s(const JobInputs& J, const JobLds& L, uint32_t nsd, uint32_t stot,
+                                                 uint32_t e0, uint32_t sh, uint64_t (&a)[U], uint32_t (&v)[U]) {
+    uint32_t valid = 0;
+#pragma unroll
+    for (int k = 0; k < U; k++) {
+        const uint32_t e = e0 + threadIdx.x + k * kMatThreads;
+        a[k] = 0;
+        v[k] = kEmpty;
+        if (e < stot) {
+            const uint32_t d = mat_find(L.spre, nsd, e);
+            a[k] = L.sbase[d] + (e - L.spre[d]);
+            v[k] = J.surv[a[k]] >> sh;
+            valid |= 1u << k;
+        }
+    }
+    return valid;
 }
 
 // Bitmap path (unique R keys v < 2^17, the blocked / sectorized join's jobs): every R key sets its
 // bit (ds_or_rtn; a bit already set means duplicate keys, and the job takes the hash table);
-// a prefix popcount per 64-bit word ranks the keys, and the R payloads are stored by rank. A
-// survivor costs a bit test, and a match two more LDS reads: no probe sequences, no CAS.
-__global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_join_mat(MatJoinParams P) {
-    // LDS union: hash table {keys (kEmpty: free) [kMatT], R payloads [kMatT]}, or the bitmap path's
-    // {bitmap [kMatBmWords], rank prefix per 64-bit word (u16) [kMatBmWords / 2], payloads [kMatRCap]}
-    __shared__ __attribute__((aligned(16))) uint32_t smem[kMatBmWords + kMatBmWords / 4 + kMatRCap];
-    static_assert(kMatBmWords + kMatBmWords / 4 + kMatRCap >= 2 * kMatT, "LDS union");
-    uint32_t* tk = smem;
-    uint32_t* tp = smem + kMatT;
-    __shared__ uint32_t dupf;
-    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
-    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
-    __shared__ uint32_t wsum[kMatThreads / 64];
-    __shared__ unsigned long long obase;
-    const int      tid  = threadIdx.x;
-    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
-    // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs, so the jobs of partition q
-    // (which read the same R sweeps and S payload lines) all go to XCD q mod 8 and share its L2
-    uint32_t job = blockIdx.x;
-    if (P.xcd8) {
-        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
-        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
+// a prefix popcount per 64-bit word ranks the keys, and what belongs to an R tuple is stored by
+// rank. A survivor costs a bit test, and a match two more LDS reads: no probe sequences, no CAS.
+// Its LDS: {bitmap [kMatBmWords], rank prefix per 64-bit word (u16) [kMatBmWords / 2], the
+// operator's arrays by rank (bm_rest)}.
+__device__ __forceinline__ uint32_t* bm_rest(uint32_t* smem) { return smem + kMatBmWords + kMatBmWords / 4; }
+__device__ __forceinline__ void bm_clear(uint32_t* smem) {
+    for (uint32_t i = threadIdx.x; i < kMatBmWords; i += kMatThreads) smem[i] = 0;
+}
+__device__ __forceinline__ uint32_t bm_test(const uint32_t* smem, uint32_t v) { return (smem[v >> 5] >> (v & 31u)) & 1u; }
+__device__ __forceinline__ uint32_t bm_rank(const uint32_t* smem, uint32_t v) {
+    const uint64_t w = ((const uint64_t*) smem)[v >> 6];
+    return (uint32_t) ((const uint16_t*) (smem + kMatBmWords))[v >> 6] +
+           (uint32_t) __builtin_popcountll(w & ((1ull << (v & 63u)) - 1ull));
+}
+// The build over this thread's R keys (bitmap and L.dupf cleared, a barrier since): false when two
+// of the job's keys are equal, else the rank prefix is complete. Contains barriers.
+__device__ __forceinline__ bool bm_build(uint32_t* smem, JobLds& L, const uint32_t (&rv)[kMatUB]) {
+    const uint64_t* bm64 = (const uint64_t*) smem;
+    uint16_t*       pfx  = (uint16_t*) (smem + kMatBmWords);
+    const int       tid  = threadIdx.x;
+    uint32_t        dup  = 0;
+#pragma unroll
+    for (int k = 0; k < kMatUB; k++)
+        if (rv[k] != kEmpty) dup |= (atomicOr(&smem[rv[k] >> 5], 1u << (rv[k] & 31u)) >> (rv[k] & 31u)) & 1u;
+    if (dup) L.dupf = 1;
+    __syncthreads();
+    if (L.dupf) return false;  // (uniform)
+    // rank prefix: thread t owns 64-bit words 4t .. 4t + 3
+    uint32_t c4[4], c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        c4[j] = (uint32_t) __builtin_popcountll(bm64[tid * 4 + j]);
+        c += c4[j];
     }
-    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
-    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
-    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
-    if (r0 == r1 || qi0 == qi1) return;  // (uniform) no R or no survivors in q
-    const uint32_t lq0 = P.list_start[q];
-    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment
-    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
-        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
-        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
-        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
-               P.surv_off[(uint64_t) it * NSUB + s];
+    uint32_t ntot;
+    uint32_t run = mat_block_scan(c, L.wsum, ntot);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        pfx[tid * 4 + j] = (uint16_t) run;
+        run += c4[j];
+    }
+    __syncthreads();
+    return true;
+}
+
+// The three forms of a job, for a policy Pol (a struct the kernel builds over its LDS):
+//   kAllR       every R tuple of the job yields a row, so a job without survivors still runs
+//   kStorePay   beside an R key the tables keep its payload (else its ordinal in the piece, and
+//               nothing by rank)
+//   clear<BM>(n)                    the operator's per-piece state for n R tuples (before a barrier)
+//   batch<BM, U>(a, cnt, hit, each) a batch of survivors at addresses a[]: cnt matches in all,
+//               hit(k) those of element k, each(k, fn) calls fn(i) for every R entry i that matches
+//               it (BM: its rank, else its table slot)
+//   end<BM, U>(rv, rp, n, index)    the piece's n R tuples have seen all of the job's survivors;
+//               this thread loaded keys rv[] and payloads rp[], index(k) is their rank / ordinal
+// - single-shot form (the usual job): every descriptor in one batch, R in one piece, the survivors
+//   in one batch; R and S descriptors, then R tuples and survivor codes, are loaded together, so the
+//   job costs four dependent global round trips. On the bitmap path or, with duplicate R keys or
+//   without P.bm, the hash table;
+// - general form: R descriptor batches x R pieces x survivor batches over the hash table.
+template <class Pol>
+__device__ __forceinline__ void payload_job(const MatJoinParams& P, Pol& pol, uint32_t* smem, JobLds& L) {
+    const JobInputs& J   = P.j;
+    const uint32_t   tid = threadIdx.x, hs = J.hash_shift;
+    uint32_t*        tk = smem;           // hash forms: keys (kEmpty: free) [kMatT],
+    uint32_t*        tp = smem + kMatT;   // and what is kept beside them [kMatT]
+    JobCtx           c  = job_open(J);
+    // (uniform) no R in q: nothing to do for any operator. No probe items in q: nothing unless
+    // every R tuple yields a row
+    if (c.r0 == c.r1 || (c.qi0 == c.qi1 && !Pol::kAllR)) return;
+    job_open_survivors(J, c);
+    auto ordinal = [&](int k) { return tid + (uint32_t) k * kMatThreads; };
+    auto clear_table = [&](uint32_t n) {
+        for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+        pol.template clear<false>(n);
     };
-    // ---- single-shot form (the usual job): every descriptor in one batch, R in one piece, the
-    // survivors in one batch; R and S descriptors, then R tuples and survivor codes, are loaded
-    // together, so the job costs four dependent global round trips
-    if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
-        const uint32_t nrd = r1 - r0, nsd = qi1 - qi0;
-        uint32_t       rcn = 0, scn = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (r0 + tid) * NSUB + s;
-            rcn        = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (r0 + tid) * P.slot + P.r_off[r];
-        }
-        if ((uint32_t) tid < nsd) s_desc(qi0 + tid, scn, sbase[tid]);
+    auto insert = [&](const uint32_t (&rv)[kMatU], const uint32_t (&rp)[kMatU]) {
+#pragma unroll
+        for (int k = 0; k < kMatU; k++)
+            if (rv[k] != kEmpty) mat_insert1(tk, tp, rv[k], Pol::kStorePay ? rp[k] : ordinal(k));
+    };
+    auto hash_batch = [&](const uint64_t (&a)[kMatU], const uint32_t (&v)[kMatU]) {
+        uint32_t m[kMatU], cnt = 0;
+        mat_count(tk, v, m);
+#pragma unroll
+        for (int k = 0; k < kMatU; k++) cnt += m[k];
+        pol.template batch<false, kMatU>(
+            a, cnt, [&](int k) { return m[k]; }, [&](int k, auto&& fn) { mat_walk(tk, v[k], fn); });
+    };
+    if (c.r1 - c.r0 <= kMatDesc && c.qi1 - c.qi0 <= kMatDesc) {  // (uniform) ---- single-shot form
+        const uint32_t nrd = c.r1 - c.r0, nsd = c.qi1 - c.qi0;
         uint32_t       rtot, stot;
-        const uint32_t rx = mat_block_scan(rcn, wsum, rtot);
-        const uint32_t sx = mat_block_scan(scn, wsum, stot);
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if ((uint32_t) tid < nsd) spre[tid] = sx;
-        if (tid == 0) {
-            rpre[nrd] = rtot;
-            spre[nsd] = stot;
-            dupf      = 0;
-        }
+        job_load_both(J, c, L, rtot, stot);
+        if (rtot == 0 || (stot == 0 && !Pol::kAllR)) return;  // (uniform) as above, for this sub
         if (P.bm && rtot <= kMatRCap) {  // (uniform) ---- bitmap path
-            uint32_t*       bmw = smem;
-            uint16_t*       pfx = (uint16_t*) (smem + kMatBmWords);
-            uint32_t*       rpy = smem + kMatBmWords + kMatBmWords / 4;
-            const uint64_t* bm64 = (const uint64_t*) smem;
-            for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) bmw[i] = 0;
-            __syncthreads();  // descriptors visible, bitmap cleared
+            bm_clear(smem);
+            pol.template clear<true>(rtot);
+            __syncthreads();  // descriptors visible, bitmap and the operator's state cleared
             uint32_t rv[kMatUB], rp[kMatUB];
+            job_keys(J, job_gather_r<kMatUB, true>(J, P.r_pay, L, nrd, 0, rtot, rv, rp), rv);
+            if (bm_build(smem, L, rv)) {  // (uniform)
+                if constexpr (Pol::kStorePay) {
 #pragma unroll
-            for (int k = 0; k < kMatUB; k++) {
-                const uint32_t e = tid + k * kMatThreads;
-                rv[k] = kEmpty;
-                if (e < rtot) {
-                    const uint32_t d  = mat_find(rpre, nrd, e);
-                    const uint64_t ra = rbase[d] + (e - rpre[d]);
-                    rv[k] = P.r_codes[ra] >> hs;
-                    rp[k] = P.r_pay[ra];
+                    for (int k = 0; k < kMatUB; k++)
+                        if (rv[k] != kEmpty) bm_rest(smem)[bm_rank(smem, rv[k])] = rp[k];
+                    __syncthreads();  // payloads by rank complete
                 }
-            }
-            uint32_t dup = 0;
-#pragma unroll
-            for (int k = 0; k < kMatUB; k++)
-                if (rv[k] != kEmpty) dup |= (atomicOr(&bmw[rv[k] >> 5], 1u << (rv[k] & 31u)) >> (rv[k] & 31u)) & 1u;
-            if (dup) dupf = 1;
-            __syncthreads();
-            if (!dupf) {  // (uniform)
-                // rank prefix: thread t owns 64-bit words 4t .. 4t + 3
-                uint32_t c4[4], c = 0;
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    c4[j] = (uint32_t) __builtin_popcountll(bm64[tid * 4 + j]);
-                    c += c4[j];
-                }
-                uint32_t       ntot;
-                uint32_t       run = mat_block_scan(c, wsum, ntot);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    pfx[tid * 4 + j] = (uint16_t) run;
-                    run += c4[j];
-                }
-                __syncthreads();
-                auto rank = [&](uint32_t v) {
-                    const uint64_t w = bm64[v >> 6];
-                    return (uint32_t) pfx[v >> 6] + (uint32_t) __builtin_popcountll(w & ((1ull << (v & 63u)) - 1ull));
-                };
-#pragma unroll
-                for (int k = 0; k < kMatUB; k++)
-                    if (rv[k] != kEmpty) rpy[rank(rv[k])] = rp[k];
-                __syncthreads();  // payloads by rank complete
                 for (uint32_t e0 = 0; e0 < stot; e0 += kMatRCap) {  // survivors, batch by batch
                     uint64_t a[kMatUB];
                     uint32_t v[kMatUB], hit = 0;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) {
-                        const uint32_t e = e0 + tid + k * kMatThreads;
-                        v[k] = kEmpty;
-                        a[k] = 0;
-                        if (e < stot) {
-                            const uint32_t d = mat_find(spre, nsd, e);
-                            a[k] = sbase[d] + (e - spre[d]);
-                            v[k] = P.surv[a[k]] >> hs;
-                        }
-                    }
+                    job_gather_s<kMatUB>(J, L, nsd, stot, e0, hs, a, v);
 #pragma unroll
                     for (int k = 0; k < kMatUB; k++)
-                        if (v[k] != kEmpty) hit |= ((bmw[v[k] >> 5] >> (v[k] & 31u)) & 1u) << k;
-                    uint32_t pos[kMatUB], sp[kMatUB];
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) pos[k] = (hit >> k) & 1u ? P.surv_pos[a[k]] : 0u;
-                    uint32_t       tot;
-                    const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(hit), wsum, tot);
-                    if (tot == 0) continue;  // (uniform)
-                    if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) sp[k] = (hit >> k) & 1u ? P.s_pay[pos[k]] : 0u;
-                    __syncthreads();
-                    uint64_t o = obase + off;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) {
-                        if (!((hit >> k) & 1u)) continue;
-                        if (o < P.cap) P.out[o] = make_uint2(rpy[rank(v[k])], sp[k]);
-                        o++;
-                    }
+                        if (v[k] != kEmpty) hit |= bm_test(smem, v[k]) << k;
+                    pol.template batch<true, kMatUB>(
+                        a, (uint32_t) __builtin_popcount(hit), [&](int k) { return (hit >> k) & 1u; },
+                        [&](int k, auto&& fn) { fn(bm_rank(smem, v[k])); });
                 }
+                pol.template end<true, kMatUB>(rv, rp, rtot, [&](int k) { return bm_rank(smem, rv[k]); });
                 return;
             }
             // duplicate R keys: the hash table (over the same LDS)
         }
-        if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform)
+        if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform) ---- one piece, one batch
             __syncthreads();  // descriptors visible; the bitmap path is done with the LDS
-            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
+            clear_table(rtot);
             __syncthreads();
-            uint32_t rc[kMatU], rp[kMatU], v[kMatU], m[kMatU];
+            uint32_t rv[kMatU], rp[kMatU], v[kMatU];
             uint64_t a[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = tid + k * kMatThreads;
-                if (e < rtot) {
-                    const uint32_t d  = mat_find(rpre, nrd, e);
-                    const uint64_t ra = rbase[d] + (e - rpre[d]);
-                    rc[k] = P.r_codes[ra];
-                    rp[k] = P.r_pay[ra];
-                }
-                v[k] = kEmpty;
-                a[k] = 0;
-                if (e < stot) {
-                    const uint32_t d = mat_find(spre, nsd, e);
-                    a[k] = sbase[d] + (e - spre[d]);
-                    v[k] = P.surv[a[k]] >> hs;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kMatU; k++)
-                if (tid + k * kMatThreads < rtot) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
+            const uint32_t rvalid = job_gather_r<kMatU, true>(J, P.r_pay, L, nrd, 0, rtot, rv, rp);
+            job_gather_s<kMatU>(J, L, nsd, stot, 0, hs, a, v);
+            job_keys(J, rvalid, rv);
+            insert(rv, rp);
             __syncthreads();  // table complete
-            mat_count(tk, v, m);
-            uint32_t cnt = 0;
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) cnt += m[k];
-            uint32_t pos[kMatU], sp[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;  // (in flight over the scan)
-            uint32_t       tot;
-            const uint32_t off = mat_block_scan(cnt, wsum, tot);
-            if (tot == 0) return;  // (uniform)
-            if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
-            __syncthreads();
-            uint64_t o = obase + off;
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                if (!m[k]) continue;
-                for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                    const uint32_t x = tk[h];
-                    if (x == kEmpty) break;
-                    if (x == v[k]) {
-                        if (o < P.cap) P.out[o] = make_uint2(tp[h], sp[k]);
-                        o++;
-                    }
-                }
-            }
+            hash_batch(a, v);
+            pol.template end<false, kMatU>(rv, rp, rtot, ordinal);
             return;
         }
     }
-    // ---- general form: R descriptor batches x R pieces x survivor batches
-    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {  // R run descriptors, batch by batch
-        const uint32_t nrd = min(kMatDesc, r1 - rd0);
-        __syncthreads();  // previous descriptors consumed
-        uint32_t c = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
-            c          = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
-        }
-        uint32_t       rtot;
-        const uint32_t rx = mat_block_scan(c, wsum, rtot);
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if (tid == 0) rpre[nrd] = rtot;
-        __syncthreads();
+    // ---- general form
+    for (uint32_t rd0 = c.r0; rd0 < c.r1; rd0 += kMatDesc) {  // R run descriptors, batch by batch
+        const uint32_t nrd  = min(kMatDesc, c.r1 - rd0);
+        const uint32_t rtot = job_load_r(J, c, L, rd0, nrd);
         for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
             const uint32_t pe = min(rtot, pb + kMatPiece);
-            __syncthreads();  // the previous piece's survivors are done with the table
-            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            uint32_t rc[kMatU], rp[kMatU];  // this thread's R tuples of the piece (loads in flight)
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = pb + tid + k * kMatThreads;
-                rc[k] = kEmpty;
-                if (e < pe) {
-                    const uint32_t d = mat_find(rpre, nrd, e);
-                    const uint64_t a = rbase[d] + (e - rpre[d]);
-                    rc[k] = P.r_codes[a];
-                    rp[k] = P.r_pay[a];
-                }
-            }
-            __syncthreads();  // table cleared
-#pragma unroll
-            for (int k = 0; k < kMatU; k++)
-                if (pb + tid + k * kMatThreads < pe) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
-            for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {  // survivor runs of the job
-                const uint32_t nsd = min(kMatDesc, qi1 - sd0);
-                __syncthreads();  // table complete; previous descriptors consumed
-                uint32_t sc = 0;
-                if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
-                uint32_t       stot;
-                const uint32_t sx = mat_block_scan(sc, wsum, stot);
-                if ((uint32_t) tid < nsd) spre[tid] = sx;
-                if (tid == 0) spre[nsd] = stot;
-                __syncthreads();
+            __syncthreads();  // the previous piece's survivors and its end are done with the table
+            clear_table(pe - pb);
+            uint32_t rv[kMatU], rp[kMatU];  // this thread's R tuples of the piece (loads in flight)
+            const uint32_t rvalid = job_gather_r<kMatU, true>(J, P.r_pay, L, nrd, pb, pe, rv, rp);
+            __syncthreads();  // table and the operator's state cleared
+            job_keys(J, rvalid, rv);
+            insert(rv, rp);
+            for (uint32_t sd0 = c.qi0; sd0 < c.qi1; sd0 += kMatDesc) {  // survivor runs of the job
+                const uint32_t nsd  = min(kMatDesc, c.qi1 - sd0);
+                const uint32_t stot = job_load_s(J, c, L, sd0, nsd);
                 for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {
                     uint64_t a[kMatU];
-                    uint32_t v[kMatU], m[kMatU];
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) {
-                        const uint32_t e = e0 + tid + k * kMatThreads;
-                        a[k] = ~0ull;
-                        v[k] = kEmpty;
-                        if (e < stot) {
-                            const uint32_t d = mat_find(spre, nsd, e);
-                            a[k] = sbase[d] + (e - spre[d]);
-                            v[k] = P.surv[a[k]] >> hs;
-                        }
-                    }
-                    mat_count(tk, v, m);
-                    uint32_t cnt = 0;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) cnt += m[k];
-                    uint32_t       tot;
-                    const uint32_t off = mat_block_scan(cnt, wsum, tot);
-                    if (tot == 0) continue;  // (uniform)
-                    if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
-                    __syncthreads();
-                    uint64_t o = obase + off;
-                    uint32_t pos[kMatU], sp[kMatU];
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) {
-                        if (!m[k]) continue;
-                        for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                            const uint32_t x = tk[h];
-                            if (x == kEmpty) break;
-                            if (x == v[k]) {
-                                if (o < P.cap) P.out[o] = make_uint2(tp[h], sp[k]);
-                                o++;
-                            }
-                        }
-                    }
+                    uint32_t v[kMatU];
+                    job_gather_s<kMatU>(J, L, nsd, stot, e0, hs, a, v);
+                    hash_batch(a, v);
                 }
             }
+            // A piece sees all of the job's survivors before the next piece is loaded, so what it
+            // accumulated per R tuple is final here (end's first barrier completes it; where a job
+            // without probe items skipped the survivor loop, also the table)
+            pol.template end<false, kMatU>(rv, rp, pe - pb, ordinal);
         }
     }
 }
 
+// The pair-writing policy: {R.payload, S.payload} of every match, a workgroup scan and one output
+// atomic per batch; the survivors' chunk positions and payloads are gathered U loads in flight, the
+// positions over the scan (bucket_chaining_join under JOIN_RESULT_MATERIALIZE,
+// src/parallel_radix_join_bloom.c:259-329, :307-312). k_join_mat is <false, false>: no mark, no flag.
+// OUTER (k_join_outer, O given):
+//  - O->keep_s: a survivor with at least one partner sets its chunk position's bit in O->mark (on
+//    every path; a survivor that matches in several pieces sets it again, which changes nothing). No
+//    survivor is judged unmatched here, since that needs all of the job's R: k_outer_emit writes the
+//    unmarked S tuples, so a job without R has nothing to do;
+//  - KR (keep_r at compile time): one matched bit per R tuple in LDS (rflag), by rank on the bitmap
+//    path, by table slot on the hash forms (mat_insert1 gives every R tuple a slot of its own, and
+//    the walk that writes a survivor's pairs visits every copy of its key). The flags are final at
+//    the end of a piece: the unflagged tuples are then written as {R.payload, null} rows, a
+//    workgroup scan and one output atomic per piece. A job without probe items, or without
+//    survivors, therefore still loads its R and writes all of it.
+constexpr uint32_t kOutFlagWords = kMatT / 32;
+static_assert(kMatRCap <= kMatT && kMatT == kMatThreads * kMatUB, "one flag per rank / slot, kMatUB per thread");
+
+template <bool OUTER, bool KR>
+struct PairPolicy {
+    static constexpr bool kAllR = KR, kStorePay = true;
+    const MatJoinParams&   P;
+    const OuterJoinParams* O;      // OUTER
+    uint32_t*              smem;
+    JobLds&                L;
+    uint32_t*              rflag;  // OUTER: [kOutFlagWords], cleared per piece; set under KR
+
+    __device__ __forceinline__ void set_flag(uint32_t i) const { atomicOr(&rflag[i >> 5], 1u << (i & 31u)); }
+
+    template <bool BM>
+    __device__ __forceinline__ void clear(uint32_t) const {
+        if constexpr (OUTER)
+            if (threadIdx.x < kOutFlagWords) rflag[threadIdx.x] = 0;
+    }
+
+    template <bool BM, int U, class Hit, class Each>
+    __device__ __forceinline__ void batch(const uint64_t (&a)[U], uint32_t cnt, Hit&& hit, Each&& each) const {
+        const uint32_t* pay = BM ? bm_rest(smem) : smem + kMatT;
+        uint32_t        pos[U], sp[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) pos[k] = hit(k) ? P.j.surv_pos[a[k]] : 0u;  // (in flight over the scan)
+        uint32_t       tot;
+        const uint32_t off = mat_block_scan(cnt, L.wsum, tot);
+        if (tot == 0) return;  // (uniform)
+        if (threadIdx.x == 0) L.obase = atomicAdd(P.count, (unsigned long long) tot);
+#pragma unroll
+        for (int k = 0; k < U; k++) sp[k] = hit(k) ? P.s_pay[pos[k]] : 0u;
+        if constexpr (OUTER) {
+            if (O->keep_s) {
+#pragma unroll
+                for (int k = 0; k < U; k++)
+                    if (hit(k)) atomicOr(&O->mark[pos[k] >> 5], 1u << (pos[k] & 31u));
+            }
+        }
+        __syncthreads();
+        uint64_t o = L.obase + off;
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            if (!hit(k)) continue;
+            each(k, [&](uint32_t i) {
+                if constexpr (KR) set_flag(i);
+                if (o < P.cap) P.out[o] = make_uint2(pay[i], sp[k]);
+                o++;
+            });
+        }
+    }
+
+    // {R.payload, null} of the unflagged R tuples among entries [0, n) (n <= kMatT): entry i holds a
+    // tuple on the bitmap path (ranks) or where the table's key is not kEmpty (slots). Contains
+    // barriers; the first one completes the flags.
+    template <bool BM, int U, class Index>
+    __device__ __forceinline__ void end(const uint32_t (&)[U], const uint32_t (&)[U], uint32_t nr, Index&&) const {
+        if constexpr (KR) {
+            const uint32_t  n = BM ? nr : kMatT, tid = threadIdx.x;
+            const uint32_t* pay = BM ? bm_rest(smem) : smem + kMatT;
+            __syncthreads();
+            uint32_t sel = 0;
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++) {
+                const uint32_t i = tid + k * kMatThreads;
+                if (i < n && (BM || smem[i] != kEmpty) && !((rflag[i >> 5] >> (i & 31u)) & 1u)) sel |= 1u << k;
+            }
+            uint32_t       tot;
+            const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), L.wsum, tot);
+            if (tot == 0) return;  // (uniform)
+            if (tid == 0) {
+                L.obase = atomicAdd(P.count, (unsigned long long) tot);
+                atomicAdd(O->n_r_only, (unsigned long long) tot);
+            }
+            __syncthreads();
+            uint64_t o = L.obase + off;
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++) {
+                if (!((sel >> k) & 1u)) continue;
+                if (o < P.cap) P.out[o] = make_uint2(pay[tid + k * kMatThreads], O->null_pay);
+                o++;
+            }
+        }
+    }
+};
+
+// LDS union of the pair-writing kernels: hash table {keys [kMatT], R payloads [kMatT]}, or the
+// bitmap path's {bitmap, rank prefix, payloads by rank [kMatRCap]}
+constexpr uint32_t kPairWords = kMatBmWords + kMatBmWords / 4 + kMatRCap;
+static_assert(kPairWords >= 2 * kMatT, "LDS union");
+
+__global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_join_mat(MatJoinParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kPairWords];
+    __shared__ JobLds L;
+    PairPolicy<false, false> pol{P, nullptr, smem, L, nullptr};
+    payload_job(P, pol, smem, L);
+}
+
+// XCD-aware job order (job_open) needs F a multiple of 8
+static uint32_t job_xcd8(uint32_t jobs, uint32_t log2NSUB) { return ((jobs >> log2NSUB) % 8 == 0) ? 1u : 0u; }
+
 void launch_join_mat(const MatJoinParams& p0, uint32_t jobs, hipStream_t st) {
     MatJoinParams p = p0;
-    p.xcd8          = ((jobs >> p.log2NSUB) % 8 == 0) ? 1u : 0u;
+    p.j.xcd8        = job_xcd8(jobs, p.j.log2NSUB);
     k_join_mat<<<jobs, kMatThreads, 0, st>>>(p);
 }
 
@@ -3897,96 +4054,45 @@ __global__ __launch_bounds__(kMatThreads) void k_join_semi(SemiJoinParams P) {
     __shared__ uint32_t tk[kMatT];
     static_assert(kMatT == kMatBmWords, "one LDS array for the bitmap and the hash set");
     __shared__ uint32_t inv[128];
-    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
-    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
-    __shared__ uint32_t wsum[kMatThreads / 64];
-    __shared__ unsigned long long obase;
-    const int      tid  = threadIdx.x;
-    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
-    uint32_t job = blockIdx.x;
-    if (P.xcd8) {  // (k_join_mat's XCD-aware job order)
-        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
-        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
-    }
-    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
-    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
-    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
+    __shared__ JobLds   L;
+    const JobInputs& J   = P.j;
+    const uint32_t   tid = threadIdx.x, hs = J.hash_shift;
+    JobCtx           c   = job_open(J);
     // (uniform) no survivors, or no R: nothing to write (SEMI) and nothing to mark (ANTI; the job's
     // survivors stay unmarked, so k_semi_emit writes all of them)
-    if (r0 == r1 || qi0 == qi1) return;
+    if (c.r0 == c.r1 || c.qi0 == c.qi1) return;
     load_tab(inv, &P.tabs->inv[0][0]);
-    const uint32_t lq0 = P.list_start[q];
-    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment
-    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
-        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
-        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
-        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
-               P.surv_off[(uint64_t) it * NSUB + s];
-    };
-    // R run descriptors [rd0, rd0 + nrd) into rbase / rpre; returns their tuples
-    auto r_batch = [&](uint32_t rd0, uint32_t nrd) {
-        __syncthreads();  // previous descriptors consumed
-        uint32_t c = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
-            c          = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
-        }
-        uint32_t       rtot;
-        const uint32_t rx = mat_block_scan(c, wsum, rtot);
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if (tid == 0) rpre[nrd] = rtot;
-        __syncthreads();
-        return rtot;
-    };
+    job_open_survivors(J, c);
     // the job's survivors, kMatPiece at a time: fn(address, word, valid mask) of this thread's kMatU
     auto for_surv = [&](auto&& fn) {
-        for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {
-            const uint32_t nsd = min(kMatDesc, qi1 - sd0);
-            __syncthreads();  // table complete; previous descriptors consumed
-            uint32_t sc = 0;
-            if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
-            uint32_t       stot;
-            const uint32_t sx = mat_block_scan(sc, wsum, stot);
-            if ((uint32_t) tid < nsd) spre[tid] = sx;
-            if (tid == 0) spre[nsd] = stot;
-            __syncthreads();
+        for (uint32_t sd0 = c.qi0; sd0 < c.qi1; sd0 += kMatDesc) {
+            const uint32_t nsd  = min(kMatDesc, c.qi1 - sd0);
+            const uint32_t stot = job_load_s(J, c, L, sd0, nsd);
             for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {
-                uint64_t a[kMatU];
-                uint32_t c[kMatU], valid = 0;
-#pragma unroll
-                for (int k = 0; k < kMatU; k++) {
-                    const uint32_t e = e0 + tid + k * kMatThreads;
-                    a[k] = 0;
-                    c[k] = 0;
-                    if (e < stot) {
-                        const uint32_t d = mat_find(spre, nsd, e);
-                        a[k] = sbase[d] + (e - spre[d]);
-                        c[k] = P.surv[a[k]];
-                        valid |= 1u << k;
-                    }
-                }
-                fn(a, c, valid);
+                uint64_t       a[kMatU];
+                uint32_t       w[kMatU];
+                const uint32_t valid = job_gather_s<kMatU>(J, L, nsd, stot, e0, 0u, a, w);
+                fn(a, w, valid);
             }
         }
     };
     // rows of the survivors in `sel`: one output atomic per batch (contains barriers)
-    auto emit = [&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t sel) {
+    auto emit = [&](const uint64_t (&a)[kMatU], const uint32_t (&w)[kMatU], uint32_t sel) {
         uint32_t pos[kMatU], sp[kMatU];
 #pragma unroll
-        for (int k = 0; k < kMatU; k++) pos[k] = (sel >> k) & 1u ? P.surv_pos[a[k]] : 0u;  // (in flight over the scan)
+        for (int k = 0; k < kMatU; k++) pos[k] = (sel >> k) & 1u ? J.surv_pos[a[k]] : 0u;  // (in flight over the scan)
         uint32_t       tot;
-        const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), wsum, tot);
+        const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), L.wsum, tot);
         if (tot == 0) return;  // (uniform)
-        if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
+        if (tid == 0) L.obase = atomicAdd(P.count, (unsigned long long) tot);
 #pragma unroll
         for (int k = 0; k < kMatU; k++) sp[k] = (sel >> k) & 1u ? P.s_pay[pos[k]] : 0u;
         __syncthreads();
-        uint64_t o = obase + off;
+        uint64_t o = L.obase + off;
 #pragma unroll
         for (int k = 0; k < kMatU; k++) {
             if (!((sel >> k) & 1u)) continue;
-            const uint32_t key = P.basic ? bunmix(c[k]) : code_key(inv, c[k]);
+            const uint32_t key = P.basic ? bunmix(w[k]) : code_key(inv, w[k]);
             if (o < P.cap) P.out[o] = make_uint2(key, sp[k]);
             o++;
         }
@@ -3995,74 +4101,56 @@ __global__ __launch_bounds__(kMatThreads) void k_join_semi(SemiJoinParams P) {
 #pragma unroll
         for (int k = 0; k < kMatU; k++)
             if ((sel >> k) & 1u) {
-                const uint32_t pos = P.surv_pos[a[k]];
+                const uint32_t pos = J.surv_pos[a[k]];
                 atomicOr(&P.mark[pos >> 5], 1u << (pos & 31u));
             }
     };
     if (P.bm) {  // (uniform) ---- bitmap path
-        for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) tk[i] = 0;
-        for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {
-            const uint32_t nrd  = min(kMatDesc, r1 - rd0);
-            const uint32_t rtot = r_batch(rd0, nrd);  // (its barriers: bitmap cleared)
+        bm_clear(tk);
+        for (uint32_t rd0 = c.r0; rd0 < c.r1; rd0 += kMatDesc) {
+            const uint32_t nrd  = min(kMatDesc, c.r1 - rd0);
+            const uint32_t rtot = job_load_r(J, c, L, rd0, nrd);  // (its barriers: bitmap cleared)
             for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
-                uint32_t rc[kMatU];
-#pragma unroll
-                for (int k = 0; k < kMatU; k++) {
-                    const uint32_t e = pb + tid + k * kMatThreads;
-                    rc[k] = 0;
-                    if (e < rtot) {
-                        const uint32_t d = mat_find(rpre, nrd, e);
-                        rc[k] = P.r_codes[rbase[d] + (e - rpre[d])];
-                    }
-                }
+                uint32_t rv[kMatU], none[kMatU];
+                job_keys(J, job_gather_r<kMatU, false>(J, nullptr, L, nrd, pb, rtot, rv, none), rv);
 #pragma unroll
                 for (int k = 0; k < kMatU; k++)
-                    if (pb + tid + k * kMatThreads < rtot) atomicOr(&tk[(rc[k] >> hs) >> 5], 1u << ((rc[k] >> hs) & 31u));
+                    if (rv[k] != kEmpty) atomicOr(&tk[rv[k] >> 5], 1u << (rv[k] & 31u));
             }
         }
-        for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t valid) {
+        for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&w)[kMatU], uint32_t valid) {
             uint32_t hit = 0;
 #pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t v = c[k] >> hs;
-                hit |= ((tk[v >> 5] >> (v & 31u)) & 1u) << k;
-            }
+            for (int k = 0; k < kMatU; k++) hit |= bm_test(tk, (valid >> k) & 1u ? w[k] >> hs : 0u) << k;
             hit &= valid;
             if (P.anti) mark(a, hit);
-            else emit(a, c, hit);
+            else emit(a, w, hit);
         });
         return;
     }
     // ---- hash-set path: R descriptor batches x R pieces x survivor batches
     bool direct = false;  // the job's only piece wrote its rows itself (SEMI)
-    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {
-        const uint32_t nrd  = min(kMatDesc, r1 - rd0);
-        const uint32_t rtot = r_batch(rd0, nrd);
-        const bool     only = r1 - r0 <= kMatDesc && rtot <= kMatPiece;  // (uniform)
+    for (uint32_t rd0 = c.r0; rd0 < c.r1; rd0 += kMatDesc) {
+        const uint32_t nrd  = min(kMatDesc, c.r1 - rd0);
+        const uint32_t rtot = job_load_r(J, c, L, rd0, nrd);
+        const bool     only = c.r1 - c.r0 <= kMatDesc && rtot <= kMatPiece;  // (uniform)
         for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
             const uint32_t pe = min(rtot, pb + kMatPiece);
             __syncthreads();  // the previous piece's survivors are done with the set
             for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            uint32_t rc[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = pb + tid + k * kMatThreads;
-                rc[k] = 0;
-                if (e < pe) {
-                    const uint32_t d = mat_find(rpre, nrd, e);
-                    rc[k] = P.r_codes[rbase[d] + (e - rpre[d])];
-                }
-            }
+            uint32_t       rv[kMatU], none[kMatU];  // (the piece's codes: loads in flight)
+            const uint32_t rvalid = job_gather_r<kMatU, false>(J, nullptr, L, nrd, pb, pe, rv, none);
             __syncthreads();  // set cleared
+            job_keys(J, rvalid, rv);
 #pragma unroll
             for (int k = 0; k < kMatU; k++)
-                if (pb + tid + k * kMatThreads < pe) semi_insert(tk, rc[k] >> hs);
-            for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t valid) {
+                if (rv[k] != kEmpty) semi_insert(tk, rv[k]);
+            for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&w)[kMatU], uint32_t valid) {
                 uint32_t hit = 0;
 #pragma unroll
                 for (int k = 0; k < kMatU; k++)
-                    if ((valid >> k) & 1u) hit |= semi_find(tk, c[k] >> hs) << k;
-                if (only && !P.anti) emit(a, c, hit);
+                    if ((valid >> k) & 1u) hit |= semi_find(tk, w[k] >> hs) << k;
+                if (only && !P.anti) emit(a, w, hit);
                 else mark(a, hit);
             });
             direct = only;
@@ -4071,23 +4159,23 @@ __global__ __launch_bounds__(kMatThreads) void k_join_semi(SemiJoinParams P) {
     if (P.anti || direct) return;  // (uniform)
     // SEMI over several pieces: every piece has been seen, the marked survivors are the rows
     __threadfence();
-    for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&c)[kMatU], uint32_t valid) {
+    for_surv([&](const uint64_t (&a)[kMatU], const uint32_t (&w)[kMatU], uint32_t valid) {
         uint32_t hit = 0;
 #pragma unroll
         for (int k = 0; k < kMatU; k++)
             if ((valid >> k) & 1u) {
-                const uint32_t pos = P.surv_pos[a[k]];
+                const uint32_t pos = J.surv_pos[a[k]];
                 // (the marks were set by atomics at the L2: read there, past this CU's vector cache)
-                const uint32_t w = __hip_atomic_load(&P.mark[pos >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                hit |= ((w >> (pos & 31u)) & 1u) << k;
+                const uint32_t mw = __hip_atomic_load(&P.mark[pos >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                hit |= ((mw >> (pos & 31u)) & 1u) << k;
             }
-        emit(a, c, hit);
+        emit(a, w, hit);
     });
 }
 
 void launch_join_semi(const SemiJoinParams& p0, uint32_t jobs, hipStream_t st) {
     SemiJoinParams p = p0;
-    p.xcd8           = ((jobs >> p.log2NSUB) % 8 == 0) ? 1u : 0u;
+    p.j.xcd8         = job_xcd8(jobs, p.j.log2NSUB);
     k_join_semi<<<jobs, kMatThreads, 0, st>>>(p);
 }
 
@@ -4233,369 +4321,23 @@ void launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* tab
 }
 
 // ================================================================= K10o: the outer join
-// k_join_mat's job layout, XCD-aware order and three forms (single-shot bitmap + rank, single-shot
-// hash table, descriptor batches x R pieces x survivor batches), writing the same pairs, and:
-//  - keep_s: a survivor with at least one partner sets its chunk position's bit in `mark` (on every
-//    path; a survivor that matches in several pieces sets it again, which changes nothing). No
-//    survivor is judged unmatched here, since that needs all of the job's R: k_outer_emit writes the
-//    unmarked S tuples, so a job without R has nothing to do;
-//  - keep_r: one matched bit per R tuple in LDS (rflag), by rank on the bitmap path, by table slot
-//    on the hash forms (mat_insert1 gives every R tuple a slot of its own, and the walk that writes
-//    a survivor's pairs visits every copy of its key). A piece sees all of the job's survivors
-//    before the next piece is loaded, so its flags are final at its end: the unflagged tuples are
-//    then written as {R.payload, null} rows, a workgroup scan and one output atomic per piece. A job
-//    without probe items, or without survivors, therefore still loads its R and writes all of it.
+// k_join_mat's job (payload_job) with the pair-writing policy's marks and R flags on (PairPolicy).
 // KR = keep_r at compile time. Without it the kernel is k_join_mat plus the marks and keeps its
-// register budget (64 VGPRs: 8 waves per SIMD, the four workgroups per CU the LDS admits). With it
-// that budget spills 27 VGPRs; 80 VGPRs at 6 waves per SIMD spill 2, outside the survivor loops
-// ("Outer joins").
-constexpr uint32_t kOutFlagWords = kMatT / 32;
-static_assert(kMatRCap <= kMatT && kMatT == kMatThreads * kMatUB, "one flag per rank / slot, kMatUB per thread");
-
+// occupancy (8 waves per SIMD, the four workgroups per CU the LDS admits). With the R flags and the
+// R-only write it needs more live registers than that budget holds, so it runs at 6 waves per SIMD
+// (figures: profiles/join_jobs/resources.txt; DESIGN.md, "Outer joins").
 template <bool KR>
 __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(KR ? 6 : 8))) void k_join_outer(OuterJoinParams O) {
-    const MatJoinParams& P = O.m;
-    // LDS union as in k_join_mat
-    __shared__ __attribute__((aligned(16))) uint32_t smem[kMatBmWords + kMatBmWords / 4 + kMatRCap];
-    uint32_t* tk = smem;
-    uint32_t* tp = smem + kMatT;
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kPairWords];
     __shared__ uint32_t rflag[kOutFlagWords];
-    __shared__ uint32_t dupf;
-    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
-    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
-    __shared__ uint32_t wsum[kMatThreads / 64];
-    __shared__ unsigned long long obase;
-    const int      tid  = threadIdx.x;
-    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
-    uint32_t job = blockIdx.x;
-    if (P.xcd8) {  // (k_join_mat's XCD-aware job order)
-        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
-        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
-    }
-    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
-    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
-    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
-    // (uniform) no R in q: no pair, no R-only row, and q's survivors stay unmarked. No probe items
-    // in q: nothing unless R is preserved (then every R tuple of the job is an R-only row)
-    if (r0 == r1 || (qi0 == qi1 && !KR)) return;
-    const uint32_t lq0 = P.list_start[q];
-    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment (0: s_desc is not called)
-    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
-        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
-        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
-        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
-               P.surv_off[(uint64_t) it * NSUB + s];
-    };
-    auto set_mark = [&](uint32_t pos) { atomicOr(&O.mark[pos >> 5], 1u << (pos & 31u)); };
-    auto set_flag = [&](uint32_t i) { atomicOr(&rflag[i >> 5], 1u << (i & 31u)); };
-    // {R.payload, null} of the unflagged R tuples among entries [0, n) (n <= kMatT): entry i holds a
-    // tuple when keys is nullptr (ranks) or keys[i] != kEmpty (slots), pay[i] is its payload.
-    // Contains barriers; the first one completes the flags.
-    auto r_only = [&](uint32_t n, const uint32_t* keys, const uint32_t* pay) {
-        __syncthreads();
-        uint32_t sel = 0;
-#pragma unroll
-        for (int k = 0; k < kMatUB; k++) {
-            const uint32_t i = tid + k * kMatThreads;
-            if (i < n && (!keys || keys[i] != kEmpty) && !((rflag[i >> 5] >> (i & 31u)) & 1u)) sel |= 1u << k;
-        }
-        uint32_t       tot;
-        const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(sel), wsum, tot);
-        if (tot == 0) return;  // (uniform)
-        if (tid == 0) {
-            obase = atomicAdd(P.count, (unsigned long long) tot);
-            atomicAdd(O.n_r_only, (unsigned long long) tot);
-        }
-        __syncthreads();
-        uint64_t o = obase + off;
-#pragma unroll
-        for (int k = 0; k < kMatUB; k++) {
-            if (!((sel >> k) & 1u)) continue;
-            if (o < P.cap) P.out[o] = make_uint2(pay[tid + k * kMatThreads], O.null_pay);
-            o++;
-        }
-    };
-    // ---- single-shot form
-    if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
-        const uint32_t nrd = r1 - r0, nsd = qi1 - qi0;
-        uint32_t       rcn = 0, scn = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (r0 + tid) * NSUB + s;
-            rcn        = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (r0 + tid) * P.slot + P.r_off[r];
-        }
-        if ((uint32_t) tid < nsd) s_desc(qi0 + tid, scn, sbase[tid]);
-        uint32_t       rtot, stot;
-        const uint32_t rx = mat_block_scan(rcn, wsum, rtot);
-        const uint32_t sx = mat_block_scan(scn, wsum, stot);
-        if (rtot == 0 || (stot == 0 && !KR)) return;  // (uniform) as above, for this sub
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if ((uint32_t) tid < nsd) spre[tid] = sx;
-        if (tid == 0) {
-            rpre[nrd] = rtot;
-            spre[nsd] = stot;
-            dupf      = 0;
-        }
-        if ((uint32_t) tid < kOutFlagWords) rflag[tid] = 0;
-        if (P.bm && rtot <= kMatRCap) {  // (uniform) ---- bitmap path
-            uint32_t*       bmw = smem;
-            uint16_t*       pfx = (uint16_t*) (smem + kMatBmWords);
-            uint32_t*       rpy = smem + kMatBmWords + kMatBmWords / 4;
-            const uint64_t* bm64 = (const uint64_t*) smem;
-            for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) bmw[i] = 0;
-            __syncthreads();  // descriptors visible, bitmap and flags cleared
-            uint32_t rv[kMatUB], rp[kMatUB];
-#pragma unroll
-            for (int k = 0; k < kMatUB; k++) {
-                const uint32_t e = tid + k * kMatThreads;
-                rv[k] = kEmpty;
-                if (e < rtot) {
-                    const uint32_t d  = mat_find(rpre, nrd, e);
-                    const uint64_t ra = rbase[d] + (e - rpre[d]);
-                    rv[k] = P.r_codes[ra] >> hs;
-                    rp[k] = P.r_pay[ra];
-                }
-            }
-            uint32_t dup = 0;
-#pragma unroll
-            for (int k = 0; k < kMatUB; k++)
-                if (rv[k] != kEmpty) dup |= (atomicOr(&bmw[rv[k] >> 5], 1u << (rv[k] & 31u)) >> (rv[k] & 31u)) & 1u;
-            if (dup) dupf = 1;
-            __syncthreads();
-            if (!dupf) {  // (uniform)
-                uint32_t c4[4], c = 0;  // rank prefix: thread t owns 64-bit words 4t .. 4t + 3
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    c4[j] = (uint32_t) __builtin_popcountll(bm64[tid * 4 + j]);
-                    c += c4[j];
-                }
-                uint32_t       ntot;
-                uint32_t       run = mat_block_scan(c, wsum, ntot);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    pfx[tid * 4 + j] = (uint16_t) run;
-                    run += c4[j];
-                }
-                __syncthreads();
-                auto rank = [&](uint32_t v) {
-                    const uint64_t w = bm64[v >> 6];
-                    return (uint32_t) pfx[v >> 6] + (uint32_t) __builtin_popcountll(w & ((1ull << (v & 63u)) - 1ull));
-                };
-#pragma unroll
-                for (int k = 0; k < kMatUB; k++)
-                    if (rv[k] != kEmpty) rpy[rank(rv[k])] = rp[k];
-                __syncthreads();  // payloads by rank complete
-                for (uint32_t e0 = 0; e0 < stot; e0 += kMatRCap) {  // survivors, batch by batch
-                    uint64_t a[kMatUB];
-                    uint32_t v[kMatUB], hit = 0;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) {
-                        const uint32_t e = e0 + tid + k * kMatThreads;
-                        v[k] = kEmpty;
-                        a[k] = 0;
-                        if (e < stot) {
-                            const uint32_t d = mat_find(spre, nsd, e);
-                            a[k] = sbase[d] + (e - spre[d]);
-                            v[k] = P.surv[a[k]] >> hs;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++)
-                        if (v[k] != kEmpty) hit |= ((bmw[v[k] >> 5] >> (v[k] & 31u)) & 1u) << k;
-                    uint32_t pos[kMatUB], sp[kMatUB];
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) pos[k] = (hit >> k) & 1u ? P.surv_pos[a[k]] : 0u;
-                    uint32_t       tot;
-                    const uint32_t off = mat_block_scan((uint32_t) __builtin_popcount(hit), wsum, tot);
-                    if (tot == 0) continue;  // (uniform)
-                    if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) sp[k] = (hit >> k) & 1u ? P.s_pay[pos[k]] : 0u;
-                    if (O.keep_s) {
-#pragma unroll
-                        for (int k = 0; k < kMatUB; k++)
-                            if ((hit >> k) & 1u) set_mark(pos[k]);
-                    }
-                    __syncthreads();
-                    uint64_t o = obase + off;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) {
-                        if (!((hit >> k) & 1u)) continue;
-                        const uint32_t rk = rank(v[k]);
-                        if (KR) set_flag(rk);
-                        if (o < P.cap) P.out[o] = make_uint2(rpy[rk], sp[k]);
-                        o++;
-                    }
-                }
-                if (KR) r_only(rtot, nullptr, rpy);  // (unique keys: ranks [0, rtot))
-                return;
-            }
-            // duplicate R keys: the hash table (over the same LDS)
-        }
-        if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform)
-            __syncthreads();  // descriptors visible; the bitmap path is done with the LDS
-            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            __syncthreads();
-            uint32_t rc[kMatU], rp[kMatU], v[kMatU], m[kMatU];
-            uint64_t a[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = tid + k * kMatThreads;
-                if (e < rtot) {
-                    const uint32_t d  = mat_find(rpre, nrd, e);
-                    const uint64_t ra = rbase[d] + (e - rpre[d]);
-                    rc[k] = P.r_codes[ra];
-                    rp[k] = P.r_pay[ra];
-                }
-                v[k] = kEmpty;
-                a[k] = 0;
-                if (e < stot) {
-                    const uint32_t d = mat_find(spre, nsd, e);
-                    a[k] = sbase[d] + (e - spre[d]);
-                    v[k] = P.surv[a[k]] >> hs;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kMatU; k++)
-                if (tid + k * kMatThreads < rtot) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
-            __syncthreads();  // table complete
-            mat_count(tk, v, m);
-            uint32_t cnt = 0;
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) cnt += m[k];
-            uint32_t pos[kMatU], sp[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;  // (in flight over the scan)
-            uint32_t       tot;
-            const uint32_t off = mat_block_scan(cnt, wsum, tot);
-            if (tot) {  // (uniform)
-                if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
-#pragma unroll
-                for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
-                if (O.keep_s) {
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++)
-                        if (m[k]) set_mark(pos[k]);
-                }
-                __syncthreads();
-                uint64_t o = obase + off;
-#pragma unroll
-                for (int k = 0; k < kMatU; k++) {
-                    if (!m[k]) continue;
-                    for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                        const uint32_t x = tk[h];
-                        if (x == kEmpty) break;
-                        if (x == v[k]) {
-                            if (KR) set_flag(h);
-                            if (o < P.cap) P.out[o] = make_uint2(tp[h], sp[k]);
-                            o++;
-                        }
-                    }
-                }
-            }
-            if (KR) r_only(kMatT, tk, tp);
-            return;
-        }
-    }
-    // ---- general form: R descriptor batches x R pieces x survivor batches
-    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {  // R run descriptors, batch by batch
-        const uint32_t nrd = min(kMatDesc, r1 - rd0);
-        __syncthreads();  // previous descriptors consumed
-        uint32_t c = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
-            c          = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
-        }
-        uint32_t       rtot;
-        const uint32_t rx = mat_block_scan(c, wsum, rtot);
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if (tid == 0) rpre[nrd] = rtot;
-        __syncthreads();
-        for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
-            const uint32_t pe = min(rtot, pb + kMatPiece);
-            __syncthreads();  // the previous piece's survivors and R-only rows are done with the table
-            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            if ((uint32_t) tid < kOutFlagWords) rflag[tid] = 0;
-            uint32_t rc[kMatU], rp[kMatU];  // this thread's R tuples of the piece (loads in flight)
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = pb + tid + k * kMatThreads;
-                rc[k] = kEmpty;
-                if (e < pe) {
-                    const uint32_t d = mat_find(rpre, nrd, e);
-                    const uint64_t a = rbase[d] + (e - rpre[d]);
-                    rc[k] = P.r_codes[a];
-                    rp[k] = P.r_pay[a];
-                }
-            }
-            __syncthreads();  // table and flags cleared
-#pragma unroll
-            for (int k = 0; k < kMatU; k++)
-                if (pb + tid + k * kMatThreads < pe) mat_insert1(tk, tp, rc[k] >> hs, rp[k]);
-            for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {  // survivor runs of the job
-                const uint32_t nsd = min(kMatDesc, qi1 - sd0);
-                __syncthreads();  // table complete; previous descriptors consumed
-                uint32_t sc = 0;
-                if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
-                uint32_t       stot;
-                const uint32_t sx = mat_block_scan(sc, wsum, stot);
-                if ((uint32_t) tid < nsd) spre[tid] = sx;
-                if (tid == 0) spre[nsd] = stot;
-                __syncthreads();
-                for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {
-                    uint64_t a[kMatU];
-                    uint32_t v[kMatU], m[kMatU];
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) {
-                        const uint32_t e = e0 + tid + k * kMatThreads;
-                        a[k] = ~0ull;
-                        v[k] = kEmpty;
-                        if (e < stot) {
-                            const uint32_t d = mat_find(spre, nsd, e);
-                            a[k] = sbase[d] + (e - spre[d]);
-                            v[k] = P.surv[a[k]] >> hs;
-                        }
-                    }
-                    mat_count(tk, v, m);
-                    uint32_t cnt = 0;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) cnt += m[k];
-                    uint32_t       tot;
-                    const uint32_t off = mat_block_scan(cnt, wsum, tot);
-                    if (tot == 0) continue;  // (uniform)
-                    if (tid == 0) obase = atomicAdd(P.count, (unsigned long long) tot);
-                    __syncthreads();
-                    uint64_t o = obase + off;
-                    uint32_t pos[kMatU], sp[kMatU];
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) {
-                        if (!m[k]) continue;
-                        if (O.keep_s) set_mark(pos[k]);
-                        for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                            const uint32_t x = tk[h];
-                            if (x == kEmpty) break;
-                            if (x == v[k]) {
-                                if (KR) set_flag(h);
-                                if (o < P.cap) P.out[o] = make_uint2(tp[h], sp[k]);
-                                o++;
-                            }
-                        }
-                    }
-                }
-            }
-            if (KR) r_only(kMatT, tk, tp);  // (its first barrier: the table complete, the flags final)
-        }
-    }
+    __shared__ JobLds   L;
+    PairPolicy<true, KR> pol{O.m, &O, smem, L, rflag};
+    payload_job(O.m, pol, smem, L);
 }
 
 void launch_join_outer(const OuterJoinParams& p0, uint32_t jobs, hipStream_t st) {
     OuterJoinParams p = p0;
-    p.m.xcd8          = ((jobs >> p.m.log2NSUB) % 8 == 0) ? 1u : 0u;
+    p.m.j.xcd8        = job_xcd8(jobs, p.m.j.log2NSUB);
     if (p.keep_r) k_join_outer<true><<<jobs, kMatThreads, 0, st>>>(p);
     else k_join_outer<false><<<jobs, kMatThreads, 0, st>>>(p);
 }
@@ -4785,14 +4527,13 @@ void launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t s
 }
 
 // ================================================================= K10g: the group join
-// k_join_mat's job layout, XCD-aware order and three forms (single-shot bitmap + rank, single-shot
-// hash table, descriptor batches x R pieces x survivor batches) and k_join_outer<true>'s early
-// returns, but no pairs: every R tuple of the job owns an accumulator {count (u32), sum (u64)} in
-// LDS, and a survivor adds 1 and its sign-extended payload to the accumulator of every R tuple with
-// its key (LDS atomics, ds_add_u32 and ds_add_u64). A survivor batch is the codes, the table test
-// and the surv_pos -> s_pay gather: no scan, no output atomic, no barrier. A piece sees all of the
-// job's survivors before the next piece is loaded, so its accumulators are final at its end; then
-// one workgroup scan and one output atomic place the rows {R.payload, count, sum}, 16 bytes each.
+// k_join_mat's job (payload_job) with a policy that writes no pairs (GroupPolicy; under ALL its early
+// returns are k_join_outer<true>'s): every R tuple of the job owns an accumulator {count (u32), sum
+// (u64)} in LDS, and a survivor adds 1 and its sign-extended payload to the accumulator of every R
+// tuple with its key (LDS atomics, ds_add_u32 and ds_add_u64). A survivor batch is the codes, the
+// table test and the surv_pos -> s_pay gather: no scan, no output atomic, no barrier. The
+// accumulators are final at the end of a piece; then one workgroup scan and one output atomic
+// place the rows {R.payload, count, sum}, 16 bytes each.
 // Accumulators are indexed by rank on the bitmap path (up to kMatRCap) and, on the hash forms, by
 // the tuple's ordinal in its piece (up to kMatPiece), which the table stores where k_join_mat's
 // stores the payload; the payloads stay in the registers of the threads that loaded them, which
@@ -4874,287 +4615,65 @@ __device__ __forceinline__ void group_rows(const GroupJoinParams& G, const uint3
     }
 }
 
+// LDS union: bitmap path {bitmap [kMatBmWords], rank prefix (u16) [kMatBmWords / 2], sums (u64)
+// [kMatRCap], counts [kMatRCap]}, or hash forms {keys [kMatT], ordinals [kMatT], sums (u64)
+// [kMatPiece], counts [kMatPiece]}; GRP_COUNT_MINMAX: minima and maxima (i32) where the sums are
+template <bool ALL, uint32_t AGG>
+struct GroupPolicy {
+    static constexpr bool kAllR = ALL, kStorePay = false;
+    const GroupJoinParams& G;
+    uint32_t*              smem;
+    JobLds&                L;
+
+    template <bool BM>
+    static constexpr uint32_t N = BM ? kMatRCap : kMatPiece;  // accumulators of the form
+    template <bool BM>
+    __device__ __forceinline__ unsigned long long* sums() const {
+        return (unsigned long long*) (BM ? bm_rest(smem) : smem + 2 * kMatT);
+    }
+    template <bool BM>
+    __device__ __forceinline__ uint32_t* counts() const { return (uint32_t*) sums<BM>() + 2 * N<BM>; }
+
+    template <bool BM>
+    __device__ __forceinline__ void clear(uint32_t n) const {
+        for (uint32_t i = threadIdx.x; i < n; i += kMatThreads) group_clear<AGG, N<BM>>(counts<BM>(), sums<BM>(), i);
+    }
+
+    template <bool BM, int U, class Hit, class Each>
+    __device__ __forceinline__ void batch(const uint64_t (&a)[U], uint32_t, Hit&& hit, Each&& each) const {
+        const uint32_t* to = smem + kMatT;
+        uint32_t        pos[U], sp[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) pos[k] = hit(k) ? G.m.j.surv_pos[a[k]] : 0u;
+#pragma unroll
+        for (int k = 0; k < U; k++) sp[k] = hit(k) ? G.m.s_pay[pos[k]] : 0u;
+#pragma unroll
+        for (int k = 0; k < U; k++)
+            if (hit(k))
+                each(k, [&](uint32_t i) { group_add<AGG, N<BM>>(counts<BM>(), sums<BM>(), BM ? i : to[i], sp[k]); });
+    }
+
+    template <bool BM, int U, class Index>
+    __device__ __forceinline__ void end(const uint32_t (&rv)[U], const uint32_t (&rp)[U], uint32_t, Index&& index) const {
+        uint32_t idx[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) idx[k] = rv[k] != kEmpty ? index(k) : kEmpty;
+        group_rows<ALL, AGG, N<BM>, U>(G, idx, rp, counts<BM>(), sums<BM>(), L.wsum, &L.ptot, &L.obase);
+    }
+};
+
 template <bool ALL, uint32_t AGG>
 __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_join_group(GroupJoinParams G) {
-    const MatJoinParams& P = G.m;
-    // LDS union: bitmap path {bitmap [kMatBmWords], rank prefix (u16) [kMatBmWords / 2], sums (u64)
-    // [kMatRCap], counts [kMatRCap]}, or hash forms {keys [kMatT], ordinals [kMatT], sums (u64)
-    // [kMatPiece], counts [kMatPiece]}; GRP_COUNT_MINMAX: minima and maxima (i32) where the sums are
     __shared__ __attribute__((aligned(16))) uint32_t smem[kGrpWords];
-    uint32_t* tk = smem;
-    uint32_t* to = smem + kMatT;
-    unsigned long long* hsum = (unsigned long long*) (smem + 2 * kMatT);
-    uint32_t*           hcnt = smem + 2 * kMatT + 2 * kMatPiece;
-    __shared__ uint32_t dupf;
-    __shared__ uint32_t rpre[kMatDesc + 1], spre[kMatDesc + 1];
-    __shared__ uint64_t rbase[kMatDesc], sbase[kMatDesc];
-    __shared__ uint32_t wsum[kMatThreads / 64];
-    __shared__ unsigned long long obase, ptot;
-    const int      tid  = threadIdx.x;
-    const uint32_t NSUB = 1u << P.log2NSUB, hs = P.hash_shift;
-    uint32_t job = blockIdx.x;
-    if (P.xcd8) {  // (k_join_mat's XCD-aware job order)
-        const uint32_t x = blockIdx.x & 7u, l = blockIdx.x >> 3;
-        job = ((((l >> P.log2NSUB) << 3) | x) << P.log2NSUB) | (l & (NSUB - 1u));
-    }
-    const uint32_t q = job >> P.log2NSUB, s = job & (NSUB - 1u);
-    const uint32_t r0 = P.r_sweep_start[q], r1 = P.r_sweep_start[q + 1];
-    const uint32_t qi0 = P.item_start[q], qi1 = P.item_start[q + 1];
-    // (uniform) no R in q: no row. No probe items in q: no row with count > 0; under ALL every R
-    // tuple of the job is a row with count 0 (k_join_outer<true>'s rule)
-    if (r0 == r1 || (qi0 == qi1 && !ALL)) return;
-    const uint32_t lq0 = P.list_start[q];
-    const uint32_t npc = (qi1 - qi0) / P.nseg;  // probe pieces of q per segment (0: s_desc is not called)
-    auto s_desc = [&](uint32_t it, uint32_t& cnt, uint64_t& base) {  // survivor run of item it
-        const uint32_t local = it - qi0, seg = local / npc, piece = local - seg * npc;
-        cnt  = P.surv_cnt[(uint64_t) it * NSUB + s];
-        base = (uint64_t) seg * P.surv_seg_stride + (uint64_t) (lq0 + piece * P.CH) * 32 +
-               P.surv_off[(uint64_t) it * NSUB + s];
-    };
-    if (tid == 0) ptot = 0;  // (first added to after a barrier)
-    // ---- single-shot form
-    if (r1 - r0 <= kMatDesc && qi1 - qi0 <= kMatDesc) {  // (uniform)
-        const uint32_t nrd = r1 - r0, nsd = qi1 - qi0;
-        uint32_t       rcn = 0, scn = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (r0 + tid) * NSUB + s;
-            rcn        = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (r0 + tid) * P.slot + P.r_off[r];
-        }
-        if ((uint32_t) tid < nsd) s_desc(qi0 + tid, scn, sbase[tid]);
-        uint32_t       rtot, stot;
-        const uint32_t rx = mat_block_scan(rcn, wsum, rtot);
-        const uint32_t sx = mat_block_scan(scn, wsum, stot);
-        if (rtot == 0 || (stot == 0 && !ALL)) return;  // (uniform) as above, for this sub
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if ((uint32_t) tid < nsd) spre[tid] = sx;
-        if (tid == 0) {
-            rpre[nrd] = rtot;
-            spre[nsd] = stot;
-            dupf      = 0;
-        }
-        if (P.bm && rtot <= kMatRCap) {  // (uniform) ---- bitmap path
-            uint32_t*           bmw  = smem;
-            uint16_t*           pfx  = (uint16_t*) (smem + kMatBmWords);
-            unsigned long long* bsum = (unsigned long long*) (smem + kMatBmWords + kMatBmWords / 4);
-            uint32_t*           bcnt = smem + kMatBmWords + kMatBmWords / 4 + 2 * kMatRCap;
-            const uint64_t*     bm64 = (const uint64_t*) smem;
-            for (uint32_t i = tid; i < kMatBmWords; i += kMatThreads) bmw[i] = 0;
-            for (uint32_t i = tid; i < rtot; i += kMatThreads) group_clear<AGG, kMatRCap>(bcnt, bsum, i);
-            __syncthreads();  // descriptors visible, bitmap and accumulators cleared
-            uint32_t rv[kMatUB], rp[kMatUB];
-#pragma unroll
-            for (int k = 0; k < kMatUB; k++) {
-                const uint32_t e = tid + k * kMatThreads;
-                rv[k] = kEmpty;
-                rp[k] = 0;
-                if (e < rtot) {
-                    const uint32_t d  = mat_find(rpre, nrd, e);
-                    const uint64_t ra = rbase[d] + (e - rpre[d]);
-                    rv[k] = P.r_codes[ra] >> hs;
-                    rp[k] = P.r_pay[ra];
-                }
-            }
-            uint32_t dup = 0;
-#pragma unroll
-            for (int k = 0; k < kMatUB; k++)
-                if (rv[k] != kEmpty) dup |= (atomicOr(&bmw[rv[k] >> 5], 1u << (rv[k] & 31u)) >> (rv[k] & 31u)) & 1u;
-            if (dup) dupf = 1;
-            __syncthreads();
-            if (!dupf) {  // (uniform)
-                uint32_t c4[4], c = 0;  // rank prefix: thread t owns 64-bit words 4t .. 4t + 3
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    c4[j] = (uint32_t) __builtin_popcountll(bm64[tid * 4 + j]);
-                    c += c4[j];
-                }
-                uint32_t       ntot;
-                uint32_t       run = mat_block_scan(c, wsum, ntot);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    pfx[tid * 4 + j] = (uint16_t) run;
-                    run += c4[j];
-                }
-                __syncthreads();
-                auto rank = [&](uint32_t v) {
-                    const uint64_t w = bm64[v >> 6];
-                    return (uint32_t) pfx[v >> 6] + (uint32_t) __builtin_popcountll(w & ((1ull << (v & 63u)) - 1ull));
-                };
-                for (uint32_t e0 = 0; e0 < stot; e0 += kMatRCap) {  // survivors, batch by batch: no barrier
-                    uint64_t a[kMatUB];
-                    uint32_t v[kMatUB], hit = 0;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) {
-                        const uint32_t e = e0 + tid + k * kMatThreads;
-                        v[k] = kEmpty;
-                        a[k] = 0;
-                        if (e < stot) {
-                            const uint32_t d = mat_find(spre, nsd, e);
-                            a[k] = sbase[d] + (e - spre[d]);
-                            v[k] = P.surv[a[k]] >> hs;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++)
-                        if (v[k] != kEmpty) hit |= ((bmw[v[k] >> 5] >> (v[k] & 31u)) & 1u) << k;
-                    uint32_t pos[kMatUB], sp[kMatUB];
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) pos[k] = (hit >> k) & 1u ? P.surv_pos[a[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++) sp[k] = (hit >> k) & 1u ? P.s_pay[pos[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatUB; k++)
-                        if ((hit >> k) & 1u) group_add<AGG, kMatRCap>(bcnt, bsum, rank(v[k]), sp[k]);
-                }
-                uint32_t idx[kMatUB];
-#pragma unroll
-                for (int k = 0; k < kMatUB; k++) idx[k] = rv[k] != kEmpty ? rank(rv[k]) : kEmpty;
-                group_rows<ALL, AGG, kMatRCap, kMatUB>(G, idx, rp, bcnt, bsum, wsum, &ptot, &obase);
-                return;
-            }
-            // duplicate R keys: the hash table (over the same LDS)
-        }
-        if (rtot <= kMatPiece && stot <= kMatPiece) {  // (uniform)
-            __syncthreads();  // descriptors visible; the bitmap path is done with the LDS
-            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            for (uint32_t i = tid; i < rtot; i += kMatThreads) group_clear<AGG, kMatPiece>(hcnt, hsum, i);
-            __syncthreads();
-            uint32_t rc[kMatU], rp[kMatU], v[kMatU], m[kMatU], idx[kMatU];
-            uint64_t a[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = tid + k * kMatThreads;
-                idx[k] = kEmpty;
-                rc[k]  = 0;
-                rp[k]  = 0;
-                if (e < rtot) {
-                    const uint32_t d  = mat_find(rpre, nrd, e);
-                    const uint64_t ra = rbase[d] + (e - rpre[d]);
-                    idx[k] = e;
-                    rc[k]  = P.r_codes[ra];
-                    rp[k]  = P.r_pay[ra];
-                }
-                v[k] = kEmpty;
-                a[k] = 0;
-                if (e < stot) {
-                    const uint32_t d = mat_find(spre, nsd, e);
-                    a[k] = sbase[d] + (e - spre[d]);
-                    v[k] = P.surv[a[k]] >> hs;
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < kMatU; k++)
-                if (idx[k] != kEmpty) mat_insert1(tk, to, rc[k] >> hs, idx[k]);
-            __syncthreads();  // table complete
-            mat_count(tk, v, m);
-            uint32_t pos[kMatU], sp[kMatU];
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                if (!m[k]) continue;
-                for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                    const uint32_t x = tk[h];
-                    if (x == kEmpty) break;
-                    if (x == v[k]) group_add<AGG, kMatPiece>(hcnt, hsum, to[h], sp[k]);
-                }
-            }
-            group_rows<ALL, AGG, kMatPiece, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
-            return;
-        }
-    }
-    // ---- general form: R descriptor batches x R pieces x survivor batches
-    for (uint32_t rd0 = r0; rd0 < r1; rd0 += kMatDesc) {  // R run descriptors, batch by batch
-        const uint32_t nrd = min(kMatDesc, r1 - rd0);
-        __syncthreads();  // previous descriptors consumed
-        uint32_t c = 0;
-        if ((uint32_t) tid < nrd) {
-            const uint64_t r = (uint64_t) (rd0 + tid) * NSUB + s;
-            c          = P.r_cnt[r];
-            rbase[tid] = (uint64_t) (rd0 + tid) * P.slot + P.r_off[r];
-        }
-        uint32_t       rtot;
-        const uint32_t rx = mat_block_scan(c, wsum, rtot);
-        if ((uint32_t) tid < nrd) rpre[tid] = rx;
-        if (tid == 0) rpre[nrd] = rtot;
-        __syncthreads();
-        for (uint32_t pb = 0; pb < rtot; pb += kMatPiece) {
-            const uint32_t pe = min(rtot, pb + kMatPiece);
-            __syncthreads();  // the previous piece's survivors and rows are done with the table
-            for (uint32_t i = tid; i < kMatT; i += kMatThreads) tk[i] = kEmpty;
-            for (uint32_t i = tid; i < kMatPiece; i += kMatThreads) group_clear<AGG, kMatPiece>(hcnt, hsum, i);
-            uint32_t rc[kMatU], rp[kMatU], idx[kMatU];  // this thread's R tuples of the piece
-#pragma unroll
-            for (int k = 0; k < kMatU; k++) {
-                const uint32_t e = pb + tid + k * kMatThreads;
-                idx[k] = kEmpty;
-                rc[k]  = 0;
-                rp[k]  = 0;
-                if (e < pe) {
-                    const uint32_t d = mat_find(rpre, nrd, e);
-                    const uint64_t a = rbase[d] + (e - rpre[d]);
-                    idx[k] = e - pb;
-                    rc[k]  = P.r_codes[a];
-                    rp[k]  = P.r_pay[a];
-                }
-            }
-            __syncthreads();  // table and accumulators cleared
-#pragma unroll
-            for (int k = 0; k < kMatU; k++)
-                if (idx[k] != kEmpty) mat_insert1(tk, to, rc[k] >> hs, idx[k]);
-            for (uint32_t sd0 = qi0; sd0 < qi1; sd0 += kMatDesc) {  // survivor runs of the job
-                const uint32_t nsd = min(kMatDesc, qi1 - sd0);
-                __syncthreads();  // table complete; previous descriptors consumed
-                uint32_t sc = 0;
-                if ((uint32_t) tid < nsd) s_desc(sd0 + tid, sc, sbase[tid]);
-                uint32_t       stot;
-                const uint32_t sx = mat_block_scan(sc, wsum, stot);
-                if ((uint32_t) tid < nsd) spre[tid] = sx;
-                if (tid == 0) spre[nsd] = stot;
-                __syncthreads();
-                for (uint32_t e0 = 0; e0 < stot; e0 += kMatPiece) {  // (no barrier in a batch)
-                    uint64_t a[kMatU];
-                    uint32_t v[kMatU], m[kMatU];
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) {
-                        const uint32_t e = e0 + tid + k * kMatThreads;
-                        a[k] = 0;
-                        v[k] = kEmpty;
-                        if (e < stot) {
-                            const uint32_t d = mat_find(spre, nsd, e);
-                            a[k] = sbase[d] + (e - spre[d]);
-                            v[k] = P.surv[a[k]] >> hs;
-                        }
-                    }
-                    mat_count(tk, v, m);
-                    uint32_t pos[kMatU], sp[kMatU];
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) pos[k] = m[k] ? P.surv_pos[a[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) sp[k] = m[k] ? P.s_pay[pos[k]] : 0u;
-#pragma unroll
-                    for (int k = 0; k < kMatU; k++) {
-                        if (!m[k]) continue;
-                        for (uint32_t h = mat_jslot(v[k]);; h = (h + 1) & (kMatT - 1)) {
-                            const uint32_t x = tk[h];
-                            if (x == kEmpty) break;
-                            if (x == v[k]) group_add<AGG, kMatPiece>(hcnt, hsum, to[h], sp[k]);
-                        }
-                    }
-                }
-            }
-            // (its first barrier: the accumulators final; under ALL a job without probe items skips
-            // the survivor loop, and the barrier also completes the table it does not read)
-            group_rows<ALL, AGG, kMatPiece, kMatU>(G, idx, rp, hcnt, hsum, wsum, &ptot, &obase);
-        }
-    }
+    __shared__ JobLds L;
+    if (threadIdx.x == 0) L.ptot = 0;  // (the piece's pairs: first added to after a barrier, zero between pieces)
+    GroupPolicy<ALL, AGG> pol{G, smem, L};
+    payload_job(G.m, pol, smem, L);
 }
 
 void launch_join_group(const GroupJoinParams& p0, uint32_t jobs, hipStream_t st) {
     GroupJoinParams p = p0;
-    p.m.xcd8          = ((jobs >> p.m.log2NSUB) % 8 == 0) ? 1u : 0u;
+    p.m.j.xcd8        = job_xcd8(jobs, p.m.j.log2NSUB);
     if (p.agg == GRP_COUNT_MINMAX) {
         if (p.all) k_join_group<true, GRP_COUNT_MINMAX><<<jobs, kMatThreads, 0, st>>>(p);
         else k_join_group<false, GRP_COUNT_MINMAX><<<jobs, kMatThreads, 0, st>>>(p);

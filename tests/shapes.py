@@ -5,6 +5,10 @@ calls, the key stream format is restated from DESIGN.md s3, and `classify` resta
 `join_job` / `k_join_mat` (hwbrj_kernels.hip) a (job, part) must take, from the tables the join left
 behind (hwbrj_tables_read) and the kernel constants (hwbrj_tables_info). No constant of the kernels
 is written down here: every threshold comes from the `info` dict.
+
+The last section builds the crafted relations that the outer-join and the materializing-join tests
+share (mat_geometry there is the one function that runs a join: it asks the library for the
+geometry the keys are crafted for).
 """
 from __future__ import annotations
 
@@ -360,3 +364,107 @@ def classify_mat(tables, info, R_dup_per_job, jobs=None):
             rec.update(cls="general", r_batches=-(-(r1 - r0) // D), pieces=pieces, s_batches=sb)
         out[job] = rec
     return out
+
+
+# ------------------------------------------------- crafted relations of the pass-2 job tests
+INT_MAX, INT_MIN = 2**31 - 1, -2**31
+_GEOM = {}
+
+
+def mat_geometry(hw, to_dev, args, name, nR):
+    """tables_info of a materializing join of |R| = nR under args (throw-away keys); `name` names
+    args in the cache, to_dev(array) puts a relation on the device."""
+    if (name, nR) not in _GEOM:
+        R = np.stack([np.arange(nR, dtype=np.int32), np.zeros(nR, dtype=np.int32)], 1)
+        hw.join_materialize_device(to_dev(R), to_dev(R[:8]), args, capacity=64)
+        _GEOM[(name, nR)] = hw.tables_info()
+    return dict(_GEOM[(name, nR)])
+
+
+def same_geometry(hw, to_dev, R, args, info):
+    """A materializing join of this R and args reports the geometry the keys were crafted for."""
+    hw.join_materialize_device(to_dev(R), to_dev(R[:8]), args, capacity=64)
+    now = hw.tables_info()
+    keys = ("mode", "format", "F", "NSUB", "sub_shift", "hash_shift", "nseg", "bitmap", "G", "CH", "BSW", "slot")
+    assert {k: now[k] for k in keys} == {k: info[k] for k in keys}
+
+
+def payloads(n, rng):
+    """n distinct random int32 payloads, none of them INT_MIN (the outer joins' default null)."""
+    p = np.unique(rng.integers(-2**31 + 1, 2**31, size=2 * n + 16))
+    assert p.size >= n
+    return rng.permutation(p)[:n]
+
+
+def rel(keys, rng):
+    keys = np.asarray(keys).astype(np.int64)
+    return np.stack([keys, payloads(keys.size, rng)], 1).astype(np.int32).reshape(-1, 2)
+
+
+def duplicates_on_both_sides(crc, args):
+    """5,000 R keys three times each, with INT_MAX, INT_MIN, 0, -1 and the key whose code is the
+    kernels' empty-slot value; S holds key i (i mod 5) times (the special keys 0 to 4 times) and
+    7,000 keys R lacks. info: special (the five keys), hits (S rows per R key)."""
+    rng = np.random.default_rng(21)
+    special = np.array([INT_MAX, INT_MIN, 0, -1, int(crc.key_of(0xFFFFFFFF))], dtype=np.int64)
+    rest = np.setdiff1d(rng.choice(np.arange(-10**6, 10**6), 6000, replace=False), special)[:5000 - special.size]
+    keys = np.concatenate([special, rest])
+    assert np.unique(keys).size == 5000
+    hits = np.concatenate([[0, 1, 2, 3, 4], np.arange(keys.size - 5) % 5])
+    Rk = np.repeat(keys, 3)
+    Sk = np.concatenate([np.repeat(keys, hits), rng.integers(2 * 10**6, 3 * 10**6, size=7000)])
+    rng.shuffle(Rk)
+    rng.shuffle(Sk)
+    return rel(Rk, rng), rel(Sk, rng), args, {"special": special, "hits": hits}
+
+
+def hot_r_key_across_pieces(crc, args, geometry):
+    """One job holds an R key 2 kMatPiece + 5 times, keys 11, 12, 13 and six keys no S row has (three
+    at the head of R, three at its tail: the job's first and last pieces), more than kMatRCap tuples.
+    Its survivors: 40 of the hot key, 10 of 11, 10 of 12, none of 13, 50 of keys R lacks.
+    geometry(nR) gives the tables_info the codes are crafted for; info is that, with the job (q0,
+    sub0) and `hot`, the hot key's R rows."""
+    rng = np.random.default_rng(33)
+    nR = 20000
+    info = geometry(nR)
+    q0, sub0 = 17, 1
+    hot = 2 * info["m_piece"] + 5
+    rv = np.concatenate([np.full(hot, 7), [11, 12, 13]])
+    lone = 2000 + np.arange(6)
+    assert rv.size + lone.size >= info["m_rcap"] + 1
+    nf = nR - rv.size - lone.size
+    fill = filler_codes(info, nf + 3000, {q0}, 1)  # distinct: R takes the first nf
+    mid = np.concatenate([job_codes(info, q0, sub0, rv), fill[:nf]])
+    rng.shuffle(mid)
+    lc = job_codes(info, q0, sub0, lone)
+    Rc = np.concatenate([lc[:3], mid, lc[3:]])
+    sv = np.concatenate([np.full(40, 7), np.repeat([11, 12], 10), 1000 + np.arange(50)])
+    Sc = np.concatenate([job_codes(info, q0, sub0, sv), fill[nf - 3000:]])  # 3,000 of R's, 3,000 not
+    rng.shuffle(Sc)
+    info.update(q0=q0, sub0=sub0, hot=hot)
+    return rel(crc.key_of(Rc), rng), rel(crc.key_of(Sc), rng), args, info
+
+
+def more_descriptors_than_a_batch(crc, args, geometry):
+    """A partition of kMatDesc * BSW * 32 + 1 R tuples (more than kMatDesc build sweeps: several R
+    descriptor batches per job), 60,000 distinct keys repeated all over it; S has rows of 50,000 of
+    them only. info: the geometry, with q0 (the partition), n_q (its R tuples), member (its 60,000 codes) and
+    the shuffled code columns Rc, Sc."""
+    rng = np.random.default_rng(55)
+    q0, fill = 5, 20000
+    probe = geometry(8)
+    n_q = probe["m_desc"] * probe["BSW"] * 32 + 1
+    nR = n_q + fill
+    info = geometry(nR)
+    assert (info["m_desc"], info["BSW"]) == (probe["m_desc"], probe["BSW"])
+    lf = info["F"].bit_length() - 1
+    hi = rng.choice(1 << min(32 - lf, 24), 66000, replace=False).astype(np.uint64)
+    qcodes = (np.uint64(q0) | (hi << np.uint64(lf))).astype(np.uint32)
+    member, absent = qcodes[:60000], qcodes[60000:]
+    Rc = np.concatenate([member[rng.integers(0, member.size, size=n_q)], filler_codes(info, fill, {q0}, 1)])
+    Sc = np.concatenate([member[rng.integers(0, 50000, size=3000)], absent[rng.integers(0, absent.size, size=3000)],
+                         Rc[n_q:n_q + 3000], filler_codes(info, 3000, {q0}, 777)])
+    rng.shuffle(Rc)
+    rng.shuffle(Sc)
+    info.update(q0=q0, n_q=n_q, member=member, Rc=Rc, Sc=Sc)
+    return rel(crc.key_of(Rc), rng), rel(crc.key_of(Sc), rng), args, info

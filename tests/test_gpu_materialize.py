@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+import shapes
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 INT_MAX = 2**31 - 1
@@ -96,6 +98,60 @@ def test_pairs_edge_sizes(hw, cuda, orc, name):
         R = np.stack([Rk, rng.integers(-2**31, 2**31, size=nR)], 1).astype(np.int32).reshape(-1, 2)
         S = np.stack([Sk, rng.integers(-2**31, 2**31, size=nS)], 1).astype(np.int32).reshape(-1, 2)
         _check(hw, cuda, orc, R, S, _args(hw)[name])
+
+
+# Crafted jobs (the relations of tests/test_gpu_outer.py's cases of the same names): k_join_mat's
+# duplicate fallback of the bitmap path, its general form over several R pieces, and several R
+# descriptor batches per job.
+@pytest.fixture(scope="module")
+def crc(orc):
+    return shapes.Crc(orc.crc)
+
+
+def _crafted_args(hw, name):
+    return {**_args(hw), "blocked_f256": hw.BloomFilterArgs(hw.BLOCKED, 1 << 18, 1, 1024)}[name]
+
+
+def _geometry(hw, cuda, name):
+    return lambda nR: shapes.mat_geometry(hw, lambda a: to_dev(cuda, a), _crafted_args(hw, name), name, nR)
+
+
+def _forms(hw, jobs=None):
+    """(tables_info, {job: shapes.classify_mat record}) of the materializing join that just ran, for
+    jobs whose R keys hold duplicates: the form of k_join_mat each job must have taken."""
+    info = hw.tables_info()
+    T = {"r_sweep_start": hw.tables_read(hw.TAB_R_SWEEP_START), "s_item_start": hw.tables_read(hw.TAB_S_ITEM_START),
+         "r_cnt": hw.tables_read(hw.TAB_R_RUN_CNT), "surv_cnt": hw.tables_read(hw.TAB_SURV_CNT)}
+    return info, shapes.classify_mat(T, info, [True] * info["jobs"], jobs)
+
+
+@pytest.mark.parametrize("name", ["nobloom", "blocked_packed"])
+def test_duplicates_on_both_sides(hw, cuda, orc, crc, name):
+    R, S, args, _ = shapes.duplicates_on_both_sides(crc, _crafted_args(hw, name))
+    _check(hw, cuda, orc, R, S, args)
+    info, C = _forms(hw)  # every R key is there three times: no job stays on the bitmap path
+    busy = [c for c in C.values() if c["cls"] != "empty"]
+    assert busy and all(c["cls"] in ("hash1", "general") for c in busy)
+    assert all(c["start"] == ("dup" if info["bitmap"] else None) for c in busy if c["cls"] == "hash1")
+
+
+@pytest.mark.parametrize("name", ["nobloom", "blocked_packed"])
+def test_hot_r_key_across_pieces(hw, cuda, orc, crc, name):
+    R, S, args, info = shapes.hot_r_key_across_pieces(crc, _crafted_args(hw, name), _geometry(hw, cuda, name))
+    shapes.same_geometry(hw, lambda a: to_dev(cuda, a), R, args, info)
+    _check(hw, cuda, orc, R, S, args)
+    job = info["q0"] * info["NSUB"] + info["sub0"]
+    c = _forms(hw, [job])[1][job]  # the general form, the hot key in three R pieces
+    assert c["cls"] == "general" and c["pieces"] >= 3 and c["r_keys"] > info["m_rcap"]
+
+
+@pytest.mark.parametrize("name", ["nobloom", "blocked_f256"])
+def test_more_descriptors_than_a_batch(hw, cuda, orc, crc, name):
+    R, S, args, info = shapes.more_descriptors_than_a_batch(crc, _crafted_args(hw, name), _geometry(hw, cuda, name))
+    _check(hw, cuda, orc, R, S, args)
+    jobs = [info["q0"] * info["NSUB"] + s for s in range(info["NSUB"])]
+    C = _forms(hw, jobs)[1]  # several R descriptor batches per job
+    assert any(c["cls"] == "general" and c["r_batches"] >= 2 for c in C.values())
 
 
 def test_pairs_zipf_and_nonunique(hw, cuda, orc, gen3):

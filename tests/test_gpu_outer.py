@@ -56,16 +56,7 @@ def _u64(rows):
     return np.sort(rows.view(np.uint64).ravel())
 
 
-def _payloads(n, rng):
-    """n distinct random int32 payloads, none of them NULL."""
-    p = np.unique(rng.integers(-2**31 + 1, 2**31, size=2 * n + 16))
-    assert p.size >= n
-    return rng.permutation(p)[:n]
-
-
-def _rel(keys, rng):
-    keys = np.asarray(keys).astype(np.int64)
-    return np.stack([keys, _payloads(keys.size, rng)], 1).astype(np.int32).reshape(-1, 2)
+_payloads, _rel = shapes.payloads, shapes.rel  # (distinct random payloads, none of them NULL)
 
 
 def _col(pay, null, left):
@@ -128,24 +119,14 @@ def job_counts(hw, rows, R, S, jobk, null=NULL):
             int((in_r & (rows[:, 1] == null)).sum()))
 
 
-_GEOM = {}
-
-
 def geometry(hw, cuda, args, name, nR):
     """tables_info of a materializing join of |R| = nR under args (throw-away keys)."""
-    if (name, nR) not in _GEOM:
-        R = np.stack([np.arange(nR, dtype=np.int32), np.zeros(nR, dtype=np.int32)], 1)
-        hw.join_materialize_device(to_dev(cuda, R), to_dev(cuda, R[:8]), args, capacity=64)
-        _GEOM[(name, nR)] = hw.tables_info()
-    return dict(_GEOM[(name, nR)])
+    return shapes.mat_geometry(hw, lambda a: to_dev(cuda, a), args, name, nR)
 
 
 def same_geometry(hw, cuda, R, args, info):
     """A materializing join of this R and args reports the geometry the keys were crafted for."""
-    hw.join_materialize_device(to_dev(cuda, R), to_dev(cuda, R[:8]), args, capacity=64)
-    now = hw.tables_info()
-    keys = ("mode", "format", "F", "NSUB", "sub_shift", "hash_shift", "nseg", "bitmap", "G", "CH", "BSW", "slot")
-    assert {k: now[k] for k in keys} == {k: info[k] for k in keys}
+    shapes.same_geometry(hw, lambda a: to_dev(cuda, a), R, args, info)
 
 
 # ------------------------------------------------------------------------------ 1: every mode
@@ -190,18 +171,9 @@ def test_duplicates_on_both_sides(hw, cuda, orc, crc, name):
     """5,000 R keys three times each, with INT_MAX, INT_MIN, 0, -1 and the key whose code is the
     kernels' empty-slot value; S holds key i (i mod 5) times (the special keys 0 to 4 times) and
     7,000 keys R lacks: inner = 3 x the hits, R-only = 3 rows for every key hit 0 times."""
-    rng = np.random.default_rng(21)
-    special = np.array([INT_MAX, INT_MIN, 0, -1, int(crc.key_of(0xFFFFFFFF))], dtype=np.int64)
-    rest = np.setdiff1d(rng.choice(np.arange(-10**6, 10**6), 6000, replace=False), special)[:5000 - special.size]
-    keys = np.concatenate([special, rest])
-    assert np.unique(keys).size == 5000
-    hits = np.concatenate([[0, 1, 2, 3, 4], np.arange(keys.size - 5) % 5])
-    Rk = np.repeat(keys, 3)
-    Sk = np.concatenate([np.repeat(keys, hits), rng.integers(2 * 10**6, 3 * 10**6, size=7000)])
-    rng.shuffle(Rk)
-    rng.shuffle(Sk)
-    R, S = _rel(Rk, rng), _rel(Sk, rng)
-    got, _ = check(hw, cuda, orc, R, S, _args(hw)[name], tag="duplicates")
+    R, S, args, info = shapes.duplicates_on_both_sides(crc, _args(hw)[name])
+    special, hits = info["special"], info["hits"]
+    got, _ = check(hw, cuda, orc, R, S, args, tag="duplicates")
     inner, s_only, r_only = _REF["duplicates"]
     assert inner.shape[0] == 3 * int(hits.sum())
     assert r_only.shape[0] == 3 * int((hits == 0).sum())
@@ -218,25 +190,9 @@ def test_hot_r_key_across_pieces(hw, cuda, orc, crc, name):
     at the head of R, three at its tail: the job's first and last pieces), more than kMatRCap tuples.
     Its survivors: 40 of the hot key, 10 of 11, 10 of 12, none of 13, 50 of keys R lacks. A flag or a
     mark decided per piece instead of per job gives other counts."""
-    rng = np.random.default_rng(33)
-    args = _args(hw)[name]
-    nR = 20000
-    info = geometry(hw, cuda, args, name, nR)
-    q0, sub0 = 17, 1
-    hot = 2 * info["m_piece"] + 5
-    rv = np.concatenate([np.full(hot, 7), [11, 12, 13]])
-    lone = 2000 + np.arange(6)
-    assert rv.size + lone.size >= info["m_rcap"] + 1
-    nf = nR - rv.size - lone.size
-    fill = shapes.filler_codes(info, nf + 3000, {q0}, 1)  # distinct: R takes the first nf
-    mid = np.concatenate([shapes.job_codes(info, q0, sub0, rv), fill[:nf]])
-    rng.shuffle(mid)
-    lc = shapes.job_codes(info, q0, sub0, lone)
-    Rc = np.concatenate([lc[:3], mid, lc[3:]])
-    sv = np.concatenate([np.full(40, 7), np.repeat([11, 12], 10), 1000 + np.arange(50)])
-    Sc = np.concatenate([shapes.job_codes(info, q0, sub0, sv), fill[nf - 3000:]])  # 3,000 of R's, 3,000 not
-    rng.shuffle(Sc)
-    R, S = _rel(crc.key_of(Rc), rng), _rel(crc.key_of(Sc), rng)
+    R, S, args, info = shapes.hot_r_key_across_pieces(
+        crc, _args(hw)[name], lambda nR: geometry(hw, cuda, _args(hw)[name], name, nR))
+    q0, sub0, hot = info["q0"], info["sub0"], info["hot"]
     same_geometry(hw, cuda, R, args, info)
     got, _ = check(hw, cuda, orc, R, S, args)
     jobk = crc.key_of(shapes.job_codes(info, q0, sub0, np.arange(3000)))
@@ -286,24 +242,9 @@ def test_more_descriptors_than_a_batch(hw, cuda, orc, crc, name):
     """A partition of kMatDesc * BSW * 32 + 1 R tuples (more than kMatDesc build sweeps: several R
     descriptor batches per job), 60,000 distinct keys repeated all over it; S has rows of 50,000 of
     them only, so R-only rows come from every descriptor batch."""
-    rng = np.random.default_rng(55)
-    args = _args(hw)[name]
-    q0, fill = 5, 20000
-    probe = geometry(hw, cuda, args, name, 8)
-    n_q = probe["m_desc"] * probe["BSW"] * 32 + 1
-    nR = n_q + fill
-    info = geometry(hw, cuda, args, name, nR)
-    assert (info["m_desc"], info["BSW"]) == (probe["m_desc"], probe["BSW"])
-    lf = info["F"].bit_length() - 1
-    hi = rng.choice(1 << min(32 - lf, 24), 66000, replace=False).astype(np.uint64)
-    qcodes = (np.uint64(q0) | (hi << np.uint64(lf))).astype(np.uint32)
-    member, absent = qcodes[:60000], qcodes[60000:]
-    Rc = np.concatenate([member[rng.integers(0, member.size, size=n_q)], shapes.filler_codes(info, fill, {q0}, 1)])
-    Sc = np.concatenate([member[rng.integers(0, 50000, size=3000)], absent[rng.integers(0, absent.size, size=3000)],
-                         Rc[n_q:n_q + 3000], shapes.filler_codes(info, 3000, {q0}, 777)])
-    rng.shuffle(Rc)
-    rng.shuffle(Sc)
-    R, S = _rel(crc.key_of(Rc), rng), _rel(crc.key_of(Sc), rng)
+    R, S, args, info = shapes.more_descriptors_than_a_batch(
+        crc, _args(hw)[name], lambda nR: geometry(hw, cuda, _args(hw)[name], name, nR))
+    n_q, member, Rc, Sc = info["n_q"], info["member"], info["Rc"], info["Sc"]
     got, _ = check(hw, cuda, orc, R, S, args)
     n_lone = int((~np.isin(Rc[np.isin(Rc, member)], Sc)).sum())
     assert n_lone > n_q // 2

@@ -96,11 +96,13 @@ for name, fn in cases:  # warm-up: code objects, buffers, clocks
     ms, _ = fn()
     print(f"warm-up {name}: {ms:.3f} ms", flush=True)
 times = {name: [] for name, _ in cases}
+joins = {name: [] for name, _ in cases}  # the join phase of every run
 phases = {}
 for r in range(reps):
     for name, fn in cases:
         ms, st = fn()
         times[name].append(ms)
+        joins[name].append(st.ms_join)
         phases[name] = st
         print(f"rep {r} {name}: {ms:.3f} ms", flush=True)
 nofilter = {}
@@ -119,6 +121,10 @@ for name, _ in cases:
     t = times[name]
     gb = bytes_moved(name, FILTERED) / 1e9 if name != "semi" else float("nan")
     lines.append(f"{name:14s} {med[name]:9.3f} {min(t):9.3f} {max(t):9.3f} {gb:9.2f} {gb / med[name] * 1e3:7.0f}")
+lines.append(f"{'join phase':14s} {'median':>9s} {'min':>9s} {'max':>9s}")
+for name, _ in cases:
+    j = joins[name]
+    lines.append(f"{name:14s} {statistics.median(j):9.3f} {min(j):9.3f} {max(j):9.3f}")
 for name, ms in nofilter.items():
     lines.append(f"{name + ' no filter':22s} {ms:9.3f} (one run after one warm-up)")
 for name, _ in cases:
