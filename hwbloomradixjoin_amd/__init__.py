@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_keys_device", "join_keys_device_async", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_keys_device", "join_keys_device_async", "join_keys_pairs_device", "semi_join_keys_device", "outer_join_keys_device", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -134,6 +134,16 @@ def lib() -> ctypes.CDLL:
         L.hwbrj_join_outer_device.argtypes = [
             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
+        L.hwbrj_join_keys_pairs_device.restype = ctypes.c_int
+        L.hwbrj_join_keys_pairs_device.argtypes = L.hwbrj_join_materialize_device.argtypes
+        L.hwbrj_join_keys_semi_device.restype = ctypes.c_int
+        L.hwbrj_join_keys_semi_device.argtypes = L.hwbrj_join_semi_device.argtypes
+        L.hwbrj_join_keys_outer_device.restype = ctypes.c_int
+        L.hwbrj_join_keys_outer_device.argtypes = [  # (hwbrj_join_outer_device's without null_payload)
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
             ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
         L.hwbrj_join_group_device.restype = ctypes.c_int
@@ -671,6 +681,107 @@ def outer_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = 
     _err(rc, "hwbrj_join_outer_device")
     stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
     return stats, out[: n.value], (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
+
+
+def _rows_out(call, what: str, capacity: int, n, device):
+    """The (n, 2) int32 rows of call(out_ptr, capacity), run again at the exact size when capacity
+    was too small (code 7, n = the full count)."""
+    import torch
+    for _ in range(2):
+        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=device)
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, what)
+    return out[: n.value]
+
+
+def join_keys_pairs_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None,
+                           capacity: Optional[int] = None):
+    """(Stats, pairs, ms): join_materialize_device on key columns (hwbrj_join_keys_pairs_device).
+    Rk, Sk are join_keys_device's columns; pairs is a (n, 2) int32 GPU tensor of {R row, S row},
+    unordered: the gather maps into the caller's other columns, exactly the pairs
+    join_materialize_device returns on {key, arange} tuples, without that interleaving pass. Both
+    columns must have fewer than 2^31 rows. The stream rule is join_keys_device's. capacity: output
+    rows to allocate (None: sized by a counting join_keys_device first; too small: the pipeline runs
+    again at the exact size)."""
+    _check_keys(Rk, Sk, stream)
+    if capacity is None:
+        capacity = join_keys_device(Rk, Sk, args, stream).matches
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n = ctypes.c_uint64()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_keys_pairs_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, out, cap,
+                                                  ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
+
+    out = _rows_out(call, "hwbrj_join_keys_pairs_device", capacity, n, Rk.device)
+    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_}), out, ms.value
+
+
+def semi_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, anti: bool = False, stream=None,
+                          capacity: Optional[int] = None):
+    """(Stats, rows, ms): semi_join_device on key columns (hwbrj_join_keys_semi_device). rows is a
+    (n, 2) int32 GPU tensor of {key, S row}, unordered: rows[:, 1] is the gather map of the S rows
+    whose key occurs in Rk (anti=True: does not occur). Stats, ms and capacity as in
+    semi_join_device (None: one count-only call first); columns and the stream rule as in
+    join_keys_device, fewer than 2^31 rows each."""
+    _check_keys(Rk, Sk, stream)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    kind = JOIN_ANTI if anti else JOIN_SEMI
+    n = ctypes.c_uint64()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_keys_semi_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, kind, out, cap,
+                                                 ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
+
+    if capacity is None:
+        rc = call(None, 0)  # count only
+        if rc not in (0, 7):
+            _err(rc, "hwbrj_join_keys_semi_device")
+        capacity = n.value
+    out = _rows_out(call, "hwbrj_join_keys_semi_device", capacity, n, Rk.device)
+    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_}), out, ms.value
+
+
+def outer_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, kind: int = OUTER_S, stream=None,
+                           capacity: Optional[int] = None):
+    """(Stats, rows, (n_inner, n_s_only, n_r_only), ms): outer_join_device on key columns
+    (hwbrj_join_keys_outer_device). rows is a (n, 2) int32 GPU tensor of {R row, S row}, unordered,
+    the missing side of an S-only or R-only row being -1 (a row index is never negative, so there is
+    no null_payload). Stats, the class counts, ms and capacity as in outer_join_device (None: one
+    count-only call first); columns and the stream rule as in join_keys_device, fewer than 2^31
+    rows each."""
+    _check_keys(Rk, Sk, stream)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n = ctypes.c_uint64()
+    cls = (ctypes.c_uint64 * 3)()
+    st = _Stats()
+    ms = ctypes.c_double()
+
+    def call(out, cap):
+        return lib().hwbrj_join_keys_outer_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, int(kind), out,
+                                                  cap, ctypes.byref(n), cls, sp, ctypes.byref(st), ctypes.byref(ms))
+
+    if capacity is None:
+        rc = call(None, 0)  # count only
+        if rc not in (0, 7):
+            _err(rc, "hwbrj_join_keys_outer_device")
+        capacity = n.value
+    out = _rows_out(call, "hwbrj_join_keys_outer_device", capacity, n, Rk.device)
+    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    return stats, out, (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
 
 
 GROUP_MATCHED, GROUP_ALL = 0, 1  # include/hwbrj.h HWBRJ_GROUP_MATCHED / _ALL

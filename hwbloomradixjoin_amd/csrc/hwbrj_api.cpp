@@ -256,23 +256,24 @@ int hwbrj_join_wait_all(hwbrj_stats_t* stats, int capacity, int* n_joins) {
 // The materializing join: the partitioned pipeline carrying payloads (Engine::run_mat); the
 // global-bitmap mode (basic k = 0 or B < 8) falls back to a counting join plus the side pass.
 // *n = all pairs (also beyond cap); *ms = the device time of the pairs' production.
-static int materialize_pairs(Engine* e, const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+// layout (here and in join_semi / join_outer below): SRC_TUPLES, or SRC_KEYS (d_R, d_S are int32 key
+// columns and every payload is the row index).
+static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                              const bloom_filter_args_t* args, tuple_t* d_out, uint64_t cap, uint64_t* n,
-                             hipStream_t stream, hwbrj_stats_t* st, double* ms) {
-    int rc = e->run_mat((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, stream,
-                        MatReq{(uint2*) d_out, cap}, st);
+                             hipStream_t stream, hwbrj_stats_t* st, double* ms, int layout = SRC_TUPLES) {
+    int rc = e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout);
     if (rc == 0) {
         *n = (uint64_t) st->matches;
         if (ms) *ms = st->ms_total;
         return 0;
     }
     if (rc != kRcMatGlobal) return rc;
-    rc = e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, stream, st);
+    rc = e->run(d_R, nR, d_S, nS, args, stream, st, 0, layout);
     if (rc) return rc;
     *n = (uint64_t) st->matches;
     if (*n > cap) return 0;  // (the caller reports the capacity)
     uint64_t m = 0;
-    rc = e->materialize((const uint2*) d_R, nR, (const uint2*) d_S, nS, (uint2*) d_out, cap, &m, stream, ms);
+    rc = e->materialize(d_R, nR, d_S, nS, (uint2*) d_out, cap, &m, stream, ms, layout);
     if (rc) return rc;
     if (m != *n) {
         set_last_error("materialized pairs differ from the counted matches");
@@ -281,16 +282,15 @@ static int materialize_pairs(Engine* e, const tuple_t* d_R, uint64_t nR, const t
     return 0;
 }
 
-int hwbrj_join_materialize_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
-                                  const bloom_filter_args_t* args, tuple_t* d_out,
-                                  uint64_t capacity, uint64_t* n_out, void* stream,
-                                  hwbrj_stats_t* stats, double* ms_materialize) {
+static int join_pairs(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
+                      const bloom_filter_args_t* args, tuple_t* d_out, uint64_t capacity, uint64_t* n_out,
+                      void* stream, hwbrj_stats_t* stats, double* ms_materialize, int layout) {
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
     hwbrj_stats_t st;
     uint64_t      n  = 0;
     const int     rc = materialize_pairs(e, d_R, nR, d_S, nS, args, d_out, capacity, &n, (hipStream_t) stream,
-                                         &st, ms_materialize);
+                                         &st, ms_materialize, layout);
     if (rc) return rc;
     if (stats) *stats = st;
     if (n_out) *n_out = n;
@@ -301,12 +301,42 @@ int hwbrj_join_materialize_device(const tuple_t* d_R, uint64_t nR, const tuple_t
     return 0;
 }
 
+int hwbrj_join_materialize_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                                  const bloom_filter_args_t* args, tuple_t* d_out,
+                                  uint64_t capacity, uint64_t* n_out, void* stream,
+                                  hwbrj_stats_t* stats, double* ms_materialize) {
+    return join_pairs(d_R, nR, d_S, nS, args, d_out, capacity, n_out, stream, stats, ms_materialize, SRC_TUPLES);
+}
+
+// Key columns with row indices as payloads (hwbrj_join_keys_pairs / _semi / _outer_device): the
+// columns' alignment rule, and rows that fit the int32 row index. Checked before any device call.
+static int keys_rows_ok(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, uint64_t nS) {
+    if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
+    if (nR >= (1ull << 31) || nS >= (1ull << 31)) {
+        set_last_error(std::string("key column ") + (nR >= (1ull << 31) ? "R" : "S") +
+                       " has 2^31 rows or more (row indices are int32)");
+        return 3;
+    }
+    return 0;
+}
+
+int hwbrj_join_keys_pairs_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, uint64_t nS,
+                                 const bloom_filter_args_t* args, tuple_t* d_out, uint64_t capacity,
+                                 uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
+    if (capacity > 0 && !d_out) {
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    return join_pairs(d_Rkeys, nR, d_Skeys, nS, args, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS);
+}
+
 // The existence join: the partitioned pipeline with S's payloads (Engine::run_semi); the
 // global-bitmap mode runs the counting join (its filter and its "S-tuples after filter") and the
 // existence side pass.
-int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
-                           const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
-                           uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
+static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
+                     const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
+                     uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms, int layout) {
     if (kind != HWBRJ_JOIN_SEMI && kind != HWBRJ_JOIN_ANTI) {  // (before any device call)
         set_last_error("unknown existence join kind (HWBRJ_JOIN_SEMI, HWBRJ_JOIN_ANTI)");
         return 2;
@@ -320,14 +350,14 @@ int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, 
     const SemiReq req{(uint2*) d_out, capacity, kind == HWBRJ_JOIN_ANTI};
     hwbrj_stats_t st;
     uint64_t      n  = 0;
-    int           rc = e->run_semi((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, req, &st);
+    int           rc = e->run_semi(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, layout);
     if (rc == 0) {
         n = (uint64_t) st.matches;
         if (ms) *ms = st.ms_total;
     } else if (rc == kRcMatGlobal) {
-        rc = e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, &st);
+        rc = e->run(d_R, nR, d_S, nS, args, (hipStream_t) stream, &st, 0, layout);
         if (rc) return rc;
-        rc = e->semi_side((const uint2*) d_R, nR, (const uint2*) d_S, nS, req, &n, (hipStream_t) stream, ms);
+        rc = e->semi_side(d_R, nR, d_S, nS, req, &n, (hipStream_t) stream, ms, layout);
         if (rc) return rc;
         st.matches = (int64_t) n;
     } else {
@@ -342,13 +372,26 @@ int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, 
     return 0;
 }
 
+int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                           const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
+                           uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
+    return join_semi(d_R, nR, d_S, nS, args, kind, d_out, capacity, n_out, stream, stats, ms, SRC_TUPLES);
+}
+
+int hwbrj_join_keys_semi_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, uint64_t nS,
+                                const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
+                                uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
+    return join_semi(d_Rkeys, nR, d_Skeys, nS, args, kind, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS);
+}
+
 // The outer join: the materializing pipeline with marks over S and matched flags over R
 // (Engine::run_outer); the global-bitmap mode runs the counting join (its filter and its "S-tuples
 // after filter") and the outer side pass.
-int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
-                            const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
-                            uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
-                            hwbrj_stats_t* stats, double* ms) {
+static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
+                      const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
+                      uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
+                      hwbrj_stats_t* stats, double* ms, int layout) {
     if (kind != HWBRJ_OUTER_S && kind != HWBRJ_OUTER_R && kind != HWBRJ_OUTER_FULL) {  // (before any device call)
         set_last_error("unknown outer join kind (HWBRJ_OUTER_S, HWBRJ_OUTER_R, HWBRJ_OUTER_FULL)");
         return 2;
@@ -363,14 +406,14 @@ int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
                        (uint32_t) null_payload};
     hwbrj_stats_t st;
     uint64_t      n = 0, cls[3] = {0, 0, 0};
-    int rc = e->run_outer((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, req, &st, cls);
+    int rc = e->run_outer(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, cls, layout);
     if (rc == 0) {
         n = (uint64_t) st.matches;
         if (ms) *ms = st.ms_total;
     } else if (rc == kRcMatGlobal) {
-        rc = e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, &st);
+        rc = e->run(d_R, nR, d_S, nS, args, (hipStream_t) stream, &st, 0, layout);
         if (rc) return rc;
-        rc = e->outer_side((const uint2*) d_R, nR, (const uint2*) d_S, nS, req, &n, cls, (hipStream_t) stream, ms);
+        rc = e->outer_side(d_R, nR, d_S, nS, req, &n, cls, (hipStream_t) stream, ms, layout);
         if (rc) return rc;
         st.matches = (int64_t) n;
     } else {
@@ -385,6 +428,24 @@ int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
         return 7;
     }
     return 0;
+}
+
+int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+                            const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
+                            uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
+                            hwbrj_stats_t* stats, double* ms) {
+    return join_outer(d_R, nR, d_S, nS, args, kind, null_payload, d_out, capacity, n_out, n_class, stream, stats, ms,
+                      SRC_TUPLES);
+}
+
+// (the missing side of a row is -1: a row index is never negative)
+int hwbrj_join_keys_outer_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, uint64_t nS,
+                                 const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
+                                 uint64_t* n_out, uint64_t* n_class, void* stream, hwbrj_stats_t* stats,
+                                 double* ms) {
+    if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
+    return join_outer(d_Rkeys, nR, d_Skeys, nS, args, kind, -1, d_out, capacity, n_out, n_class, stream, stats, ms,
+                      SRC_KEYS);
 }
 
 // The group join: the materializing pipeline up to the join, then per-R-tuple accumulators instead of

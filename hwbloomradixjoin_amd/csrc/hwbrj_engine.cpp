@@ -353,24 +353,24 @@ int Engine::reserve(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
     return rc;
 }
 
-int Engine::run_mat(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+int Engine::run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
-                    hwbrj_stats_t* st) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, &mat);
+                    hwbrj_stats_t* st, int layout) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, &mat, nullptr, nullptr, nullptr, layout);
     return rc ? rc : wait(st);
 }
 
-int Engine::run_semi(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+int Engine::run_semi(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                      const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
-                     hwbrj_stats_t* st) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, &semi);
+                     hwbrj_stats_t* st, int layout) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, &semi, nullptr, nullptr, layout);
     return rc ? rc : wait(st);
 }
 
-int Engine::run_outer(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+int Engine::run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                       const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
-                      hwbrj_stats_t* st, uint64_t cls[3]) {
-    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, &outer);
+                      hwbrj_stats_t* st, uint64_t cls[3], int layout) {
+    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, &outer, nullptr, layout);
     if (rc == 0) rc = wait(st);
     if (rc) return rc;
     uint64_t c[2];  // (the join has completed; its ring slot is taken again by the next enqueue only)
@@ -395,9 +395,10 @@ int Engine::run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS
 // mat / semi / outer / group: the payload-carrying pipeline (pl below). mat carries both relations'
 // payloads, and so do outer and group (from the join on they have kernels of their own); semi only
 // S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
-// layout: what dR and dS point to, SRC_TUPLES or SRC_KEYS (key columns: the counting join only).
-// It selects the kernels that read the relations; the partition words, and so everything from the
-// pools on, do not depend on it.
+// layout: what dR and dS point to, SRC_TUPLES or SRC_KEYS (key columns: the counting join, and mat /
+// semi / outer with the row index as the payload; not group, whose aggregates of row indices mean
+// nothing). It selects the kernels that read the relations; the partition words and payloads, and so
+// everything from the pools on, do not depend on it.
 int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                     const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group,
@@ -413,9 +414,13 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     Geometry    g;
     std::string err;
     const bool  pl = mat || semi;  // S payloads beside the words, the materializing geometry
-    if (layout != SRC_TUPLES && (layout != SRC_KEYS || pl)) {
-        set_last_error("key columns: the counting join only");
+    if (layout != SRC_TUPLES && (layout != SRC_KEYS || group)) {
+        set_last_error("key columns: the counting, pair, existence and outer joins only");
         return 2;
+    }
+    if (layout == SRC_KEYS && pl && (nR >= (1ull << 31) || nS >= (1ull << 31))) {  // (hwbrj_api.cpp refuses first)
+        set_last_error("key columns: row indices are int32 (|R|, |S| < 2^31)");
+        return 3;
     }
     if (!plan_geometry(args, nR, &g, &err, pl)) {
         set_last_error(err);
@@ -1414,8 +1419,8 @@ int Engine::tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t*
     return 0;
 }
 
-int Engine::materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, uint2* out,
-                        uint64_t cap, uint64_t* n, hipStream_t stream, double* ms) {
+int Engine::materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
+                        uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout) {
     HWBRJ_CHECK(hipSetDevice(device_));
     if (!stream) stream = own_stream_;
     uint64_t T = 2;
@@ -1427,11 +1432,11 @@ int Engine::materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t 
     HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
     HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 8, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
     if (nR && nS) {
         Geometry g = last_g_;  // the counting join's filter (materialize follows it)
         if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_mat_probe(dS, nS, dR, mtab.as<unsigned long long>(), T - 1, out, cap,
+        launch_mat_probe(dS, layout, nS, dR, mtab.as<unsigned long long>(), T - 1, out, cap,
                          mcount.as<unsigned long long>(), g, slices.as<uint32_t>(),
                          bitmap.as<uint32_t>(), d_tabs_, stream);
     }
@@ -1447,8 +1452,8 @@ int Engine::materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t 
     return 0;
 }
 
-int Engine::outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const OuterReq& outer,
-                       uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms) {
+int Engine::outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
+                       uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout) {
     HWBRJ_CHECK(hipSetDevice(device_));
     if (!stream) stream = own_stream_;
     uint64_t T = 2;
@@ -1463,17 +1468,17 @@ int Engine::outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t n
     HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 24, stream));
     if (outer.keep_r) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, fbytes, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
     uint32_t* rflag = outer.keep_r ? smark.as<uint32_t>() : nullptr;
     if (nS) {
         Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
         if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_outer_probe(dS, nS, dR, mtab.as<unsigned long long>(), T - 1, outer.keep_s ? 1u : 0u,
+        launch_outer_probe(dS, layout, nS, dR, mtab.as<unsigned long long>(), T - 1, outer.keep_s ? 1u : 0u,
                            outer.null_pay, rflag, outer.out, outer.cap, mcount.as<unsigned long long>(), g,
                            slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_, stream);
     }
     if (outer.keep_r && nR)
-        launch_outer_rtab(dR, mtab.as<unsigned long long>(), T, rflag, outer.null_pay, outer.out, outer.cap,
+        launch_outer_rtab(dR, layout, mtab.as<unsigned long long>(), T, rflag, outer.null_pay, outer.out, outer.cap,
                           mcount.as<unsigned long long>(), stream);
     HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
     HWBRJ_CHECK(hipGetLastError());
@@ -1512,7 +1517,7 @@ int Engine::group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t n
     if (minmax) launch_group_minmax_init(gmin.as<int32_t>(), gmax.as<int32_t>(), rows, stream);
     else HWBRJ_CHECK(hipMemsetAsync(gsum.p, 0, rows * 8, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nR) launch_mat_build(dR, SRC_TUPLES, nR, mtab.as<unsigned long long>(), T - 1, stream);
     if (nR && nS) {
         Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
         if (!have_filter_) g.mode = MODE_NOBLOOM;
@@ -1546,8 +1551,8 @@ int Engine::group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t n
     return 0;
 }
 
-int Engine::semi_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const SemiReq& semi,
-                      uint64_t* n, hipStream_t stream, double* ms) {
+int Engine::semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
+                      uint64_t* n, hipStream_t stream, double* ms, int layout) {
     HWBRJ_CHECK(hipSetDevice(device_));
     if (!stream) stream = own_stream_;
     uint64_t T = 2;
@@ -1559,11 +1564,11 @@ int Engine::semi_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS
     HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
     HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 8, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
     if (nS) {
         Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
         if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_semi_probe(dS, nS, mtab.as<unsigned long long>(), T - 1, semi.anti ? 1u : 0u, semi.out, semi.cap,
+        launch_semi_probe(dS, layout, nS, mtab.as<unsigned long long>(), T - 1, semi.anti ? 1u : 0u, semi.out, semi.cap,
                           mcount.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(),
                           d_tabs_, stream);
     }

@@ -130,21 +130,23 @@ class Engine {
     int  tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t* bytes);
     // The materializing join (the partitioned pipeline carrying payloads): st->matches = pairs
     // (all of them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
-    int  run_mat(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+    // layout (here, run_semi, run_outer and their side passes): SRC_TUPLES, or SRC_KEYS: key columns
+    // as in run(), every element's payload its row index (|R|, |S| < 2^31). run_group: tuples only.
+    int  run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                  const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
-                 hwbrj_stats_t* st);
+                 hwbrj_stats_t* st, int layout = SRC_TUPLES);
     // The existence join (semi / anti) on the materializing pipeline's geometry: S carries its
     // payloads, R does not (k_join_semi, and k_semi_emit for anti). st->matches = rows (all of
     // them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
-    int  run_semi(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+    int  run_semi(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                   const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
-                  hwbrj_stats_t* st);
+                  hwbrj_stats_t* st, int layout = SRC_TUPLES);
     // The outer join on the materializing pipeline (both payloads; k_join_outer, and k_outer_emit
     // when S is preserved). st->matches = rows (all of them, also beyond cap); cls = {inner, S-only,
     // R-only} rows. kRcMatGlobal: not for the global-bitmap mode.
-    int  run_outer(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+    int  run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
-                   hwbrj_stats_t* st, uint64_t cls[3]);
+                   hwbrj_stats_t* st, uint64_t cls[3], int layout = SRC_TUPLES);
     // The group join on the materializing pipeline up to the join, then k_join_group. st->matches =
     // rows (all of them, also beyond cap); *pairs = the sum of their counts. kRcMatGlobal: not for the
     // global-bitmap mode.
@@ -155,15 +157,15 @@ class Engine {
     int  group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const GroupReq& group,
                     uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms);
     // Its side pass after a counting join (global-bitmap mode): *n = rows, cls as above.
-    int  outer_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const OuterReq& outer,
-                    uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms);
+    int  outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
+                    uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout = SRC_TUPLES);
     // Its side pass after a counting join (global-bitmap mode): *n = number of rows.
-    int  semi_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const SemiReq& semi,
-                   uint64_t* n, hipStream_t stream, double* ms);
+    int  semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
+                   uint64_t* n, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
     // Side pass after a counting join (global-bitmap mode): (R.payload, S.payload) of every match
     // into out[0, cap); *n = number of pairs.
-    int  materialize(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, uint2* out,
-                     uint64_t cap, uint64_t* n, hipStream_t stream, double* ms);
+    int  materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
+                     uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
     int  generate(uint2* d_out, uint64_t n, uint64_t offset, uint64_t count, uint32_t nthreads,
                   uint64_t maxid, uint64_t threshold, double selectivity, uint64_t seed,
                   hipStream_t stream);

@@ -209,8 +209,10 @@ struct SemiEmitParams {
 };
 void   launch_semi_emit(const SemiEmitParams& p, uint32_t grid, hipStream_t st);
 // the existence join's side pass (global-bitmap mode): every S tuple against launch_mat_build's
-// table of R, stopping at the first hit; rows {key, payload} on a hit (anti = 0) or on none
-void   launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
+// table of R, stopping at the first hit; rows {key, payload} on a hit (anti = 0) or on none.
+// src (the side passes: here, launch_outer_probe / _rtab, launch_mat_build / _probe): SRC_TUPLES, or
+// SRC_KEYS: uint32 keys whose payload is the row index
+void   launch_semi_probe(const void* S, int src, uint64_t n, const unsigned long long* tab, uint64_t mask,
                          uint32_t anti, uint2* out, uint64_t cap, unsigned long long* count,
                          const Geometry& g, const uint32_t* slices, const uint32_t* bm,
                          const CrcTables* tabs, hipStream_t st);
@@ -249,12 +251,13 @@ void   launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st
 // without a partner (keep_s), and a bit per table slot that was hit (rflag, or nullptr);
 // cnt[0] += rows, cnt[1] += S-only rows. launch_outer_rtab then writes {R.payload, null_pay} of the
 // table's unflagged entries; cnt[0] and cnt[2] += those rows.
-void   launch_outer_probe(const uint2* S, uint64_t n, const uint2* R, const unsigned long long* tab,
+void   launch_outer_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab,
                           uint64_t mask, uint32_t keep_s, uint32_t null_pay, uint32_t* rflag, uint2* out,
                           uint64_t cap, unsigned long long* cnt, const Geometry& g, const uint32_t* slices,
                           const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
-void   launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
-                         uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st);
+void   launch_outer_rtab(const void* R, int src, const unsigned long long* tab, uint64_t slots,
+                         const uint32_t* rflag, uint32_t null_pay, uint2* out, uint64_t cap,
+                         unsigned long long* cnt, hipStream_t st);
 
 // The group join (k_join_group): the materializing join's inputs (m; m.out is not used), no pairs.
 // Every R tuple of a job accumulates, in LDS, the number of the job's survivors with its key and the
@@ -354,10 +357,10 @@ struct PathConstants {
 PathConstants path_constants();
 void   launch_join_mat(const MatJoinParams& p, uint32_t jobs, hipStream_t st);
 // result materialization (K12): R table build, S probe writing (R.payload, S.payload) pairs
-void   launch_mat_build(const uint2* R, uint64_t n, unsigned long long* tab, uint64_t mask,
+void   launch_mat_build(const void* R, int src, uint64_t n, unsigned long long* tab, uint64_t mask,
                         hipStream_t st);
 // g/slices/bm/tabs: the last join's filter, used as a pre-test (g.mode = MODE_NOBLOOM: none)
-void   launch_mat_probe(const uint2* S, uint64_t n, const uint2* R, const unsigned long long* tab,
+void   launch_mat_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab,
                         uint64_t mask, uint2* out, uint64_t cap, unsigned long long* count,
                         const Geometry& g, const uint32_t* slices, const uint32_t* bm,
                         const CrcTables* tabs, hipStream_t st);

@@ -340,6 +340,12 @@ __device__ __forceinline__ bool global_contains(uint32_t key, uint32_t code, con
 // k_probe_global and k_bitpos are instantiated for both.
 __device__ __forceinline__ uint32_t elem_key(const uint2& t) { return t.x; }
 __device__ __forceinline__ uint32_t elem_key(uint32_t k) { return k; }
+// the payload of element i of a relation: the tuple's own, or a key column's row index (i < 2^31)
+__device__ __forceinline__ uint32_t elem_pay(const uint2& t, uint64_t) { return t.y; }
+__device__ __forceinline__ uint32_t elem_pay(uint32_t, uint64_t i) { return (uint32_t) i; }
+// element i as {key, payload}
+__device__ __forceinline__ uint2 elem_tuple(const uint2& t, uint64_t) { return t; }
+__device__ __forceinline__ uint2 elem_tuple(uint32_t k, uint64_t i) { return make_uint2(k, elem_pay(k, i)); }
 
 template <class T>
 __global__ __launch_bounds__(256) void k_build_global(const T* R, uint64_t n, Geometry g,
@@ -889,8 +895,21 @@ constexpr int      kScKP     = HWBRJ_SC_KP;  // flush tasks per thread per round
                                              // words + of payloads); ~512 halves per round on average
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 
-template <int MODE, int FMT>
+template <int SRC>
+struct ScPayRaw {  // one round's raw loads of this thread: {key, payload} tuples, or a key column's keys
+    v2u      t[SRC == SRC_TUPLES ? kScE : 1];
+    uint32_t k[SRC == SRC_KEYS ? kScE : 1];
+};
+
+// SRC: SRC_TUPLES, or SRC_KEYS: a key column whose payloads are the row indices (element i of the
+// relation carries payload i, computed from the index that addressed its load and never read).
+// One round of loads in flight in both: the kernel sits at the 128 VGPRs its one 1024-thread
+// workgroup per CU allows, and a second round of key loads spills (DESIGN "Key columns: row-index joins").
+template <int SRC, int MODE, int FMT>
 __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
+    static_assert(SRC == SRC_TUPLES || SRC == SRC_KEYS, "tuples or a key column");
+    static_assert(kScE % 4 == 0 && kScPayThreads == kScThreads, "four keys per 16-byte load");
+    constexpr uint32_t EB = SRC == SRC_KEYS ? 4u : 8u;  // bytes per element
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ uint32_t crc_tab[128];
     const uint32_t F     = 1u << P.g.log2F;
@@ -931,23 +950,46 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     const uint64_t e1  = e1r < n ? e1r : n;
     const uint32_t len = __builtin_amdgcn_readfirstlane(e1 > e0 ? (uint32_t) (e1 - e0) : 0u);
     uint16_t* __restrict__ meta = (uint16_t*) P.meta + wg * P.cap;
-    const auto rsrc   = buf_rsrc((const uint8_t*) P.src + e0 * 8, len * 8);  // OOB loads return 0
+    const auto rsrc   = buf_rsrc((const uint8_t*) P.src + e0 * EB, len * EB);  // OOB loads return 0
     const auto rpool  = buf_rsrc(P.pool + wg * P.cap * 32, (uint32_t) (P.cap * 128));
     const auto rppool = buf_rsrc(P.ppool + wg * P.cap * 32, (uint32_t) (P.cap * 128));
     const auto rmeta  = buf_rsrc(meta, (uint32_t) (P.cap * 2));
     __syncthreads();
 
     auto hword = [&](uint32_t H) { return H * 16u; };  // word offset of half H in the region
-    auto load_round = [&](uint32_t base, v2u (&R)[kScE]) {  // {key, payload} as one 8-byte load
-        if (base + kScRound <= len) {
+    // element j of this thread in the round at `base`: its index inside the workgroup's range.
+    // SRC_KEYS: four consecutive keys per thread and load (scatter_body's SRC_KEYS shape); the index
+    // addresses the load and, added to e0, is the element's payload (its row).
+    auto eidx = [&](uint32_t base, int j) -> uint32_t {
+        if (SRC == SRC_KEYS) return base + (j >> 2) * 4 * kScPayThreads + 4 * tid + (j & 3);
+        return base + j * kScPayThreads + tid;
+    };
+    const uint32_t row0 = (uint32_t) e0;  // (rows < 2^31: hwbrj_join_keys_*_device)
+    auto load_round = [&](uint32_t base, ScPayRaw<SRC>& R) {
+        if (SRC == SRC_KEYS && base + kScRound <= len) {  // four keys per 16-byte load: eidx(base, 4 h .. 4 h + 3)
+#pragma unroll
+            for (int h = 0; h < kScE / 4; h++) {
+                const v4u x = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 4 * tid * EB, (base + h * 4 * kScPayThreads) * EB, HWBRJ_SC_LAUX);
+                R.k[4 * h]     = x.x;
+                R.k[4 * h + 1] = x.y;
+                R.k[4 * h + 2] = x.z;
+                R.k[4 * h + 3] = x.w;
+            }
+        } else if (SRC == SRC_KEYS) {
+#pragma unroll
+            for (int j = 0; j < kScE; j++) {
+                const uint32_t i = eidx(base, j);
+                R.k[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, i < len ? i * EB : kOob, 0, 0);
+            }
+        } else if (base + kScRound <= len) {  // {key, payload} as one 8-byte load
 #pragma unroll
             for (int j = 0; j < kScE; j++)
-                R[j] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, tid * 8, (base + j * kScPayThreads) * 8, 0);
+                R.t[j] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, tid * 8, (base + j * kScPayThreads) * 8, 0);
         } else {
 #pragma unroll
             for (int j = 0; j < kScE; j++) {
                 const uint32_t i = base + j * kScPayThreads + tid;
-                R[j] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, i < len ? i * 8 : kOob, 0, 0);
+                R.t[j] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, i < len ? i * 8 : kOob, 0, 0);
             }
         }
     };
@@ -1007,21 +1049,21 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         for (int j = 0; j < kScE; j++) stg[ps[j]] = make_uint2(pw[j], pp[j]);
     };
 
-    v2u RA[kScE];
+    ScPayRaw<SRC> RA;
     load_round(0, RA);
     auto round = [&](uint32_t base) {
         const bool full = base + kScRound <= len;  // uniform
         uint32_t   q[kScE], w[kScE], p[kScE];
 #pragma unroll
         for (int j = 0; j < kScE; j++) {
-            sc_word_lds0<SRC_TUPLES, MODE, FMT>(RA[j].x, P.g, crc_tab, w[j], q[j]);
-            p[j] = RA[j].y;
+            sc_word_lds0<SRC, MODE, FMT>(SRC == SRC_KEYS ? RA.k[j] : RA.t[j].x, P.g, crc_tab, w[j], q[j]);
+            p[j] = SRC == SRC_KEYS ? row0 + eidx(base, j) : RA.t[j].y;
             if ((j % HWBRJ_SC_SB) == HWBRJ_SC_SB - 1) __builtin_amdgcn_sched_barrier(0);
         }
         if (!full) {
 #pragma unroll
             for (int j = 0; j < kScE; j++)
-                if (base + j * kScPayThreads + tid >= len) q[j] = F;  // invalid: ranked on the dummy counter
+                if (eidx(base, j) >= len) q[j] = F;  // invalid: ranked on the dummy counter
         }
         load_round(base + kScRound, RA);
         flush_copy();
@@ -3413,13 +3455,14 @@ __device__ __forceinline__ uint32_t mat_slot(uint32_t key, uint64_t mask) {
     return (uint32_t) (mix32(key * 0x9E3779B1u + 0x7F4A7C15u) & mask);
 }
 
-__global__ __launch_bounds__(256) void k_mat_build(const uint2* __restrict__ R, uint64_t n,
+template <class T>  // (uint2 tuples or uint32_t keys, as k_build_global; the side-pass kernels below alike)
+__global__ __launch_bounds__(256) void k_mat_build(const T* __restrict__ R, uint64_t n,
                                                     unsigned long long* __restrict__ tab,
                                                     uint64_t mask) {
     uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        const uint32_t           key = R[i].x;
+        const uint32_t           key = elem_key(R[i]);
         const unsigned long long e   = ((unsigned long long) (i + 1) << 32) | key;
         uint64_t                 h   = mat_slot(key, mask);
         while (atomicCAS(&tab[h], 0ull, e) != 0ull) h = (h + 1) & mask;
@@ -3468,8 +3511,9 @@ __device__ __forceinline__ bool mat_filter(uint32_t key, const Geometry& g, cons
 
 constexpr uint32_t kMatBuf = 4096;  // pairs staged in LDS per workgroup before one output atomic
 
-__global__ __launch_bounds__(256) void k_mat_probe(const uint2* __restrict__ S, uint64_t n,
-                                                    const uint2* __restrict__ R,
+template <class T>
+__global__ __launch_bounds__(256) void k_mat_probe(const T* __restrict__ S, uint64_t n,
+                                                    const T* __restrict__ R,
                                                     const unsigned long long* __restrict__ tab,
                                                     uint64_t mask, uint2* __restrict__ out,
                                                     uint64_t cap, unsigned long long* __restrict__ count,
@@ -3498,13 +3542,13 @@ __global__ __launch_bounds__(256) void k_mat_probe(const uint2* __restrict__ S, 
     for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
         const uint64_t i  = t0 + threadIdx.x;
         if (i < e1) {
-            const uint2 st = S[i];
+            const uint2 st = elem_tuple(S[i], i);
             if (mat_filter(st.x, g, slices, bm, tabs)) {
                 for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
                     const unsigned long long e = tab[h];
                     if (e == 0ull) break;
                     if ((uint32_t) e != st.x) continue;
-                    const uint2    pr   = make_uint2(R[(e >> 32) - 1].y, st.y);  // (R rid, S rid)
+                    const uint2    pr   = make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), st.y);  // (R rid, S rid)
                     const uint32_t slot = atomicAdd(&nbuf, 1u);
                     if (slot < kMatBuf) {
                         buf[slot] = pr;
@@ -3521,15 +3565,21 @@ __global__ __launch_bounds__(256) void k_mat_probe(const uint2* __restrict__ S, 
     flush();
 }
 
-void launch_mat_build(const uint2* R, uint64_t n, unsigned long long* tab, uint64_t mask, hipStream_t st) {
-    k_mat_build<<<8192, 256, 0, st>>>(R, n, tab, mask);
+void launch_mat_build(const void* R, int src, uint64_t n, unsigned long long* tab, uint64_t mask, hipStream_t st) {
+    if (src == SRC_KEYS) k_mat_build<uint32_t><<<8192, 256, 0, st>>>((const uint32_t*) R, n, tab, mask);
+    else k_mat_build<uint2><<<8192, 256, 0, st>>>((const uint2*) R, n, tab, mask);
 }
 
-void launch_mat_probe(const uint2* S, uint64_t n, const uint2* R, const unsigned long long* tab,
+void launch_mat_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab,
                       uint64_t mask, uint2* out, uint64_t cap, unsigned long long* count,
                       const Geometry& g, const uint32_t* slices, const uint32_t* bm,
                       const CrcTables* tabs, hipStream_t st) {
-    k_mat_probe<<<2048, 256, 0, st>>>(S, n, R, tab, mask, out, cap, count, g, slices, bm, tabs);
+    if (src == SRC_KEYS)
+        k_mat_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, (const uint32_t*) R, tab, mask, out, cap,
+                                                    count, g, slices, bm, tabs);
+    else
+        k_mat_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, (const uint2*) R, tab, mask, out, cap, count, g,
+                                                 slices, bm, tabs);
 }
 
 // ================================= K13: partitioned multi-GPU join (R and survivors exchanged)
@@ -4269,7 +4319,8 @@ void launch_semi_emit(const SemiEmitParams& p, uint32_t grid, hipStream_t st) {
 // The side pass of the global-bitmap mode (k_mat_probe's existence form): the walk of R's table
 // stops at the first hit; a tuple the filter rejects is a certain miss. Rows are staged in LDS and
 // appended with one atomic per flush (the stage always has room for a round of the workgroup).
-__global__ __launch_bounds__(256) void k_semi_probe(const uint2* __restrict__ S, uint64_t n,
+template <class T>
+__global__ __launch_bounds__(256) void k_semi_probe(const T* __restrict__ S, uint64_t n,
                                                      const unsigned long long* __restrict__ tab,
                                                      uint64_t mask, uint32_t anti, uint2* __restrict__ out,
                                                      uint64_t cap, unsigned long long* __restrict__ count,
@@ -4295,7 +4346,7 @@ __global__ __launch_bounds__(256) void k_semi_probe(const uint2* __restrict__ S,
     for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
         const uint64_t i = t0 + threadIdx.x;
         if (i < e1) {
-            const uint2 st  = S[i];
+            const uint2 st  = elem_tuple(S[i], i);
             uint32_t    hit = 0;
             if (mat_filter(st.x, g, slices, bm, tabs))
                 for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
@@ -4314,10 +4365,13 @@ __global__ __launch_bounds__(256) void k_semi_probe(const uint2* __restrict__ S,
     flush();
 }
 
-void launch_semi_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask, uint32_t anti,
+void launch_semi_probe(const void* S, int src, uint64_t n, const unsigned long long* tab, uint64_t mask, uint32_t anti,
                        uint2* out, uint64_t cap, unsigned long long* count, const Geometry& g,
                        const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
-    k_semi_probe<<<2048, 256, 0, st>>>(S, n, tab, mask, anti, out, cap, count, g, slices, bm, tabs);
+    if (src == SRC_KEYS)
+        k_semi_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, tab, mask, anti, out, cap, count, g, slices,
+                                                     bm, tabs);
+    else k_semi_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, tab, mask, anti, out, cap, count, g, slices, bm, tabs);
 }
 
 // ================================================================= K10o: the outer join
@@ -4414,8 +4468,9 @@ void launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st) 
 // The outer join's side pass (global-bitmap mode), k_mat_probe's outer form: the rows of an S tuple
 // are its pairs, or {null, S.payload} when it has none (a tuple the filter rejects has none); a hit
 // table slot gets its bit in rflag. Rows are staged in LDS as in k_mat_probe.
-__global__ __launch_bounds__(256) void k_outer_probe(const uint2* __restrict__ S, uint64_t n,
-                                                      const uint2* __restrict__ R,
+template <class T>
+__global__ __launch_bounds__(256) void k_outer_probe(const T* __restrict__ S, uint64_t n,
+                                                      const T* __restrict__ R,
                                                       const unsigned long long* __restrict__ tab,
                                                       uint64_t mask, uint32_t keep_s, uint32_t null_pay,
                                                       uint32_t* __restrict__ rflag, uint2* __restrict__ out,
@@ -4451,7 +4506,7 @@ __global__ __launch_bounds__(256) void k_outer_probe(const uint2* __restrict__ S
     for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
         const uint64_t i = t0 + threadIdx.x;
         if (i < e1) {
-            const uint2 st  = S[i];
+            const uint2 st  = elem_tuple(S[i], i);
             bool        any = false;
             if (mat_filter(st.x, g, slices, bm, tabs)) {
                 for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
@@ -4460,7 +4515,7 @@ __global__ __launch_bounds__(256) void k_outer_probe(const uint2* __restrict__ S
                     if ((uint32_t) e != st.x) continue;
                     any = true;
                     if (rflag) atomicOr(&rflag[h >> 5], 1u << (h & 31u));
-                    push(make_uint2(R[(e >> 32) - 1].y, st.y));
+                    push(make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), st.y));
                 }
             }
             if (!any && keep_s) {
@@ -4476,7 +4531,8 @@ __global__ __launch_bounds__(256) void k_outer_probe(const uint2* __restrict__ S
 }
 
 // {R.payload, null} of the table's entries whose slot no S tuple hit, staged like k_semi_probe's rows
-__global__ __launch_bounds__(256) void k_outer_rtab(const uint2* __restrict__ R,
+template <class T>
+__global__ __launch_bounds__(256) void k_outer_rtab(const T* __restrict__ R,
                                                      const unsigned long long* __restrict__ tab, uint64_t slots,
                                                      const uint32_t* __restrict__ rflag, uint32_t null_pay,
                                                      uint2* __restrict__ out, uint64_t cap,
@@ -4504,8 +4560,8 @@ __global__ __launch_bounds__(256) void k_outer_rtab(const uint2* __restrict__ R,
         const uint64_t h = t0 + threadIdx.x;
         if (h < e1) {
             const unsigned long long e = tab[h];
-            if (e != 0ull && !((rflag[h >> 5] >> (h & 31u)) & 1u))
-                buf[atomicAdd(&nbuf, 1u)] = make_uint2(R[(e >> 32) - 1].y, null_pay);  // (nbuf + 256 <= kMatBuf)
+            if (e != 0ull && !((rflag[h >> 5] >> (h & 31u)) & 1u))  // (nbuf + 256 <= kMatBuf)
+                buf[atomicAdd(&nbuf, 1u)] = make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), null_pay);
         }
         __syncthreads();
         if (nbuf > kMatBuf - 256) flush();  // uniform (read after the barrier)
@@ -4513,17 +4569,23 @@ __global__ __launch_bounds__(256) void k_outer_rtab(const uint2* __restrict__ R,
     flush();
 }
 
-void launch_outer_probe(const uint2* S, uint64_t n, const uint2* R, const unsigned long long* tab, uint64_t mask,
+void launch_outer_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab, uint64_t mask,
                         uint32_t keep_s, uint32_t null_pay, uint32_t* rflag, uint2* out, uint64_t cap,
                         unsigned long long* cnt, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
                         const CrcTables* tabs, hipStream_t st) {
-    k_outer_probe<<<2048, 256, 0, st>>>(S, n, R, tab, mask, keep_s, null_pay, rflag, out, cap, cnt, g, slices, bm,
-                                        tabs);
+    if (src == SRC_KEYS)
+        k_outer_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, (const uint32_t*) R, tab, mask, keep_s,
+                                                      null_pay, rflag, out, cap, cnt, g, slices, bm, tabs);
+    else
+        k_outer_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, (const uint2*) R, tab, mask, keep_s, null_pay,
+                                                   rflag, out, cap, cnt, g, slices, bm, tabs);
 }
 
-void launch_outer_rtab(const uint2* R, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
+void launch_outer_rtab(const void* R, int src, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
                        uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st) {
-    k_outer_rtab<<<2048, 256, 0, st>>>(R, tab, slots, rflag, null_pay, out, cap, cnt);
+    if (src == SRC_KEYS)
+        k_outer_rtab<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) R, tab, slots, rflag, null_pay, out, cap, cnt);
+    else k_outer_rtab<uint2><<<2048, 256, 0, st>>>((const uint2*) R, tab, slots, rflag, null_pay, out, cap, cnt);
 }
 
 // ================================================================= K10g: the group join
@@ -4895,29 +4957,40 @@ size_t scatter_pay_lds_bytes(uint32_t log2F) {
     return (2 * (F * kPayDepth + 64) + F + 4 + 5 * F + 8) * sizeof(uint32_t);  // (+512 B static)
 }
 
-template <int MODE, int FMT>
-__global__ __launch_bounds__(kScPayThreads) void k_scatter_rp(ScatterParams P) { scatter_body_pay<MODE, FMT>(P); }
-template <int MODE, int FMT>
-__global__ __launch_bounds__(kScPayThreads) void k_scatter_sp(ScatterParams P) { scatter_body_pay<MODE, FMT>(P); }
+template <int SRC, int MODE, int FMT>
+__global__ __launch_bounds__(kScPayThreads) void k_scatter_rp(ScatterParams P) { scatter_body_pay<SRC, MODE, FMT>(P); }
+template <int SRC, int MODE, int FMT>
+__global__ __launch_bounds__(kScPayThreads) void k_scatter_sp(ScatterParams P) { scatter_body_pay<SRC, MODE, FMT>(P); }
 
-template <int MODE, int FMT>
+template <int SRC, int MODE, int FMT>
 static void scatter_pay_inst(const ScatterParams& p, int side, uint32_t grid, hipStream_t st) {
     const size_t lds = scatter_pay_lds_bytes(p.g.log2F);
-    const void*  fn  = side == SIDE_R ? (const void*) &k_scatter_rp<MODE, FMT> : (const void*) &k_scatter_sp<MODE, FMT>;
+    const void*  fn  = side == SIDE_R ? (const void*) &k_scatter_rp<SRC, MODE, FMT> : (const void*) &k_scatter_sp<SRC, MODE, FMT>;
     (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-    if (side == SIDE_R) k_scatter_rp<MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
-    else k_scatter_sp<MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
+    if (side == SIDE_R) k_scatter_rp<SRC, MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
+    else k_scatter_sp<SRC, MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
 }
 
 void launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hipStream_t st) {
     const Geometry& g = p.g;
+    if (p.ppool && src == SRC_KEYS) {  // a key column, its row indices as payloads: the modes of the tuples below
+        switch (g.mode) {
+            case MODE_SLICE_BLOCK:
+                if (g.format == FMT_PACKED)
+                    return scatter_pay_inst<SRC_KEYS, MODE_SLICE_BLOCK, FMT_PACKED>(p, side, grid, st);
+                return scatter_pay_inst<SRC_KEYS, MODE_SLICE_BLOCK, FMT_CODE>(p, side, grid, st);
+            case MODE_SLICE_BASIC: return scatter_pay_inst<SRC_KEYS, MODE_SLICE_BASIC, FMT_CODE>(p, side, grid, st);
+            default: return scatter_pay_inst<SRC_KEYS, MODE_NOBLOOM, FMT_CODE>(p, side, grid, st);
+        }
+    }
     if (p.ppool) {  // tuples with payloads (materialization): no global-mode codes
         switch (g.mode) {
             case MODE_SLICE_BLOCK:
-                if (g.format == FMT_PACKED) return scatter_pay_inst<MODE_SLICE_BLOCK, FMT_PACKED>(p, side, grid, st);
-                return scatter_pay_inst<MODE_SLICE_BLOCK, FMT_CODE>(p, side, grid, st);
-            case MODE_SLICE_BASIC: return scatter_pay_inst<MODE_SLICE_BASIC, FMT_CODE>(p, side, grid, st);
-            default: return scatter_pay_inst<MODE_NOBLOOM, FMT_CODE>(p, side, grid, st);
+                if (g.format == FMT_PACKED)
+                    return scatter_pay_inst<SRC_TUPLES, MODE_SLICE_BLOCK, FMT_PACKED>(p, side, grid, st);
+                return scatter_pay_inst<SRC_TUPLES, MODE_SLICE_BLOCK, FMT_CODE>(p, side, grid, st);
+            case MODE_SLICE_BASIC: return scatter_pay_inst<SRC_TUPLES, MODE_SLICE_BASIC, FMT_CODE>(p, side, grid, st);
+            default: return scatter_pay_inst<SRC_TUPLES, MODE_NOBLOOM, FMT_CODE>(p, side, grid, st);
         }
     }
     if (src == SRC_CODES) {

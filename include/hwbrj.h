@@ -197,8 +197,10 @@ int hwbrj_set_async_timing(int on);
  * 16-byte load). A misaligned pointer is refused before any device call: 2 is returned,
  * hwbrj_last_error() says "align", and *stats is not written. A caller sharding a column must
  * therefore cut it at multiples of 4 keys.
- * Not offered on key columns: the materializing, existence, outer and group joins, the host BPRO
- * family and the partitioned joins take tuples only. */
+ * The pair, existence and outer joins on key columns return row indices (hwbrj_join_keys_pairs_device,
+ * hwbrj_join_keys_semi_device, hwbrj_join_keys_outer_device, below). Not offered on key columns:
+ * payload or value columns, the group joins (an aggregate of row indices means nothing), async forms
+ * of the row-index joins, the host BPRO family and the partitioned joins; those take tuples only. */
 int hwbrj_join_keys_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys, uint64_t nS,
                            const bloom_filter_args_t * args, int algorithm, void * stream,
                            hwbrj_stats_t * stats);
@@ -266,6 +268,39 @@ int hwbrj_join_outer_device(const tuple_t * d_R, uint64_t nR, const tuple_t * d_
                             tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
                             uint64_t * n_class /* [3], optional */, void * stream,
                             hwbrj_stats_t * stats, double * ms);
+/* The pair, existence and outer joins on key columns (hwbrj_join_keys_device's layout): the result
+ * is row indices, the gather maps a columnar caller applies to its other columns. Every element's
+ * payload is its position in its column, computed by the scatter from the position and never read,
+ * so no {key, arange} interleaving pass is needed and the payload scatters read 4 instead of 8 bytes
+ * per element. Each entry keeps the contract of its tuple counterpart (hwbrj_join_materialize_device,
+ * hwbrj_join_semi_device, hwbrj_join_outer_device) in every clause not named here: capacity in rows,
+ * *n_out always the full count, 7 when it exceeds capacity, capacity 0 with d_out NULL as the
+ * count-only form, an unknown kind returning 2 without writing *n_out, args == NULL running PRO,
+ * every filter configuration (the global-bitmap ones run the counting join on key columns and a side
+ * pass), stats, ms, synchronous, collecting pending async joins, and hwbrj_tables_info /
+ * hwbrj_tables_read answering as after the tuple form.
+ *  - pairs: rows {R row, S row}, exactly the multiset hwbrj_join_materialize_device returns on
+ *    {key, row index} tuples.
+ *  - semi: rows {key, S row} (a tuple row, as the tuple form writes; the second column is the
+ *    gather map), kind HWBRJ_JOIN_SEMI or HWBRJ_JOIN_ANTI.
+ *  - outer: rows {R row, S row}, the missing side -1 (a row index is never negative, so there is no
+ *    null_payload argument); kind and n_class as in hwbrj_join_outer_device.
+ * Refused before any device call: a non-empty column that does not start at a 16-byte boundary (2,
+ * "align" in hwbrj_last_error(), nothing written; hwbrj_join_keys_device's rule), nR or nS of 2^31 or
+ * more (3, the message names the side: row indices are int32), capacity > 0 with d_out NULL (2). */
+int hwbrj_join_keys_pairs_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys,
+                                 uint64_t nS, const bloom_filter_args_t * args, tuple_t * d_out,
+                                 uint64_t capacity, uint64_t * n_out, void * stream,
+                                 hwbrj_stats_t * stats, double * ms);
+int hwbrj_join_keys_semi_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys,
+                                uint64_t nS, const bloom_filter_args_t * args, int kind,
+                                tuple_t * d_out, uint64_t capacity, uint64_t * n_out, void * stream,
+                                hwbrj_stats_t * stats, double * ms);
+int hwbrj_join_keys_outer_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys,
+                                 uint64_t nS, const bloom_filter_args_t * args, int kind,
+                                 tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
+                                 uint64_t * n_class /* [3], optional */, void * stream,
+                                 hwbrj_stats_t * stats, double * ms);
 /* The group join of R and S (join and aggregate per build-side row: SELECT R.payload, COUNT(*),
  * SUM(S.payload) ... GROUP BY R-row): d_out receives one row per R row, not per key, in no
  * particular order. count is the number of S rows whose key equals the R row's key, sum the sum of
