@@ -18,7 +18,7 @@ import numpy as np
 
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
-    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_keys_device", "join_keys_device_async", "join_keys_pairs_device", "semi_join_keys_device", "outer_join_keys_device", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
+    "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "group_join_keys_device", "group_minmax_join_keys_device", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_keys_device", "join_keys_device_async", "join_keys_pairs_device", "semi_join_keys_device", "outer_join_keys_device", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
     "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
@@ -154,6 +154,14 @@ def lib() -> ctypes.CDLL:
             ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
         L.hwbrj_join_group_minmax_device.restype = ctypes.c_int
         L.hwbrj_join_group_minmax_device.argtypes = L.hwbrj_join_group_device.argtypes
+        L.hwbrj_join_keys_group_device.restype = ctypes.c_int
+        L.hwbrj_join_keys_group_device.argtypes = [  # (hwbrj_join_group_device's with d_Svals before nS)
+            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
+            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
+            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
+        L.hwbrj_join_keys_group_minmax_device.restype = ctypes.c_int
+        L.hwbrj_join_keys_group_minmax_device.argtypes = L.hwbrj_join_keys_group_device.argtypes
         L.hwbrj_set_materialize.restype = None
         L.hwbrj_set_materialize.argtypes = [ctypes.c_int]
         L.hwbrj_set_gpus.restype = ctypes.c_int
@@ -515,12 +523,15 @@ def join_device(R, S, args: Optional[BloomFilterArgs] = None, stream=None,
     return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
 
 
-def _check_keys(Rk, Sk, stream):
-    """Both key columns: contiguous 1-D torch.int32 tensors on one GPU, each (when non-empty)
-    starting at a 16-byte boundary. Switches the library's HIP device as _check_rel does. Without
-    a stream of the caller's, waits for torch's current stream (the columns' producer)."""
+def _check_keys(Rk, Sk, stream, Sv=None):
+    """Both key columns (and Sv, S's value column of a group join, of Sk's length): contiguous 1-D
+    torch.int32 tensors on one GPU, each (when non-empty) starting at a 16-byte boundary. Switches
+    the library's HIP device as _check_rel does. Without a stream of the caller's, waits for torch's
+    current stream (the columns' producer)."""
     import torch
-    for name, t in (("Rk", Rk), ("Sk", Sk)):
+    for name, t in (("Rk", Rk), ("Sk", Sk)) + ((("Sv", Sv),) if Sv is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch tensor")
         if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
             raise ValueError(f"{name} must be a contiguous 1-D torch.int32 tensor on the GPU "
                              "(a strided view such as T[:, 0]: call .contiguous() first)")
@@ -529,6 +540,10 @@ def _check_keys(Rk, Sk, stream):
                              "multiples of 4 keys)")
     if Rk.device != Sk.device:
         raise ValueError(f"Rk is on {Rk.device} but Sk is on {Sk.device}")
+    if Sv is not None and Sv.device != Sk.device:
+        raise ValueError(f"Sv is on {Sv.device} but Sk is on {Sk.device}")
+    if Sv is not None and Sv.shape[0] != Sk.shape[0]:
+        raise ValueError(f"Sv has {Sv.shape[0]} values for the {Sk.shape[0]} keys of Sk")
     _err(lib().hwbrj_set_device(Rk.device.index or 0), "hwbrj_set_device")
     if stream is None:
         # a column is typically cut by a torch kernel (.contiguous()) that may still be running on
@@ -906,6 +921,70 @@ def group_minmax_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind:
     raw = out[: n.value]
     rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
     return stats, rows, int(pairs.value), ms.value
+
+
+def _group_keys(entry: str, minmax: bool, Rk, Sk, Sv, args, kind, stream, capacity):
+    """group_join_keys_device / group_minmax_join_keys_device: (Stats, raw rows, n_pairs, ms) of
+    `entry`, with the capacity behaviour of the tuple wrappers."""
+    import torch
+    _check_keys(Rk, Sk, stream, Sv)
+    a = args._c() if args is not None else None
+    ap = ctypes.byref(a) if a is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n, pairs = ctypes.c_uint64(), ctypes.c_uint64()
+    st = _Stats()
+    ms = ctypes.c_double()
+    fn = getattr(lib(), entry)
+
+    def call(out, cap):
+        return fn(_ptr(Rk), Rk.shape[0], _ptr(Sk), _ptr(Sv), Sk.shape[0], ap, int(kind), out, cap, ctypes.byref(n),
+                  ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
+
+    if capacity is None:
+        if int(kind) == GROUP_ALL:
+            capacity = Rk.shape[0]
+        else:
+            rc = call(None, 0)  # count only
+            if rc not in (0, 7):
+                _err(rc, entry)
+            capacity = n.value
+    for _ in range(2):
+        out = (torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=Rk.device) if minmax else
+               torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=Rk.device))
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, entry)
+    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+    return stats, out[: n.value], int(pairs.value), ms.value
+
+
+def group_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED, stream=None,
+                           capacity: Optional[int] = None):
+    """(Stats, GroupRows, n_pairs, ms): group_join_device on key columns with S's aggregated value in
+    a third column (hwbrj_join_keys_group_device). Rk, Sk are join_keys_device's columns and Sv a
+    column of Sk's length and kind: Sv[i] is the value of S row i. GroupRows.r_payload is the R row
+    index (the gather map for R's other columns), count and sum are over Sv of the S rows with the R
+    row's key: exactly group_join_device's rows on stack(Rk, arange) and stack(Sk, Sv), without that
+    interleaving pass. len(Rk) < 2^31, len(Sk) < 2^32. kind, capacity, n_pairs, Stats and ms are
+    group_join_device's; the stream rule is join_keys_device's."""
+    import torch
+    stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_device", False, Rk, Sk, Sv, args, kind, stream, capacity)
+    rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
+    return stats, rows, pairs, ms
+
+
+def group_minmax_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED,
+                                  stream=None, capacity: Optional[int] = None):
+    """(Stats, GroupMinMaxRows, n_pairs, ms): group_minmax_join_device on key columns
+    (hwbrj_join_keys_group_minmax_device): group_join_keys_device's arguments, r_payload the R row
+    index, min and max over Sv of the S rows with the R row's key, compared as signed int32."""
+    import torch
+    stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_minmax_device", True, Rk, Sk, Sv, args, kind, stream,
+                                        capacity)
+    rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
+    return stats, rows, pairs, ms
 
 
 def copy_bandwidth(nbytes: int = 4 << 30, reps: int = 5) -> float:

@@ -452,9 +452,12 @@ int hwbrj_join_keys_outer_device(const int32_t* d_Rkeys, uint64_t nR, const int3
 // pairs (Engine::run_group); the global-bitmap mode runs the counting join (its filter and its
 // "S-tuples after filter") and the group side pass. Both aggregate sets (agg: GroupAgg) share it:
 // their rows are 16 bytes and every clause of the contract is the same.
-static int join_group(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
+// layout SRC_KEYS: d_R, d_S are int32 key columns, R's payload is its row index and the aggregated S
+// payloads are the value column d_Svals (SRC_TUPLES: nullptr).
+static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void* d_Svals, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, uint32_t agg, void* d_out, uint64_t capacity,
-                      uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms) {
+                      uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms,
+                      int layout) {
     static_assert(sizeof(hwbrj_group_row_t) == 16 && sizeof(hwbrj_group_minmax_row_t) == 16,
                   "a row is one 16-byte store");
     if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {  // (before any device call)
@@ -475,17 +478,17 @@ static int join_group(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint6
     }
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
-    const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL, agg};
+    const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL, agg, d_Svals};
     hwbrj_stats_t  st;
     uint64_t       n = 0, pairs = 0;
-    int rc = e->run_group((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, req, &st, &pairs);
+    int rc = e->run_group(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, &pairs, layout);
     if (rc == 0) {
         n = (uint64_t) st.matches;
         if (ms) *ms = st.ms_total;
     } else if (rc == kRcMatGlobal) {
-        rc = e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, &st);
+        rc = e->run(d_R, nR, d_S, nS, args, (hipStream_t) stream, &st, 0, layout);
         if (rc) return rc;
-        rc = e->group_side((const uint2*) d_R, nR, (const uint2*) d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms);
+        rc = e->group_side(d_R, nR, d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms, layout);
         if (rc) return rc;
         st.matches = (int64_t) n;
     } else {
@@ -505,7 +508,8 @@ int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S,
                             const bloom_filter_args_t* args, int kind, hwbrj_group_row_t* d_out,
                             uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
                             hwbrj_stats_t* stats, double* ms) {
-    return join_group(d_R, nR, d_S, nS, args, kind, GRP_COUNT_SUM, d_out, capacity, n_out, n_pairs, stream, stats, ms);
+    return join_group(d_R, nR, d_S, nullptr, nS, args, kind, GRP_COUNT_SUM, d_out, capacity, n_out, n_pairs, stream,
+                      stats, ms, SRC_TUPLES);
 }
 
 // The group join's MIN / MAX form: k_join_group's {count, min, max} accumulators ("Group
@@ -514,8 +518,48 @@ int hwbrj_join_group_minmax_device(const tuple_t* d_R, uint64_t nR, const tuple_
                                    const bloom_filter_args_t* args, int kind, hwbrj_group_minmax_row_t* d_out,
                                    uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
                                    hwbrj_stats_t* stats, double* ms) {
-    return join_group(d_R, nR, d_S, nS, args, kind, GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs, stream, stats,
-                      ms);
+    return join_group(d_R, nR, d_S, nullptr, nS, args, kind, GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs, stream,
+                      stats, ms, SRC_TUPLES);
+}
+
+// The group joins on key columns: the columns' alignment rule (the value column's as the key
+// columns': its loads have the keys' shape), a value for every S key, and R rows that fit the int32
+// row index. Checked before any device call; join_group then checks the rest (|S| < 2^32 among it).
+static int keys_group_ok(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys, const int32_t* d_Svals,
+                         uint64_t nS) {
+    if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
+    if (nS && !d_Svals) {
+        set_last_error("d_Svals must hold a value for each of the nS keys of S");
+        return 2;
+    }
+    if (nS && ((uintptr_t) d_Svals & 15u)) {
+        set_last_error("value column S is not 16-byte aligned (shard a column at multiples of 4 values)");
+        return 2;
+    }
+    if (nR >= (1ull << 31)) {
+        set_last_error("key column R has 2^31 rows or more (row indices are int32)");
+        return 3;
+    }
+    return 0;
+}
+
+int hwbrj_join_keys_group_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys,
+                                 const int32_t* d_Svals, uint64_t nS, const bloom_filter_args_t* args, int kind,
+                                 hwbrj_group_row_t* d_out, uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs,
+                                 void* stream, hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = keys_group_ok(d_Rkeys, nR, d_Skeys, d_Svals, nS)) return rc;
+    return join_group(d_Rkeys, nR, d_Skeys, d_Svals, nS, args, kind, GRP_COUNT_SUM, d_out, capacity, n_out, n_pairs,
+                      stream, stats, ms, SRC_KEYS);
+}
+
+int hwbrj_join_keys_group_minmax_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys,
+                                        const int32_t* d_Svals, uint64_t nS, const bloom_filter_args_t* args,
+                                        int kind, hwbrj_group_minmax_row_t* d_out, uint64_t capacity,
+                                        uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats,
+                                        double* ms) {
+    if (const int rc = keys_group_ok(d_Rkeys, nR, d_Skeys, d_Svals, nS)) return rc;
+    return join_group(d_Rkeys, nR, d_Skeys, d_Svals, nS, args, kind, GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs,
+                      stream, stats, ms, SRC_KEYS);
 }
 
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE

@@ -381,10 +381,10 @@ int Engine::run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     return 0;
 }
 
-int Engine::run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+int Engine::run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                       const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
-                      hwbrj_stats_t* st, uint64_t* pairs) {
-    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, nullptr, &group);
+                      hwbrj_stats_t* st, uint64_t* pairs, int layout) {
+    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, nullptr, &group, layout);
     if (rc == 0) rc = wait(st);
     if (rc) return rc;
     // (the join has completed; its ring slot is taken again by the next enqueue only)
@@ -395,10 +395,11 @@ int Engine::run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS
 // mat / semi / outer / group: the payload-carrying pipeline (pl below). mat carries both relations'
 // payloads, and so do outer and group (from the join on they have kernels of their own); semi only
 // S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
-// layout: what dR and dS point to, SRC_TUPLES or SRC_KEYS (key columns: the counting join, and mat /
-// semi / outer with the row index as the payload; not group, whose aggregates of row indices mean
-// nothing). It selects the kernels that read the relations; the partition words and payloads, and so
-// everything from the pools on, do not depend on it.
+// layout: what dR and dS point to, SRC_TUPLES or SRC_KEYS (key columns: the counting join; mat /
+// semi / outer with the row index as the payload; group with R's row index and, as S's payloads, its
+// value column group->s_val: the S payload scatter then reads SRC_KEYS_VAL). It selects the kernels
+// that read the relations; the partition words and payloads, and so everything from the pools on, do
+// not depend on it.
 int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                     const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group,
@@ -414,14 +415,21 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     Geometry    g;
     std::string err;
     const bool  pl = mat || semi;  // S payloads beside the words, the materializing geometry
-    if (layout != SRC_TUPLES && (layout != SRC_KEYS || group)) {
-        set_last_error("key columns: the counting, pair, existence and outer joins only");
+    if (layout != SRC_TUPLES && layout != SRC_KEYS) {
+        set_last_error("relations are tuples or key columns");
         return 2;
     }
-    if (layout == SRC_KEYS && pl && (nR >= (1ull << 31) || nS >= (1ull << 31))) {  // (hwbrj_api.cpp refuses first)
+    if (layout == SRC_KEYS && group && nS && !group->s_val) {
+        set_last_error("key columns: a group join needs S's value column");
+        return 2;
+    }
+    // (hwbrj_api.cpp refuses first; a group join produces no S row index, so S is not held to 2^31)
+    if (layout == SRC_KEYS && pl && (nR >= (1ull << 31) || (!group && nS >= (1ull << 31)))) {
         set_last_error("key columns: row indices are int32 (|R|, |S| < 2^31)");
         return 3;
     }
+    // what the S payload scatter reads: the layout, or S's key column with its value column
+    const int layout_s = layout == SRC_KEYS && group ? SRC_KEYS_VAL : layout;
     if (!plan_geometry(args, nR, &g, &err, pl)) {
         set_last_error(err);
         return 2;
@@ -538,11 +546,12 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
             ss.src   = dS;
             ss.n     = nS;
             ss.n_dev = nullptr;
+            if (layout_s == SRC_KEYS_VAL) ss.src_val = group->s_val;  // (shares seg_cnt's slot: not SRC_CODES)
         }
         S_.bind(&ss, capS);
         ss.ppool = pl ? ppoolS.as<uint32_t>() : nullptr;
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
-        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : layout, SIDE_S, G, st);
+        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : layout_s, SIDE_S, G, st);
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
         if (marks) HWBRJ_CHECK(mark(4, st));
         index_side(S_, capS, g.log2F, CH, nseg, G, st);
@@ -1497,8 +1506,12 @@ int Engine::outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     return 0;
 }
 
-int Engine::group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const GroupReq& group,
-                       uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms) {
+int Engine::group_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const GroupReq& group,
+                       uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms, int layout) {
+    if (layout == SRC_KEYS && nS && !group.s_val) {
+        set_last_error("key columns: a group join needs S's value column");
+        return 2;
+    }
     HWBRJ_CHECK(hipSetDevice(device_));
     if (!stream) stream = own_stream_;
     uint64_t T = 2;
@@ -1517,25 +1530,25 @@ int Engine::group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t n
     if (minmax) launch_group_minmax_init(gmin.as<int32_t>(), gmax.as<int32_t>(), rows, stream);
     else HWBRJ_CHECK(hipMemsetAsync(gsum.p, 0, rows * 8, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, SRC_TUPLES, nR, mtab.as<unsigned long long>(), T - 1, stream);
+    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
     if (nR && nS) {
         Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
         if (!have_filter_) g.mode = MODE_NOBLOOM;
         if (minmax)
-            launch_group_probe_minmax(dS, nS, mtab.as<unsigned long long>(), T - 1, gcnt.as<uint32_t>(),
-                                      gmin.as<int32_t>(), gmax.as<int32_t>(), g, slices.as<uint32_t>(),
-                                      bitmap.as<uint32_t>(), d_tabs_, stream);
+            launch_group_probe_minmax(dS, group.s_val, layout, nS, mtab.as<unsigned long long>(), T - 1,
+                                      gcnt.as<uint32_t>(), gmin.as<int32_t>(), gmax.as<int32_t>(), g,
+                                      slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_, stream);
         else
-            launch_group_probe(dS, nS, mtab.as<unsigned long long>(), T - 1, gcnt.as<uint32_t>(),
-                               gsum.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_,
-                               stream);
+            launch_group_probe(dS, group.s_val, layout, nS, mtab.as<unsigned long long>(), T - 1,
+                               gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), g, slices.as<uint32_t>(),
+                               bitmap.as<uint32_t>(), d_tabs_, stream);
     }
     if (nR && minmax)
-        launch_group_rows_minmax(dR, nR, gcnt.as<uint32_t>(), gmin.as<int32_t>(), gmax.as<int32_t>(),
+        launch_group_rows_minmax(dR, layout, nR, gcnt.as<uint32_t>(), gmin.as<int32_t>(), gmax.as<int32_t>(),
                                  group.all ? 1u : 0u, group.out, group.cap, mcount.as<unsigned long long>(), stream);
     else if (nR)
-        launch_group_rows(dR, nR, gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), group.all ? 1u : 0u, group.out,
-                          group.cap, mcount.as<unsigned long long>(), stream);
+        launch_group_rows(dR, layout, nR, gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), group.all ? 1u : 0u,
+                          group.out, group.cap, mcount.as<unsigned long long>(), stream);
     HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
     HWBRJ_CHECK(hipGetLastError());
     HWBRJ_CHECK(hipEventSynchronize(ev_[8]));

@@ -46,11 +46,14 @@ struct OuterReq {
 // A group join's output: rows {R.payload, count, sum} (hwbrj_group_row_t, 16 bytes) into
 // out[0, cap). all: every R row is a row; otherwise those with count > 0. agg (GroupAgg):
 // GRP_COUNT_MINMAX gives rows {R.payload, count, min, max} (hwbrj_group_minmax_row_t) instead.
+// s_val: with key columns (layout SRC_KEYS), S's value column, |S| uint32 beside its key column: the
+// S payloads that are aggregated (R.payload is then the R row index); tuples: not read.
 struct GroupReq {
-    uint4*   out;
-    uint64_t cap;
-    bool     all;
-    uint32_t agg = GRP_COUNT_SUM;
+    uint4*      out;
+    uint64_t    cap;
+    bool        all;
+    uint32_t    agg   = GRP_COUNT_SUM;
+    const void* s_val = nullptr;
 };
 
 struct DevBuf {
@@ -131,7 +134,7 @@ class Engine {
     // The materializing join (the partitioned pipeline carrying payloads): st->matches = pairs
     // (all of them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
     // layout (here, run_semi, run_outer and their side passes): SRC_TUPLES, or SRC_KEYS: key columns
-    // as in run(), every element's payload its row index (|R|, |S| < 2^31). run_group: tuples only.
+    // as in run(), every element's payload its row index (|R|, |S| < 2^31).
     int  run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                  const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
                  hwbrj_stats_t* st, int layout = SRC_TUPLES);
@@ -149,13 +152,14 @@ class Engine {
                    hwbrj_stats_t* st, uint64_t cls[3], int layout = SRC_TUPLES);
     // The group join on the materializing pipeline up to the join, then k_join_group. st->matches =
     // rows (all of them, also beyond cap); *pairs = the sum of their counts. kRcMatGlobal: not for the
-    // global-bitmap mode.
-    int  run_group(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
+    // global-bitmap mode. layout SRC_KEYS: R's payload is its row index (|R| < 2^31) and S's payloads
+    // are group.s_val (GroupReq), the only payloads of S that are read.
+    int  run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
-                   hwbrj_stats_t* st, uint64_t* pairs);
+                   hwbrj_stats_t* st, uint64_t* pairs, int layout = SRC_TUPLES);
     // Its side pass after a counting join (global-bitmap mode): *n = rows, *pairs as above.
-    int  group_side(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS, const GroupReq& group,
-                    uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms);
+    int  group_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const GroupReq& group,
+                    uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
     // Its side pass after a counting join (global-bitmap mode): *n = rows, cls as above.
     int  outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
                     uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout = SRC_TUPLES);

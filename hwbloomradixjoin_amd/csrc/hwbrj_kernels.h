@@ -14,7 +14,10 @@ namespace hwbrj {
 
 // What a scatter reads: {key, payload} tuples, 4-byte codes, or a column of 4-byte keys (hashed as
 // the tuples' keys are). SRC_KEYS is also the input layout of a whole counting join (Engine::run).
-enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2 };
+// SRC_KEYS_VAL: a key column with a value column of the same length beside it (ScatterParams::
+// src_val), the payload scatter of S only: element i carries payload src_val[i] (the group joins on
+// key columns).
+enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2, SRC_KEYS_VAL = 3 };
 
 struct ScatterParams {
     const void*      src;          // uint2 tuples {key, payload}, uint32 codes or uint32 keys
@@ -27,8 +30,14 @@ struct ScatterParams {
     uint32_t*        wgq_chunks;   // [G][F] chunks of partition q in workgroup wg's region
     uint32_t*        wgq_elems;    // [G][F] elements of partition q in workgroup wg's region
     uint64_t         cap;          // chunk capacity of one workgroup region
-    const uint32_t*  seg_cnt;      // SRC_CODES from per-workgroup segments: workgroup w partitions
-    uint64_t         seg_stride;   // src + w * seg_stride (elements), seg_cnt[w] of them; or nullptr
+    union {                        // (one slot: no source uses both, and every field keeps the
+                                   // kernel-argument offset it had before src_val)
+        const uint32_t* seg_cnt;   // SRC_CODES from per-workgroup segments: workgroup w partitions
+                                   // src + w * seg_stride (elements), seg_cnt[w] of them; or nullptr
+        const void*     src_val;   // SRC_KEYS_VAL: the n uint32 values beside src's keys, 16-byte
+                                   // aligned as src
+    };
+    uint64_t         seg_stride;
     uint64_t         vn;           // MODE_BASIC_POS: tuples / keys of src (n = k * vn elements, k <= grid)
     // the join's per-call zeroing, done by workgroup 0 instead of memset dispatches: zero_small[0, 16)
     // (counts) and *zero_word (the join's extra-task count), each when not nullptr
@@ -281,19 +290,21 @@ void   launch_join_group(const GroupJoinParams& p, uint32_t jobs, hipStream_t st
 // table entry with its key (cnt, sum: one element per R row, zero on entry). launch_group_rows then
 // writes the rows of R[0, n) (all of them, or those with cnt > 0) to out, up to cap;
 // res[0] += rows, res[1] += their counts.
-void   launch_group_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
-                          uint32_t* cnt, unsigned long long* sum, const Geometry& g, const uint32_t* slices,
-                          const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
-void   launch_group_rows(const uint2* R, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
+// src: SRC_TUPLES (Sv is not read), or SRC_KEYS: S and R are uint32 key columns, S's payloads the
+// uint32 value column Sv and R's payload the row index.
+void   launch_group_probe(const void* S, const void* Sv, int src, uint64_t n, const unsigned long long* tab,
+                          uint64_t mask, uint32_t* cnt, unsigned long long* sum, const Geometry& g,
+                          const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
+void   launch_group_rows(const void* R, int src, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
                          uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st);
 // The side pass's min/max form: mn[row] and mx[row] (one int32 per R row, INT32_MAX and INT32_MIN
 // on entry: launch_group_minmax_init) take the payload of every matching S tuple.
 void   launch_group_minmax_init(int32_t* mn, int32_t* mx, uint64_t n, hipStream_t st);
-void   launch_group_probe_minmax(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
-                                 uint32_t* cnt, int32_t* mn, int32_t* mx, const Geometry& g,
-                                 const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs,
-                                 hipStream_t st);
-void   launch_group_rows_minmax(const uint2* R, uint64_t n, const uint32_t* cnt, const int32_t* mn,
+void   launch_group_probe_minmax(const void* S, const void* Sv, int src, uint64_t n,
+                                 const unsigned long long* tab, uint64_t mask, uint32_t* cnt, int32_t* mn,
+                                 int32_t* mx, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
+                                 const CrcTables* tabs, hipStream_t st);
+void   launch_group_rows_minmax(const void* R, int src, uint64_t n, const uint32_t* cnt, const int32_t* mn,
                                 const int32_t* mx, uint32_t all, uint4* out, uint64_t cap,
                                 unsigned long long* res, hipStream_t st);
 
@@ -315,6 +326,7 @@ void   launch_slice_fill(const uint32_t* pool, const uint32_t* list, const uint3
 size_t scatter_lds_bytes(uint32_t log2F);
 size_t scatter_pay_lds_bytes(uint32_t log2F);  // (ScatterParams::ppool set)
 enum { SIDE_R = 0, SIDE_S = 1 };  // which relation a scatter partitions (kernel name; S uses g.s_format)
+// (src = SRC_KEYS_VAL: SIDE_S with p.ppool and p.src_val set, nothing else)
 void   launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hipStream_t st);
 // k_plan: per-(wg, q) list offsets + per-partition chunk / element totals (colc, cole);
 // k_list_fill: scans the totals into list / element / item starts [F + 1] and fills the lists.

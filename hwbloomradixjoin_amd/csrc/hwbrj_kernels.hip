@@ -346,6 +346,12 @@ __device__ __forceinline__ uint32_t elem_pay(uint32_t, uint64_t i) { return (uin
 // element i as {key, payload}
 __device__ __forceinline__ uint2 elem_tuple(const uint2& t, uint64_t) { return t; }
 __device__ __forceinline__ uint2 elem_tuple(uint32_t k, uint64_t i) { return make_uint2(k, elem_pay(k, i)); }
+// element i as {key, value} where a key column has a value column beside it (the group joins' S
+// side); tuples carry their value themselves and V is not read
+__device__ __forceinline__ uint2 elem_key_val(const uint2* E, const uint32_t*, uint64_t i) { return E[i]; }
+__device__ __forceinline__ uint2 elem_key_val(const uint32_t* K, const uint32_t* V, uint64_t i) {
+    return make_uint2(K[i], V[i]);
+}
 
 template <class T>
 __global__ __launch_bounds__(256) void k_build_global(const T* R, uint64_t n, Geometry g,
@@ -898,18 +904,24 @@ typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 template <int SRC>
 struct ScPayRaw {  // one round's raw loads of this thread: {key, payload} tuples, or a key column's keys
     v2u      t[SRC == SRC_TUPLES ? kScE : 1];
-    uint32_t k[SRC == SRC_KEYS ? kScE : 1];
+    uint32_t k[SRC == SRC_KEYS || SRC == SRC_KEYS_VAL ? kScE : 1];
+    uint32_t v[SRC == SRC_KEYS_VAL ? kScE : 1];  // (and the value column's values at the keys' indices)
 };
 
 // SRC: SRC_TUPLES, or SRC_KEYS: a key column whose payloads are the row indices (element i of the
 // relation carries payload i, computed from the index that addressed its load and never read).
 // One round of loads in flight in both: the kernel sits at the 128 VGPRs its one 1024-thread
 // workgroup per CU allows, and a second round of key loads spills (DESIGN "Key columns: row-index joins").
+// SRC_KEYS_VAL: SRC_KEYS with every payload read from a value column (P.src_val) at the index that
+// addressed the key: each key load has a value load of the same shape, offsets and bound through a
+// resource of its own (DESIGN "Key columns: group joins").
 template <int SRC, int MODE, int FMT>
 __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
-    static_assert(SRC == SRC_TUPLES || SRC == SRC_KEYS, "tuples or a key column");
+    static_assert(SRC == SRC_TUPLES || SRC == SRC_KEYS || SRC == SRC_KEYS_VAL, "tuples or a key column");
     static_assert(kScE % 4 == 0 && kScPayThreads == kScThreads, "four keys per 16-byte load");
-    constexpr uint32_t EB = SRC == SRC_KEYS ? 4u : 8u;  // bytes per element
+    constexpr bool     KEYS = SRC == SRC_KEYS || SRC == SRC_KEYS_VAL;  // the key column's load and index shape
+    constexpr bool     VAL  = SRC == SRC_KEYS_VAL;
+    constexpr uint32_t EB   = KEYS ? 4u : 8u;  // bytes per element (of each column)
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ uint32_t crc_tab[128];
     const uint32_t F     = 1u << P.g.log2F;
@@ -951,6 +963,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     const uint32_t len = __builtin_amdgcn_readfirstlane(e1 > e0 ? (uint32_t) (e1 - e0) : 0u);
     uint16_t* __restrict__ meta = (uint16_t*) P.meta + wg * P.cap;
     const auto rsrc   = buf_rsrc((const uint8_t*) P.src + e0 * EB, len * EB);  // OOB loads return 0
+    const auto rval   = VAL ? buf_rsrc((const uint8_t*) P.src_val + e0 * EB, len * EB) : rsrc;  // the values of [e0, e1)
     const auto rpool  = buf_rsrc(P.pool + wg * P.cap * 32, (uint32_t) (P.cap * 128));
     const auto rppool = buf_rsrc(P.ppool + wg * P.cap * 32, (uint32_t) (P.cap * 128));
     const auto rmeta  = buf_rsrc(meta, (uint32_t) (P.cap * 2));
@@ -959,14 +972,15 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     auto hword = [&](uint32_t H) { return H * 16u; };  // word offset of half H in the region
     // element j of this thread in the round at `base`: its index inside the workgroup's range.
     // SRC_KEYS: four consecutive keys per thread and load (scatter_body's SRC_KEYS shape); the index
-    // addresses the load and, added to e0, is the element's payload (its row).
+    // addresses the load and, added to e0, is the element's payload (its row), or addresses the
+    // value column's load as well (SRC_KEYS_VAL).
     auto eidx = [&](uint32_t base, int j) -> uint32_t {
-        if (SRC == SRC_KEYS) return base + (j >> 2) * 4 * kScPayThreads + 4 * tid + (j & 3);
+        if (KEYS) return base + (j >> 2) * 4 * kScPayThreads + 4 * tid + (j & 3);
         return base + j * kScPayThreads + tid;
     };
     const uint32_t row0 = (uint32_t) e0;  // (rows < 2^31: hwbrj_join_keys_*_device)
     auto load_round = [&](uint32_t base, ScPayRaw<SRC>& R) {
-        if (SRC == SRC_KEYS && base + kScRound <= len) {  // four keys per 16-byte load: eidx(base, 4 h .. 4 h + 3)
+        if (KEYS && base + kScRound <= len) {  // four keys per 16-byte load: eidx(base, 4 h .. 4 h + 3)
 #pragma unroll
             for (int h = 0; h < kScE / 4; h++) {
                 const v4u x = __builtin_amdgcn_raw_buffer_load_b128(rsrc, 4 * tid * EB, (base + h * 4 * kScPayThreads) * EB, HWBRJ_SC_LAUX);
@@ -974,12 +988,20 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
                 R.k[4 * h + 1] = x.y;
                 R.k[4 * h + 2] = x.z;
                 R.k[4 * h + 3] = x.w;
+                if (VAL) {  // the four values of those keys
+                    const v4u y = __builtin_amdgcn_raw_buffer_load_b128(rval, 4 * tid * EB, (base + h * 4 * kScPayThreads) * EB, HWBRJ_SC_LAUX);
+                    R.v[4 * h]     = y.x;
+                    R.v[4 * h + 1] = y.y;
+                    R.v[4 * h + 2] = y.z;
+                    R.v[4 * h + 3] = y.w;
+                }
             }
-        } else if (SRC == SRC_KEYS) {
+        } else if (KEYS) {
 #pragma unroll
             for (int j = 0; j < kScE; j++) {
                 const uint32_t i = eidx(base, j);
                 R.k[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, i < len ? i * EB : kOob, 0, 0);
+                if (VAL) R.v[j] = __builtin_amdgcn_raw_buffer_load_b32(rval, i < len ? i * EB : kOob, 0, 0);
             }
         } else if (base + kScRound <= len) {  // {key, payload} as one 8-byte load
 #pragma unroll
@@ -1056,8 +1078,8 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         uint32_t   q[kScE], w[kScE], p[kScE];
 #pragma unroll
         for (int j = 0; j < kScE; j++) {
-            sc_word_lds0<SRC, MODE, FMT>(SRC == SRC_KEYS ? RA.k[j] : RA.t[j].x, P.g, crc_tab, w[j], q[j]);
-            p[j] = SRC == SRC_KEYS ? row0 + eidx(base, j) : RA.t[j].y;
+            sc_word_lds0<KEYS ? SRC_KEYS : SRC, MODE, FMT>(KEYS ? RA.k[j] : RA.t[j].x, P.g, crc_tab, w[j], q[j]);
+            p[j] = VAL ? RA.v[j] : KEYS ? row0 + eidx(base, j) : RA.t[j].y;
             if ((j % HWBRJ_SC_SB) == HWBRJ_SC_SB - 1) __builtin_amdgcn_sched_barrier(0);
         }
         if (!full) {
@@ -4747,17 +4769,21 @@ void launch_join_group(const GroupJoinParams& p0, uint32_t jobs, hipStream_t st)
 
 // The group join's side pass (global-bitmap mode): k_mat_probe's walk with the filter as a pre-test;
 // a matching entry's R row gets the S tuple in its two accumulators (device-scope atomics).
-__global__ __launch_bounds__(256) void k_group_probe(const uint2* __restrict__ S, uint64_t n,
+// T: uint2 tuples, or uint32_t: key columns, S's values in Sv (elem_key_val) and R's payload its row
+// index (elem_pay), as the other side-pass kernels. Sv comes last: the tuple form keeps its arguments.
+template <class T>
+__global__ __launch_bounds__(256) void k_group_probe(const T* __restrict__ S, uint64_t n,
                                                       const unsigned long long* __restrict__ tab,
                                                       uint64_t mask, uint32_t* __restrict__ cnt,
                                                       unsigned long long* __restrict__ sum, Geometry g,
                                                       const uint32_t* __restrict__ slices,
                                                       const uint32_t* __restrict__ bm,
-                                                      const CrcTables* __restrict__ tabs) {
+                                                      const CrcTables* __restrict__ tabs,
+                                                      const uint32_t* __restrict__ Sv) {
     uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        const uint2 st = S[i];
+        const uint2 st = elem_key_val(S, Sv, i);
         if (!mat_filter(st.x, g, slices, bm, tabs)) continue;
         for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
             const unsigned long long e = tab[h];
@@ -4772,7 +4798,8 @@ __global__ __launch_bounds__(256) void k_group_probe(const uint2* __restrict__ S
 
 // One pass over R writes the rows; a wave takes its output range with one atomic (and adds its
 // counts to the pair total with it).
-__global__ __launch_bounds__(256) void k_group_rows(const uint2* __restrict__ R, uint64_t n,
+template <class T>
+__global__ __launch_bounds__(256) void k_group_rows(const T* __restrict__ R, uint64_t n,
                                                      const uint32_t* __restrict__ cnt,
                                                      const unsigned long long* __restrict__ sum, uint32_t all,
                                                      uint4* __restrict__ out, uint64_t cap,
@@ -4795,20 +4822,24 @@ __global__ __launch_bounds__(256) void k_group_rows(const uint2* __restrict__ R,
         const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
         if (w && o < cap) {
             const unsigned long long sm = sum[i];
-            out[o] = make_uint4(R[i].y, c, (uint32_t) sm, (uint32_t) (sm >> 32));
+            out[o] = make_uint4(elem_pay(R[i], i), c, (uint32_t) sm, (uint32_t) (sm >> 32));
         }
     }
 }
 
-void launch_group_probe(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask, uint32_t* cnt,
-                        unsigned long long* sum, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
-                        const CrcTables* tabs, hipStream_t st) {
-    k_group_probe<<<2048, 256, 0, st>>>(S, n, tab, mask, cnt, sum, g, slices, bm, tabs);
+void launch_group_probe(const void* S, const void* Sv, int src, uint64_t n, const unsigned long long* tab,
+                        uint64_t mask, uint32_t* cnt, unsigned long long* sum, const Geometry& g,
+                        const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
+    if (src == SRC_KEYS)
+        k_group_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, tab, mask, cnt, sum, g, slices, bm, tabs,
+                                                      (const uint32_t*) Sv);
+    else k_group_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, tab, mask, cnt, sum, g, slices, bm, tabs, nullptr);
 }
 
-void launch_group_rows(const uint2* R, uint64_t n, const uint32_t* cnt, const unsigned long long* sum, uint32_t all,
-                       uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
-    k_group_rows<<<2048, 256, 0, st>>>(R, n, cnt, sum, all, out, cap, res);
+void launch_group_rows(const void* R, int src, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
+                       uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
+    if (src == SRC_KEYS) k_group_rows<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) R, n, cnt, sum, all, out, cap, res);
+    else k_group_rows<uint2><<<2048, 256, 0, st>>>((const uint2*) R, n, cnt, sum, all, out, cap, res);
 }
 
 // The side pass's min/max form: the same walk and the same row pass over {cnt, mn, mx}; mn and mx
@@ -4823,17 +4854,19 @@ __global__ __launch_bounds__(256) void k_group_minmax_init(int32_t* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void k_group_probe_minmax(const uint2* __restrict__ S, uint64_t n,
+template <class T>
+__global__ __launch_bounds__(256) void k_group_probe_minmax(const T* __restrict__ S, uint64_t n,
                                                              const unsigned long long* __restrict__ tab,
                                                              uint64_t mask, uint32_t* __restrict__ cnt,
                                                              int32_t* __restrict__ mn, int32_t* __restrict__ mx,
                                                              Geometry g, const uint32_t* __restrict__ slices,
                                                              const uint32_t* __restrict__ bm,
-                                                             const CrcTables* __restrict__ tabs) {
+                                                             const CrcTables* __restrict__ tabs,
+                                                             const uint32_t* __restrict__ Sv) {
     uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
     const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
     for (; i < n; i += stride) {
-        const uint2 st = S[i];
+        const uint2 st = elem_key_val(S, Sv, i);
         if (!mat_filter(st.x, g, slices, bm, tabs)) continue;
         for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
             const unsigned long long e = tab[h];
@@ -4847,7 +4880,8 @@ __global__ __launch_bounds__(256) void k_group_probe_minmax(const uint2* __restr
     }
 }
 
-__global__ __launch_bounds__(256) void k_group_rows_minmax(const uint2* __restrict__ R, uint64_t n,
+template <class T>
+__global__ __launch_bounds__(256) void k_group_rows_minmax(const T* __restrict__ R, uint64_t n,
                                                             const uint32_t* __restrict__ cnt,
                                                             const int32_t* __restrict__ mn,
                                                             const int32_t* __restrict__ mx, uint32_t all,
@@ -4869,7 +4903,7 @@ __global__ __launch_bounds__(256) void k_group_rows_minmax(const uint2* __restri
         }
         base = __shfl(base, 0, 64);
         const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
-        if (w && o < cap) out[o] = make_uint4(R[i].y, c, (uint32_t) mn[i], (uint32_t) mx[i]);
+        if (w && o < cap) out[o] = make_uint4(elem_pay(R[i], i), c, (uint32_t) mn[i], (uint32_t) mx[i]);
     }
 }
 
@@ -4877,15 +4911,23 @@ void launch_group_minmax_init(int32_t* mn, int32_t* mx, uint64_t n, hipStream_t 
     k_group_minmax_init<<<2048, 256, 0, st>>>(mn, mx, n);
 }
 
-void launch_group_probe_minmax(const uint2* S, uint64_t n, const unsigned long long* tab, uint64_t mask,
-                               uint32_t* cnt, int32_t* mn, int32_t* mx, const Geometry& g, const uint32_t* slices,
-                               const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
-    k_group_probe_minmax<<<2048, 256, 0, st>>>(S, n, tab, mask, cnt, mn, mx, g, slices, bm, tabs);
+void launch_group_probe_minmax(const void* S, const void* Sv, int src, uint64_t n, const unsigned long long* tab,
+                               uint64_t mask, uint32_t* cnt, int32_t* mn, int32_t* mx, const Geometry& g,
+                               const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
+    if (src == SRC_KEYS)
+        k_group_probe_minmax<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, tab, mask, cnt, mn, mx, g, slices,
+                                                             bm, tabs, (const uint32_t*) Sv);
+    else
+        k_group_probe_minmax<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, tab, mask, cnt, mn, mx, g, slices, bm,
+                                                          tabs, nullptr);
 }
 
-void launch_group_rows_minmax(const uint2* R, uint64_t n, const uint32_t* cnt, const int32_t* mn, const int32_t* mx,
-                              uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
-    k_group_rows_minmax<<<2048, 256, 0, st>>>(R, n, cnt, mn, mx, all, out, cap, res);
+void launch_group_rows_minmax(const void* R, int src, uint64_t n, const uint32_t* cnt, const int32_t* mn,
+                              const int32_t* mx, uint32_t all, uint4* out, uint64_t cap, unsigned long long* res,
+                              hipStream_t st) {
+    if (src == SRC_KEYS)
+        k_group_rows_minmax<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) R, n, cnt, mn, mx, all, out, cap, res);
+    else k_group_rows_minmax<uint2><<<2048, 256, 0, st>>>((const uint2*) R, n, cnt, mn, mx, all, out, cap, res);
 }
 
 // ===================================================================== launch wrappers
@@ -4971,8 +5013,26 @@ static void scatter_pay_inst(const ScatterParams& p, int side, uint32_t grid, hi
     else k_scatter_sp<SRC, MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
 }
 
+// (the value-column form has no R side: k_scatter_rp<SRC_KEYS_VAL, ...> is not instantiated)
+template <int SRC, int MODE, int FMT>
+static void scatter_sp_inst(const ScatterParams& p, uint32_t grid, hipStream_t st) {
+    const size_t lds = scatter_pay_lds_bytes(p.g.log2F);
+    (void) hipFuncSetAttribute((const void*) &k_scatter_sp<SRC, MODE, FMT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int) lds);
+    k_scatter_sp<SRC, MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
+}
+
 void launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hipStream_t st) {
     const Geometry& g = p.g;
+    if (p.ppool && src == SRC_KEYS_VAL && side == SIDE_S) {  // S's key column, its value column as payloads
+        switch (g.mode) {
+            case MODE_SLICE_BLOCK:
+                if (g.format == FMT_PACKED) return scatter_sp_inst<SRC_KEYS_VAL, MODE_SLICE_BLOCK, FMT_PACKED>(p, grid, st);
+                return scatter_sp_inst<SRC_KEYS_VAL, MODE_SLICE_BLOCK, FMT_CODE>(p, grid, st);
+            case MODE_SLICE_BASIC: return scatter_sp_inst<SRC_KEYS_VAL, MODE_SLICE_BASIC, FMT_CODE>(p, grid, st);
+            default: return scatter_sp_inst<SRC_KEYS_VAL, MODE_NOBLOOM, FMT_CODE>(p, grid, st);
+        }
+    }
     if (p.ppool && src == SRC_KEYS) {  // a key column, its row indices as payloads: the modes of the tuples below
         switch (g.mode) {
             case MODE_SLICE_BLOCK:

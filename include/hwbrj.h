@@ -198,9 +198,11 @@ int hwbrj_set_async_timing(int on);
  * hwbrj_last_error() says "align", and *stats is not written. A caller sharding a column must
  * therefore cut it at multiples of 4 keys.
  * The pair, existence and outer joins on key columns return row indices (hwbrj_join_keys_pairs_device,
- * hwbrj_join_keys_semi_device, hwbrj_join_keys_outer_device, below). Not offered on key columns:
- * payload or value columns, the group joins (an aggregate of row indices means nothing), async forms
- * of the row-index joins, the host BPRO family and the partitioned joins; those take tuples only. */
+ * hwbrj_join_keys_semi_device, hwbrj_join_keys_outer_device, below), and the group joins on key
+ * columns aggregate a value column of S (hwbrj_join_keys_group_device,
+ * hwbrj_join_keys_group_minmax_device, below). Not offered on key columns: a value column for R or
+ * more than one for S, values other than int32, async forms of the row-index and group joins, the
+ * host BPRO family and the partitioned joins; those take tuples only. */
 int hwbrj_join_keys_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys, uint64_t nS,
                            const bloom_filter_args_t * args, int algorithm, void * stream,
                            hwbrj_stats_t * stats);
@@ -360,6 +362,37 @@ int hwbrj_join_group_minmax_device(const tuple_t * d_R, uint64_t nR, const tuple
                                    hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
                                    uint64_t * n_out, uint64_t * n_pairs /* optional */,
                                    void * stream, hwbrj_stats_t * stats, double * ms);
+/* The group joins on key columns (hwbrj_join_keys_device's layout) with S's aggregated value in a
+ * third column: d_Svals[i] is the value of the S row whose key is d_Skeys[i]. The rows are the tuple
+ * entries' rows: r_payload is the R row index (the gather map for R's other columns, as in the
+ * row-index joins above), and count, sum, min and max are over d_Svals[i] of the S rows i whose key
+ * equals the R row's key. The result is exactly what hwbrj_join_group_device /
+ * hwbrj_join_group_minmax_device return on the tuples R = {d_Rkeys[i], i} and S = {d_Skeys[i],
+ * d_Svals[i]}, without the pass that interleaves them: the S scatter reads each key with its value,
+ * two 16-byte loads per four rows. An aggregate of S row indices would mean nothing, so none is
+ * produced and S is not held to 2^31 rows. Each entry keeps its tuple counterpart's contract in every
+ * clause not named here: the kinds (an unknown one returns 2 without writing *n_out), capacity in
+ * rows, *n_out always the full row count, 7 when it exceeds capacity, capacity 0 with d_out NULL as
+ * the count-only form, d_out 16-byte aligned, n_pairs, stats->filtered and stats->matches, ms, args
+ * == NULL running PRO, every filter configuration (the global-bitmap ones run the counting join on
+ * key columns and the side pass), synchronous, single-GPU, collecting pending async joins, and
+ * hwbrj_tables_info / hwbrj_tables_read answering 13 afterwards.
+ * Refused before any device call: a non-empty column of the three that does not start at a 16-byte
+ * boundary (2, "align" in hwbrj_last_error(), nothing written; hwbrj_join_keys_device's rule, and the
+ * value column is loaded as the keys are), nS > 0 with d_Svals NULL (2), nR of 2^31 or more (3, the
+ * message names R: the R row index is int32), nS of 2^32 or more (3, the group join's own rule). */
+int hwbrj_join_keys_group_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys,
+                                 const int32_t * d_Svals, uint64_t nS,
+                                 const bloom_filter_args_t * args, int kind,
+                                 hwbrj_group_row_t * d_out, uint64_t capacity, uint64_t * n_out,
+                                 uint64_t * n_pairs /* optional */, void * stream,
+                                 hwbrj_stats_t * stats, double * ms);
+int hwbrj_join_keys_group_minmax_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys,
+                                        const int32_t * d_Svals, uint64_t nS,
+                                        const bloom_filter_args_t * args, int kind,
+                                        hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
+                                        uint64_t * n_out, uint64_t * n_pairs /* optional */,
+                                        void * stream, hwbrj_stats_t * stats, double * ms);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
