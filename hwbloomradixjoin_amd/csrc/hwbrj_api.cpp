@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <mutex>
 #include <set>
 #include <string>
@@ -253,15 +254,15 @@ int hwbrj_join_wait_all(hwbrj_stats_t* stats, int capacity, int* n_joins) {
     return e->wait_all(stats, capacity, n_joins);
 }
 
-// The materializing join: the partitioned pipeline carrying payloads (Engine::run_mat); the
-// global-bitmap mode (basic k = 0 or B < 8) falls back to a counting join plus the side pass.
-// *n = all pairs (also beyond cap); *ms = the device time of the pairs' production.
-// layout (here and in join_semi / join_outer below): SRC_TUPLES, or SRC_KEYS (d_R, d_S are int32 key
-// columns and every payload is the row index).
-static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
-                             const bloom_filter_args_t* args, tuple_t* d_out, uint64_t cap, uint64_t* n,
-                             hipStream_t stream, hwbrj_stats_t* st, double* ms, int layout = SRC_TUPLES) {
-    int rc = e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout);
+// Every payload join runs its partitioned pipeline (pipe(): st->matches rows, st->ms_total); the
+// global-bitmap mode (basic k = 0 or B < 8: kRcMatGlobal) falls back to the counting join (its
+// filter and its "S-tuples after filter") plus the kind's side pass (side(): *n rows, *ms its device
+// time). *n = all rows (also beyond the capacity), and st->matches with it.
+static int pipeline_or_side_pass(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
+                                 const bloom_filter_args_t* args, hipStream_t stream, int layout, hwbrj_stats_t* st,
+                                 uint64_t* n, double* ms, const std::function<int()>& pipe,
+                                 const std::function<int()>& side) {
+    int rc = pipe();
     if (rc == 0) {
         *n = (uint64_t) st->matches;
         if (ms) *ms = st->ms_total;
@@ -270,16 +271,47 @@ static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void
     if (rc != kRcMatGlobal) return rc;
     rc = e->run(d_R, nR, d_S, nS, args, stream, st, 0, layout);
     if (rc) return rc;
-    *n = (uint64_t) st->matches;
-    if (*n > cap) return 0;  // (the caller reports the capacity)
-    uint64_t m = 0;
-    rc = e->materialize(d_R, nR, d_S, nS, (uint2*) d_out, cap, &m, stream, ms, layout);
+    rc = side();
     if (rc) return rc;
-    if (m != *n) {
-        set_last_error("materialized pairs differ from the counted matches");
-        return 8;
+    st->matches = (int64_t) *n;
+    return 0;
+}
+
+// The caller's outputs of a payload join and its capacity rule (what: "match" or "row")
+static int publish(const hwbrj_stats_t& st, uint64_t n, uint64_t capacity, hwbrj_stats_t* stats, uint64_t* n_out,
+                   const char* what) {
+    if (stats) *stats = st;
+    if (n_out) *n_out = n;
+    if (n > capacity) {
+        set_last_error(std::string("output capacity below the ") + what + " count (*n_out holds the count)");
+        return 7;
     }
     return 0;
+}
+
+// The materializing join (Engine::run_mat, or Engine::materialize after the counting join).
+// *n = all pairs (also beyond cap); *ms = the device time of the pairs' production. In the
+// global-bitmap mode a count above cap returns before the side pass: no pair is written.
+// layout (here and in join_semi / join_outer below): SRC_TUPLES, or SRC_KEYS (d_R, d_S are int32 key
+// columns and every payload is the row index).
+static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
+                             const bloom_filter_args_t* args, tuple_t* d_out, uint64_t cap, uint64_t* n,
+                             hipStream_t stream, hwbrj_stats_t* st, double* ms, int layout = SRC_TUPLES) {
+    return pipeline_or_side_pass(
+        e, d_R, nR, d_S, nS, args, stream, layout, st, n, ms,
+        [&] { return e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout); },
+        [&] {
+            *n = (uint64_t) st->matches;
+            if (*n > cap) return 0;  // (the caller reports the capacity)
+            uint64_t  m  = 0;
+            const int rc = e->materialize(d_R, nR, d_S, nS, (uint2*) d_out, cap, &m, stream, ms, layout);
+            if (rc) return rc;
+            if (m != *n) {
+                set_last_error("materialized pairs differ from the counted matches");
+                return 8;
+            }
+            return 0;
+        });
 }
 
 static int join_pairs(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
@@ -291,14 +323,7 @@ static int join_pairs(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS
     uint64_t      n  = 0;
     const int     rc = materialize_pairs(e, d_R, nR, d_S, nS, args, d_out, capacity, &n, (hipStream_t) stream,
                                          &st, ms_materialize, layout);
-    if (rc) return rc;
-    if (stats) *stats = st;
-    if (n_out) *n_out = n;
-    if (n > capacity) {
-        set_last_error("output capacity below the match count (*n_out holds the count)");
-        return 7;
-    }
-    return 0;
+    return rc ? rc : publish(st, n, capacity, stats, n_out, "match");
 }
 
 int hwbrj_join_materialize_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -350,26 +375,11 @@ static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
     const SemiReq req{(uint2*) d_out, capacity, kind == HWBRJ_JOIN_ANTI};
     hwbrj_stats_t st;
     uint64_t      n  = 0;
-    int           rc = e->run_semi(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, layout);
-    if (rc == 0) {
-        n = (uint64_t) st.matches;
-        if (ms) *ms = st.ms_total;
-    } else if (rc == kRcMatGlobal) {
-        rc = e->run(d_R, nR, d_S, nS, args, (hipStream_t) stream, &st, 0, layout);
-        if (rc) return rc;
-        rc = e->semi_side(d_R, nR, d_S, nS, req, &n, (hipStream_t) stream, ms, layout);
-        if (rc) return rc;
-        st.matches = (int64_t) n;
-    } else {
-        return rc;
-    }
-    if (stats) *stats = st;
-    if (n_out) *n_out = n;
-    if (n > capacity) {
-        set_last_error("output capacity below the row count (*n_out holds the count)");
-        return 7;
-    }
-    return 0;
+    const int     rc = pipeline_or_side_pass(
+        e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
+        [&] { return e->run_semi(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, layout); },
+        [&] { return e->semi_side(d_R, nR, d_S, nS, req, &n, (hipStream_t) stream, ms, layout); });
+    return rc ? rc : publish(st, n, capacity, stats, n_out, "row");
 }
 
 int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -406,28 +416,14 @@ static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS
                        (uint32_t) null_payload};
     hwbrj_stats_t st;
     uint64_t      n = 0, cls[3] = {0, 0, 0};
-    int rc = e->run_outer(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, cls, layout);
-    if (rc == 0) {
-        n = (uint64_t) st.matches;
-        if (ms) *ms = st.ms_total;
-    } else if (rc == kRcMatGlobal) {
-        rc = e->run(d_R, nR, d_S, nS, args, (hipStream_t) stream, &st, 0, layout);
-        if (rc) return rc;
-        rc = e->outer_side(d_R, nR, d_S, nS, req, &n, cls, (hipStream_t) stream, ms, layout);
-        if (rc) return rc;
-        st.matches = (int64_t) n;
-    } else {
-        return rc;
-    }
-    if (stats) *stats = st;
-    if (n_out) *n_out = n;
+    const int     rc = pipeline_or_side_pass(
+        e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
+        [&] { return e->run_outer(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, cls, layout); },
+        [&] { return e->outer_side(d_R, nR, d_S, nS, req, &n, cls, (hipStream_t) stream, ms, layout); });
+    if (rc) return rc;
     if (n_class)
         for (int i = 0; i < 3; i++) n_class[i] = cls[i];
-    if (n > capacity) {
-        set_last_error("output capacity below the row count (*n_out holds the count)");
-        return 7;
-    }
-    return 0;
+    return publish(st, n, capacity, stats, n_out, "row");
 }
 
 int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -481,27 +477,13 @@ static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void*
     const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL, agg, d_Svals};
     hwbrj_stats_t  st;
     uint64_t       n = 0, pairs = 0;
-    int rc = e->run_group(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, &pairs, layout);
-    if (rc == 0) {
-        n = (uint64_t) st.matches;
-        if (ms) *ms = st.ms_total;
-    } else if (rc == kRcMatGlobal) {
-        rc = e->run(d_R, nR, d_S, nS, args, (hipStream_t) stream, &st, 0, layout);
-        if (rc) return rc;
-        rc = e->group_side(d_R, nR, d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms, layout);
-        if (rc) return rc;
-        st.matches = (int64_t) n;
-    } else {
-        return rc;
-    }
-    if (stats) *stats = st;
-    if (n_out) *n_out = n;
+    const int      rc = pipeline_or_side_pass(
+        e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
+        [&] { return e->run_group(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, &pairs, layout); },
+        [&] { return e->group_side(d_R, nR, d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms, layout); });
+    if (rc) return rc;
     if (n_pairs) *n_pairs = pairs;
-    if (n > capacity) {
-        set_last_error("output capacity below the row count (*n_out holds the count)");
-        return 7;
-    }
-    return 0;
+    return publish(st, n, capacity, stats, n_out, "row");
 }
 
 int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,

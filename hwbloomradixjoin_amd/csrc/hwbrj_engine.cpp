@@ -1428,31 +1428,42 @@ int Engine::tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t*
     return 0;
 }
 
-int Engine::materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
-                        uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout) {
-    HWBRJ_CHECK(hipSetDevice(device_));
-    if (!stream) stream = own_stream_;
+// The side pass of the global-bitmap mode, once for every payload join: the table of R
+// (side_slots(nR) slots) and the counters c[0, nc) in mcount, the kind's own buffers (`own`, each
+// filled with its 32-bit value), the table build, then the kind's probes: launch(t, stream), t =
+// the table and the counting join's filter (the side pass follows it). *ms = the device time from
+// the build to the last probe.
+static uint64_t side_slots(uint64_t nR) {
     uint64_t T = 2;
     while (T < 2 * nR) T <<= 1;
-    if (!mtab.ensure(T * 8) || !mcount.ensure(8)) {
-        set_last_error("hipMalloc failed (materialization table)");
+    return T;
+}
+
+template <class Launch>
+int Engine::side_pass(const void* dR, uint64_t nR, int layout, hipStream_t stream, const char* what,
+                      const std::vector<SideBuf>& own, uint64_t* c, uint32_t nc, double* ms, Launch&& launch) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    const uint64_t T  = side_slots(nR);
+    bool           ok = mtab.ensure(T * 8) && mcount.ensure(nc * 8);
+    for (const SideBuf& b : own) ok = ok && b.buf->ensure(b.bytes);
+    if (!ok) {
+        set_last_error(std::string("hipMalloc failed (") + what + ")");
         return 4;
     }
     HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
-    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 8, stream));
+    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, nc * 8, stream));
+    for (const SideBuf& b : own)
+        HWBRJ_CHECK(hipMemsetD32Async((hipDeviceptr_t) b.buf->p, (int) b.fill, b.bytes / 4, stream));
     HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
     if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
-    if (nR && nS) {
-        Geometry g = last_g_;  // the counting join's filter (materialize follows it)
-        if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_mat_probe(dS, layout, nS, dR, mtab.as<unsigned long long>(), T - 1, out, cap,
-                         mcount.as<unsigned long long>(), g, slices.as<uint32_t>(),
-                         bitmap.as<uint32_t>(), d_tabs_, stream);
-    }
+    SideTable t{mtab.as<unsigned long long>(), T - 1, last_g_, slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_};
+    if (!have_filter_) t.g.mode = MODE_NOBLOOM;
+    launch(t, stream);
     HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
     HWBRJ_CHECK(hipGetLastError());
     HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
-    HWBRJ_CHECK(hipMemcpy(n, mcount.p, 8, hipMemcpyDeviceToHost));
+    HWBRJ_CHECK(hipMemcpy(c, mcount.p, nc * 8, hipMemcpyDeviceToHost));
     if (ms) {
         float f = 0;
         HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
@@ -1461,48 +1472,48 @@ int Engine::materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS
     return 0;
 }
 
+int Engine::materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
+                        uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout) {
+    return side_pass(dR, nR, layout, stream, "materialization table", {}, n, 1, ms,
+                     [&](const SideTable& t, hipStream_t s) {
+                         if (nR && nS)
+                             launch_pair_probe(dS, layout, nS, dR, t, 0u, 0u, nullptr, out, cap,
+                                               mcount.as<unsigned long long>(), s);
+                     });
+}
+
+int Engine::semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
+                      uint64_t* n, hipStream_t stream, double* ms, int layout) {
+    return side_pass(dR, nR, layout, stream, "existence table", {}, n, 1, ms,
+                     [&](const SideTable& t, hipStream_t s) {
+                         if (nS)
+                             launch_semi_probe(dS, layout, nS, t, semi.anti ? 1u : 0u, semi.out, semi.cap,
+                                               mcount.as<unsigned long long>(), s);
+                     });
+}
+
 int Engine::outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
                        uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout) {
-    HWBRJ_CHECK(hipSetDevice(device_));
-    if (!stream) stream = own_stream_;
-    uint64_t T = 2;
-    while (T < 2 * nR) T <<= 1;
     tab_.state = kTabOther;  // (an outer join's tables are not read back, in this mode either)
-    const size_t fbytes = (size_t) std::max<uint64_t>(T / 8, 4);  // one bit per table slot
-    if (!mtab.ensure(T * 8) || !mcount.ensure(24) || (outer.keep_r && !smark.ensure(fbytes))) {
-        set_last_error("hipMalloc failed (outer join table)");
-        return 4;
-    }
-    HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
-    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 24, stream));
-    if (outer.keep_r) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, fbytes, stream));
-    HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
-    uint32_t* rflag = outer.keep_r ? smark.as<uint32_t>() : nullptr;
-    if (nS) {
-        Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
-        if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_outer_probe(dS, layout, nS, dR, mtab.as<unsigned long long>(), T - 1, outer.keep_s ? 1u : 0u,
-                           outer.null_pay, rflag, outer.out, outer.cap, mcount.as<unsigned long long>(), g,
-                           slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_, stream);
-    }
-    if (outer.keep_r && nR)
-        launch_outer_rtab(dR, layout, mtab.as<unsigned long long>(), T, rflag, outer.null_pay, outer.out, outer.cap,
-                          mcount.as<unsigned long long>(), stream);
-    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
-    HWBRJ_CHECK(hipGetLastError());
-    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
-    uint64_t c[3];
-    HWBRJ_CHECK(hipMemcpy(c, mcount.p, sizeof(c), hipMemcpyDeviceToHost));
+    const size_t fbytes = (size_t) std::max<uint64_t>(side_slots(nR) / 8, 4);  // one bit per table slot
+    std::vector<SideBuf> own;
+    if (outer.keep_r) own.push_back({&smark, fbytes, 0u});
+    uint64_t  c[3];
+    const int rc = side_pass(
+        dR, nR, layout, stream, "outer join table", own, c, 3, ms, [&](const SideTable& t, hipStream_t s) {
+            uint32_t*           rflag = outer.keep_r ? smark.as<uint32_t>() : nullptr;
+            unsigned long long* cnt   = mcount.as<unsigned long long>();
+            if (nS)
+                launch_pair_probe(dS, layout, nS, dR, t, outer.keep_s ? 1u : 0u, outer.null_pay, rflag, outer.out,
+                                  outer.cap, cnt, s);
+            if (outer.keep_r && nR)
+                launch_outer_rtab(dR, layout, t.tab, t.mask + 1, rflag, outer.null_pay, outer.out, outer.cap, cnt, s);
+        });
+    if (rc) return rc;
     *n     = c[0];
     cls[0] = c[0] - c[1] - c[2];
     cls[1] = c[1];
     cls[2] = c[2];
-    if (ms) {
-        float f = 0;
-        HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
-        *ms = f;
-    }
     return 0;
 }
 
@@ -1512,88 +1523,24 @@ int Engine::group_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         set_last_error("key columns: a group join needs S's value column");
         return 2;
     }
-    HWBRJ_CHECK(hipSetDevice(device_));
-    if (!stream) stream = own_stream_;
-    uint64_t T = 2;
-    while (T < 2 * nR) T <<= 1;
     tab_.state = kTabOther;  // (a group join's tables are not read back, in this mode either)
     const size_t rows = (size_t) std::max<uint64_t>(nR, 1);  // one count and one sum (or min and max) per R row
     const bool   minmax = group.agg == GRP_COUNT_MINMAX;
-    if (!mtab.ensure(T * 8) || !mcount.ensure(16) || !gcnt.ensure(rows * 4) ||
-        (minmax ? !gmin.ensure(rows * 4) || !gmax.ensure(rows * 4) : !gsum.ensure(rows * 8))) {
-        set_last_error("hipMalloc failed (group join table)");
-        return 4;
-    }
-    HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
-    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 16, stream));
-    HWBRJ_CHECK(hipMemsetAsync(gcnt.p, 0, rows * 4, stream));
-    if (minmax) launch_group_minmax_init(gmin.as<int32_t>(), gmax.as<int32_t>(), rows, stream);
-    else HWBRJ_CHECK(hipMemsetAsync(gsum.p, 0, rows * 8, stream));
-    HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
-    if (nR && nS) {
-        Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
-        if (!have_filter_) g.mode = MODE_NOBLOOM;
-        if (minmax)
-            launch_group_probe_minmax(dS, group.s_val, layout, nS, mtab.as<unsigned long long>(), T - 1,
-                                      gcnt.as<uint32_t>(), gmin.as<int32_t>(), gmax.as<int32_t>(), g,
-                                      slices.as<uint32_t>(), bitmap.as<uint32_t>(), d_tabs_, stream);
-        else
-            launch_group_probe(dS, group.s_val, layout, nS, mtab.as<unsigned long long>(), T - 1,
-                               gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), g, slices.as<uint32_t>(),
-                               bitmap.as<uint32_t>(), d_tabs_, stream);
-    }
-    if (nR && minmax)
-        launch_group_rows_minmax(dR, layout, nR, gcnt.as<uint32_t>(), gmin.as<int32_t>(), gmax.as<int32_t>(),
-                                 group.all ? 1u : 0u, group.out, group.cap, mcount.as<unsigned long long>(), stream);
-    else if (nR)
-        launch_group_rows(dR, layout, nR, gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), group.all ? 1u : 0u,
-                          group.out, group.cap, mcount.as<unsigned long long>(), stream);
-    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
-    HWBRJ_CHECK(hipGetLastError());
-    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
-    uint64_t c[2];
-    HWBRJ_CHECK(hipMemcpy(c, mcount.p, sizeof(c), hipMemcpyDeviceToHost));
+    std::vector<SideBuf> own{{&gcnt, rows * 4, 0u}};
+    if (minmax) own.insert(own.end(), {{&gmin, rows * 4, (uint32_t) INT32_MAX}, {&gmax, rows * 4, (uint32_t) INT32_MIN}});
+    else own.push_back({&gsum, rows * 8, 0u});
+    uint64_t  c[2];
+    const int rc = side_pass(dR, nR, layout, stream, "group join table", own, c, 2, ms,
+                                [&](const SideTable& t, hipStream_t s) {
+        const GroupAcc a{gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), gmin.as<int32_t>(), gmax.as<int32_t>()};
+        if (nR && nS) launch_group_probe(dS, group.s_val, layout, nS, t, a, group.agg, s);
+        if (nR)
+            launch_group_rows(dR, layout, nR, a, group.agg, group.all ? 1u : 0u, group.out, group.cap,
+                              mcount.as<unsigned long long>(), s);
+    });
+    if (rc) return rc;
     *n     = c[0];
     *pairs = c[1];
-    if (ms) {
-        float f = 0;
-        HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
-        *ms = f;
-    }
-    return 0;
-}
-
-int Engine::semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
-                      uint64_t* n, hipStream_t stream, double* ms, int layout) {
-    HWBRJ_CHECK(hipSetDevice(device_));
-    if (!stream) stream = own_stream_;
-    uint64_t T = 2;
-    while (T < 2 * nR) T <<= 1;
-    if (!mtab.ensure(T * 8) || !mcount.ensure(8)) {
-        set_last_error("hipMalloc failed (existence table)");
-        return 4;
-    }
-    HWBRJ_CHECK(hipMemsetAsync(mtab.p, 0, T * 8, stream));
-    HWBRJ_CHECK(hipMemsetAsync(mcount.p, 0, 8, stream));
-    HWBRJ_CHECK(hipEventRecord(ev_[0], stream));
-    if (nR) launch_mat_build(dR, layout, nR, mtab.as<unsigned long long>(), T - 1, stream);
-    if (nS) {
-        Geometry g = last_g_;  // the counting join's filter (the side pass follows it)
-        if (!have_filter_) g.mode = MODE_NOBLOOM;
-        launch_semi_probe(dS, layout, nS, mtab.as<unsigned long long>(), T - 1, semi.anti ? 1u : 0u, semi.out, semi.cap,
-                          mcount.as<unsigned long long>(), g, slices.as<uint32_t>(), bitmap.as<uint32_t>(),
-                          d_tabs_, stream);
-    }
-    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
-    HWBRJ_CHECK(hipGetLastError());
-    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
-    HWBRJ_CHECK(hipMemcpy(n, mcount.p, 8, hipMemcpyDeviceToHost));
-    if (ms) {
-        float f = 0;
-        HWBRJ_CHECK(hipEventElapsedTime(&f, ev_[0], ev_[8]));
-        *ms = f;
-    }
     return 0;
 }
 

@@ -157,17 +157,15 @@ class Engine {
     int  run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
                    hwbrj_stats_t* st, uint64_t* pairs, int layout = SRC_TUPLES);
-    // Its side pass after a counting join (global-bitmap mode): *n = rows, *pairs as above.
+    // The side passes after a counting join (global-bitmap mode; one skeleton: side_pass). *n = rows
+    // (all of them, also beyond the capacity); *pairs, cls as above; materialize: (R.payload, S.payload)
+    // of every match into out[0, cap). *ms = the side pass's device time.
     int  group_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const GroupReq& group,
                     uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
-    // Its side pass after a counting join (global-bitmap mode): *n = rows, cls as above.
     int  outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
                     uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout = SRC_TUPLES);
-    // Its side pass after a counting join (global-bitmap mode): *n = number of rows.
     int  semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
                    uint64_t* n, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
-    // Side pass after a counting join (global-bitmap mode): (R.payload, S.payload) of every match
-    // into out[0, cap); *n = number of pairs.
     int  materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
                      uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
     int  generate(uint2* d_out, uint64_t n, uint64_t offset, uint64_t count, uint32_t nthreads,
@@ -271,6 +269,14 @@ class Engine {
     hipEvent_t            pjEv_[2 * kPjDepth] = {};
 
   private:
+    struct SideBuf {  // a buffer of one kind's side pass: `bytes` of 32-bit words `fill` on entry
+        DevBuf*  buf;
+        size_t   bytes;
+        uint32_t fill;
+    };
+    template <class Launch>
+    int side_pass(const void* dR, uint64_t nR, int layout, hipStream_t stream, const char* what,
+                  const std::vector<SideBuf>& own, uint64_t* c, uint32_t nc, double* ms, Launch&& launch);
     void*        comm_       = nullptr;  // ncclComm_t of this device's rank (hwbrj_comm_init)
     int          comm_world_ = 1, comm_rank_ = 0;
     bool         bcast_      = false;
@@ -353,7 +359,7 @@ class Engine {
     PartSide R_, S_;
     DevBuf slices, bitmap, rjoin, rrun, surv, survcnt, survoff, dense, small;
     DevBuf bpos;        // basic k >= 2: R bit positions (k_bitpos)
-    DevBuf mtab, mcount;  // materialization (side pass): R table, pair counter
+    DevBuf mtab, mcount;  // the side passes: R table, counters
     // materializing pipeline: payload pools (chunk layout of R_.pool / S_.pool), R payloads of the
     // build sweeps, survivors' chunk positions
     DevBuf ppoolR, ppoolS, rpay, survpos;

@@ -217,14 +217,6 @@ struct SemiEmitParams {
     unsigned long long* count;
 };
 void   launch_semi_emit(const SemiEmitParams& p, uint32_t grid, hipStream_t st);
-// the existence join's side pass (global-bitmap mode): every S tuple against launch_mat_build's
-// table of R, stopping at the first hit; rows {key, payload} on a hit (anti = 0) or on none.
-// src (the side passes: here, launch_outer_probe / _rtab, launch_mat_build / _probe): SRC_TUPLES, or
-// SRC_KEYS: uint32 keys whose payload is the row index
-void   launch_semi_probe(const void* S, int src, uint64_t n, const unsigned long long* tab, uint64_t mask,
-                         uint32_t anti, uint2* out, uint64_t cap, unsigned long long* count,
-                         const Geometry& g, const uint32_t* slices, const uint32_t* bm,
-                         const CrcTables* tabs, hipStream_t st);
 
 // The outer join (k_join_outer): the materializing join's inputs and pairs (m), and
 //  - keep_s: every survivor with a partner marks its chunk position in `mark` (one bit per S chunk
@@ -255,18 +247,6 @@ struct OuterEmitParams {
     unsigned long long* n_s_only;
 };
 void   launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st);
-// The outer join's side pass (global-bitmap mode) over launch_mat_build's table of R: the pairs of
-// every S tuple (k_mat_probe's walk, the filter as a pre-test), {null_pay, S.payload} for an S tuple
-// without a partner (keep_s), and a bit per table slot that was hit (rflag, or nullptr);
-// cnt[0] += rows, cnt[1] += S-only rows. launch_outer_rtab then writes {R.payload, null_pay} of the
-// table's unflagged entries; cnt[0] and cnt[2] += those rows.
-void   launch_outer_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab,
-                          uint64_t mask, uint32_t keep_s, uint32_t null_pay, uint32_t* rflag, uint2* out,
-                          uint64_t cap, unsigned long long* cnt, const Geometry& g, const uint32_t* slices,
-                          const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
-void   launch_outer_rtab(const void* R, int src, const unsigned long long* tab, uint64_t slots,
-                         const uint32_t* rflag, uint32_t null_pay, uint2* out, uint64_t cap,
-                         unsigned long long* cnt, hipStream_t st);
 
 // The group join (k_join_group): the materializing join's inputs (m; m.out is not used), no pairs.
 // Every R tuple of a job accumulates, in LDS, the number of the job's survivors with its key and the
@@ -285,28 +265,6 @@ struct GroupJoinParams {
     unsigned long long* n_pairs;  // zero on entry
 };
 void   launch_join_group(const GroupJoinParams& p, uint32_t jobs, hipStream_t st);
-// The group join's side pass (global-bitmap mode) over launch_mat_build's table of R: every S tuple
-// (the filter as a pre-test) adds 1 to cnt[row] and its sign-extended payload to sum[row] of every
-// table entry with its key (cnt, sum: one element per R row, zero on entry). launch_group_rows then
-// writes the rows of R[0, n) (all of them, or those with cnt > 0) to out, up to cap;
-// res[0] += rows, res[1] += their counts.
-// src: SRC_TUPLES (Sv is not read), or SRC_KEYS: S and R are uint32 key columns, S's payloads the
-// uint32 value column Sv and R's payload the row index.
-void   launch_group_probe(const void* S, const void* Sv, int src, uint64_t n, const unsigned long long* tab,
-                          uint64_t mask, uint32_t* cnt, unsigned long long* sum, const Geometry& g,
-                          const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st);
-void   launch_group_rows(const void* R, int src, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
-                         uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st);
-// The side pass's min/max form: mn[row] and mx[row] (one int32 per R row, INT32_MAX and INT32_MIN
-// on entry: launch_group_minmax_init) take the payload of every matching S tuple.
-void   launch_group_minmax_init(int32_t* mn, int32_t* mx, uint64_t n, hipStream_t st);
-void   launch_group_probe_minmax(const void* S, const void* Sv, int src, uint64_t n,
-                                 const unsigned long long* tab, uint64_t mask, uint32_t* cnt, int32_t* mn,
-                                 int32_t* mx, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
-                                 const CrcTables* tabs, hipStream_t st);
-void   launch_group_rows_minmax(const void* R, int src, uint64_t n, const uint32_t* cnt, const int32_t* mn,
-                                const int32_t* mx, uint32_t all, uint4* out, uint64_t cap,
-                                unsigned long long* res, hipStream_t st);
 
 void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                   hipStream_t st);
@@ -368,14 +326,52 @@ struct PathConstants {
 };
 PathConstants path_constants();
 void   launch_join_mat(const MatJoinParams& p, uint32_t jobs, hipStream_t st);
-// result materialization (K12): R table build, S probe writing (R.payload, S.payload) pairs
+
+// The side passes of the global-bitmap mode (K12): every payload join there is a pass of its own
+// after a counting join. launch_mat_build fills an open-addressing table of R (zero on entry,
+// mask + 1 slots); every probe then streams S against it through one walk (side_walk), with the
+// counting join's filter as a pre-test (g.mode = MODE_NOBLOOM: none). 8-byte rows are appended to
+// out[0, cap) through one LDS stage per workgroup (SideStage); the counters also count the rows beyond
+// cap. src: SRC_TUPLES, or SRC_KEYS: uint32 key columns whose payload is the row index.
+struct SideTable {
+    const unsigned long long* tab;
+    uint64_t                  mask;
+    Geometry                  g;  // the filter: g, slices, bm, tabs
+    const uint32_t*           slices;
+    const uint32_t*           bm;
+    const CrcTables*          tabs;
+};
 void   launch_mat_build(const void* R, int src, uint64_t n, unsigned long long* tab, uint64_t mask,
                         hipStream_t st);
-// g/slices/bm/tabs: the last join's filter, used as a pre-test (g.mode = MODE_NOBLOOM: none)
-void   launch_mat_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab,
-                        uint64_t mask, uint2* out, uint64_t cap, unsigned long long* count,
-                        const Geometry& g, const uint32_t* slices, const uint32_t* bm,
-                        const CrcTables* tabs, hipStream_t st);
+// Pairs and the outer join: {R.payload, S.payload} of every match; {null_pay, S.payload} for an S
+// tuple without a partner (keep_s), and a bit per table slot that was hit (rflag, or nullptr);
+// cnt[0] += rows, cnt[1] += S-only rows. Pairs alone: keep_s = 0 and rflag = nullptr (cnt: one word).
+void   launch_pair_probe(const void* S, int src, uint64_t n, const void* R, const SideTable& t, uint32_t keep_s,
+                         uint32_t null_pay, uint32_t* rflag, uint2* out, uint64_t cap, unsigned long long* cnt,
+                         hipStream_t st);
+// {R.payload, null_pay} of the table's entries whose slot has no bit in rflag; cnt[0] and cnt[2] += rows
+void   launch_outer_rtab(const void* R, int src, const unsigned long long* tab, uint64_t slots,
+                         const uint32_t* rflag, uint32_t null_pay, uint2* out, uint64_t cap,
+                         unsigned long long* cnt, hipStream_t st);
+// The existence join: the walk stops at the first hit; rows {key, payload} on a hit (anti = 0) or on none
+void   launch_semi_probe(const void* S, int src, uint64_t n, const SideTable& t, uint32_t anti, uint2* out,
+                         uint64_t cap, unsigned long long* count, hipStream_t st);
+// The group joins (agg: GroupAgg): every S tuple adds 1 to cnt[row] and its sign-extended payload to
+// sum[row] (GRP_COUNT_SUM; both zero on entry), or takes mn[row] and mx[row] with it (GRP_COUNT_MINMAX;
+// INT32_MAX and INT32_MIN on entry), of every table entry with its key:
+// one element per R row. launch_group_rows then writes the rows of R[0, n) (all of them, or those
+// with cnt > 0) to out, up to cap; res[0] += rows, res[1] += their counts.
+// SRC_KEYS: S's payloads are the uint32 value column Sv (SRC_TUPLES: not read).
+struct GroupAcc {
+    uint32_t*           cnt;
+    unsigned long long* sum;  // GRP_COUNT_SUM
+    int32_t *           mn, *mx;  // GRP_COUNT_MINMAX
+};
+void   launch_group_probe(const void* S, const void* Sv, int src, uint64_t n, const SideTable& t,
+                          const GroupAcc& a, uint32_t agg, hipStream_t st);
+void   launch_group_rows(const void* R, int src, uint64_t n, const GroupAcc& a, uint32_t agg, uint32_t all,
+                         uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st);
+
 // partitioned multi-GPU join (K13): chunks in list order + rebased entries; receiver lists;
 // survivor runs of items packed per destination
 // partitioned join, device-side item tables: probe items -> region, survivor totals, their

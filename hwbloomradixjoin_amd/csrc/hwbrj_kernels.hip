@@ -15,7 +15,8 @@
 //   k_join_split splits (partition, sub) jobs with skewed survivor counts into parts.
 //   k_join       per job part: LDS bitmap (or hash table) of the R codes of (partition, sub),
 //                survivors count equal keys (bucket_chaining_join, :259-329).
-//   k_mat_*      result materialization (JOIN_RESULT_MATERIALIZE): {R.payload, S.payload} pairs.
+//   K12          the side passes of the global-bitmap mode: a table of R in HBM (k_mat_build) and
+//                one probe per payload join (pairs: JOIN_RESULT_MATERIALIZE's {R.payload, S.payload}).
 // Keys travel as 32-bit "codes" = crc32c(42, key): a bijection of the key, so code equality is key
 // equality and the code's low bits ARE the bloom block index.
 #include <hip/hip_runtime.h>
@@ -3466,18 +3467,20 @@ void launch_slice_fill(const uint32_t* pool, const uint32_t* list, const uint32_
     k_slice_fill<<<1u << g.log2F, 1024, lds, st>>>(pool, list, list_start, g, slices);
 }
 
-// ================================================================ K12: result materialization
-// (R.payload, S.payload) pairs of every match, the reference's JOIN_RESULT_MATERIALIZE output
-// (src/parallel_radix_join_bloom.c:307-312: key = R rid, payload = S rid). A separate pass after
-// the counting pipeline (which fixes the output size): an open-addressing table of R
-// (entry = (row + 1) << 32 | key, 0 = empty, linear probing), then every S tuple walks its probe
-// sequence; a wave takes its output range with one atomic and every matching lane writes its
-// pairs there (a second walk, taken only by lanes that matched).
+// ================================================ K12: the side passes of the global-bitmap mode
+// Every payload join of MODE_GLOBAL (pairs: the reference's JOIN_RESULT_MATERIALIZE output,
+// src/parallel_radix_join_bloom.c:307-312, key = R rid, payload = S rid; the existence, outer and
+// group joins alike) is a separate pass after the counting pipeline: an open-addressing table of R
+// in HBM (entry = (row + 1) << 32 | key, 0 = empty, linear probing: k_mat_build), then every S tuple
+// walks its probe sequence (side_walk, the last join's filter as a pre-test). Rows of 8 bytes go
+// through one LDS stage per workgroup (SideStage); the group joins accumulate per R row instead.
+// T: uint2 tuples, or uint32_t: key columns whose payload is the row index (elem_pay), S's values
+// of a group join in Sv (elem_key_val).
 __device__ __forceinline__ uint32_t mat_slot(uint32_t key, uint64_t mask) {
     return (uint32_t) (mix32(key * 0x9E3779B1u + 0x7F4A7C15u) & mask);
 }
 
-template <class T>  // (uint2 tuples or uint32_t keys, as k_build_global; the side-pass kernels below alike)
+template <class T>
 __global__ __launch_bounds__(256) void k_mat_build(const T* __restrict__ R, uint64_t n,
                                                     unsigned long long* __restrict__ tab,
                                                     uint64_t mask) {
@@ -3531,77 +3534,283 @@ __device__ __forceinline__ bool mat_filter(uint32_t key, const Geometry& g, cons
     return true;
 }
 
-constexpr uint32_t kMatBuf = 4096;  // pairs staged in LDS per workgroup before one output atomic
+// The walk of every probe: on_match(entry, slot) for each table entry with the key, in probe order,
+// until it returns true (the existence join stops at its first hit) or the sequence ends. A key the
+// filter rejects has no entry.
+template <class F>
+__device__ __forceinline__ void side_walk(const SideTable& t, uint32_t key, F&& on_match) {
+    if (!mat_filter(key, t.g, t.slices, t.bm, t.tabs)) return;
+    for (uint64_t h = mat_slot(key, t.mask);; h = (h + 1) & t.mask) {
+        const unsigned long long e = t.tab[h];
+        if (e == 0ull) break;
+        if ((uint32_t) e == key && on_match(e, h)) break;
+    }
+}
 
-template <class T>
-__global__ __launch_bounds__(256) void k_mat_probe(const T* __restrict__ S, uint64_t n,
-                                                    const T* __restrict__ R,
-                                                    const unsigned long long* __restrict__ tab,
-                                                    uint64_t mask, uint2* __restrict__ out,
-                                                    uint64_t cap, unsigned long long* __restrict__ count,
-                                                    Geometry g, const uint32_t* __restrict__ slices,
-                                                    const uint32_t* __restrict__ bm,
-                                                    const CrcTables* __restrict__ tabs) {
-    // Pairs are staged in LDS and appended to `out` with one atomic per flush (a single global
-    // counter taken per wave serialises at the L2); a burst beyond the stage takes one atomic per
-    // pair.
-    __shared__ uint2              buf[kMatBuf];
-    __shared__ uint32_t           nbuf;
-    __shared__ unsigned long long obase;
-    const uint64_t e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
-    if (threadIdx.x == 0) nbuf = 0;
-    __syncthreads();
-    auto flush = [&]() {
-        const uint32_t c = min(nbuf, kMatBuf);
-        if (threadIdx.x == 0) obase = c ? atomicAdd(count, (unsigned long long) c) : 0ull;
+// The row stage of a workgroup: rows are collected in LDS and appended to out[0, cap) with one
+// atomic on *count per flush (a single global counter taken per wave serialises at the L2); the
+// counter also counts the rows beyond cap. count2 (or nullptr) takes the same rows a second time
+// (the R-only class of k_outer_rtab). BURST: a thread may push any number of rows in a round, so the
+// stage is flushed from half full and a row that finds it full takes one atomic of its own; else a
+// thread pushes at most one row per round and the stage is flushed while a round still fits.
+constexpr uint32_t kMatBuf = 4096;  // rows of a stage
+
+struct StageLds {
+    uint2              buf[kMatBuf];
+    uint32_t           nbuf;
+    unsigned long long obase;
+};
+
+template <bool BURST>
+struct SideStage {
+    StageLds&           L;
+    uint2*              out;
+    uint64_t            cap;
+    unsigned long long* count;
+    unsigned long long* count2 = nullptr;
+
+    __device__ __forceinline__ void init() {
+        if (threadIdx.x == 0) L.nbuf = 0;
         __syncthreads();
-        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
-            if (obase + i < cap) out[obase + i] = buf[i];
-        __syncthreads();
-        if (threadIdx.x == 0) nbuf = 0;
-        __syncthreads();
-    };
-    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
-        const uint64_t i  = t0 + threadIdx.x;
-        if (i < e1) {
-            const uint2 st = elem_tuple(S[i], i);
-            if (mat_filter(st.x, g, slices, bm, tabs)) {
-                for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
-                    const unsigned long long e = tab[h];
-                    if (e == 0ull) break;
-                    if ((uint32_t) e != st.x) continue;
-                    const uint2    pr   = make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), st.y);  // (R rid, S rid)
-                    const uint32_t slot = atomicAdd(&nbuf, 1u);
-                    if (slot < kMatBuf) {
-                        buf[slot] = pr;
-                    } else {  // burst beyond the stage
-                        const unsigned long long o = atomicAdd(count, 1ull);
-                        if (o < cap) out[o] = pr;
-                    }
-                }
-            }
+    }
+    __device__ __forceinline__ void push(uint2 row) {
+        const uint32_t slot = atomicAdd(&L.nbuf, 1u);
+        if (!BURST || slot < kMatBuf) {  // (!BURST: nbuf + 256 <= kMatBuf after every end_round)
+            L.buf[slot] = row;
+        } else {
+            const unsigned long long o = atomicAdd(count, 1ull);
+            if (count2) atomicAdd(count2, 1ull);
+            if (o < cap) out[o] = row;
+        }
+    }
+    __device__ __forceinline__ void flush() {  // (uniform)
+        const uint32_t c = min(L.nbuf, kMatBuf);
+        if (threadIdx.x == 0) {
+            L.obase = c ? atomicAdd(count, (unsigned long long) c) : 0ull;
+            if (c && count2) atomicAdd(count2, (unsigned long long) c);
         }
         __syncthreads();
-        if (nbuf >= kMatBuf / 2) flush();  // uniform (read after the barrier)
+        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
+            if (L.obase + i < cap) out[L.obase + i] = L.buf[i];
+        __syncthreads();
+        if (threadIdx.x == 0) L.nbuf = 0;
+        __syncthreads();
     }
-    flush();
+    __device__ __forceinline__ void end_round() {  // after every round of the workgroup (uniform)
+        __syncthreads();
+        if (L.nbuf >= (BURST ? kMatBuf / 2 : kMatBuf - 255)) flush();  // uniform (read after the barrier)
+    }
+};
+
+// Pairs and the outer join: the rows of an S tuple are its pairs {R.payload, S.payload}. OUTER: or
+// {null_pay, S.payload} when it has none and keep_s is set (a tuple the filter rejects has none;
+// cnt[1] += those rows), and a hit table slot gets its bit in rflag (or nullptr). cnt[0] += rows.
+template <class T, bool OUTER>
+__global__ __launch_bounds__(256) void k_pair_probe(const T* __restrict__ S, uint64_t n,
+                                                     const T* __restrict__ R, SideTable t, uint32_t keep_s,
+                                                     uint32_t null_pay, uint32_t* __restrict__ rflag,
+                                                     uint2* __restrict__ out, uint64_t cap,
+                                                     unsigned long long* __restrict__ cnt) {
+    __shared__ StageLds L;
+    __shared__ uint32_t nso;
+    SideStage<true>     sg{L, out, cap, &cnt[0]};
+    const uint64_t      e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
+    if (OUTER && threadIdx.x == 0) nso = 0;
+    sg.init();
+    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
+        const uint64_t i = t0 + threadIdx.x;
+        if (i < e1) {
+            const uint2 st  = elem_tuple(S[i], i);
+            bool        any = false;
+            side_walk(t, st.x, [&](unsigned long long e, uint64_t h) {
+                any = true;
+                if (OUTER && rflag) atomicOr(&rflag[h >> 5], 1u << (h & 31u));
+                sg.push(make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), st.y));  // (R rid, S rid)
+                return false;
+            });
+            if (OUTER && !any && keep_s) {
+                atomicAdd(&nso, 1u);
+                sg.push(make_uint2(null_pay, st.y));
+            }
+        }
+        sg.end_round();
+    }
+    sg.flush();
+    if (OUTER && threadIdx.x == 0 && nso) atomicAdd(&cnt[1], (unsigned long long) nso);
 }
+
+// The existence join: the walk stops at the first hit; rows {key, payload} of the S tuples with a
+// hit (anti = 0) or without one.
+template <class T>
+__global__ __launch_bounds__(256) void k_semi_probe(const T* __restrict__ S, uint64_t n, SideTable t,
+                                                     uint32_t anti, uint2* __restrict__ out, uint64_t cap,
+                                                     unsigned long long* __restrict__ count) {
+    __shared__ StageLds L;
+    SideStage<false>    sg{L, out, cap, count};
+    const uint64_t      e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
+    sg.init();
+    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
+        const uint64_t i = t0 + threadIdx.x;
+        if (i < e1) {
+            const uint2 st  = elem_tuple(S[i], i);
+            uint32_t    hit = 0;
+            side_walk(t, st.x, [&](unsigned long long, uint64_t) {
+                hit = 1;
+                return true;
+            });
+            if (hit != anti) sg.push(st);
+        }
+        sg.end_round();
+    }
+    sg.flush();
+}
+
+// The outer join's R-only rows: {R.payload, null_pay} of the table's entries whose slot no S tuple
+// hit; cnt[0] and cnt[2] += those rows.
+template <class T>
+__global__ __launch_bounds__(256) void k_outer_rtab(const T* __restrict__ R,
+                                                     const unsigned long long* __restrict__ tab, uint64_t slots,
+                                                     const uint32_t* __restrict__ rflag, uint32_t null_pay,
+                                                     uint2* __restrict__ out, uint64_t cap,
+                                                     unsigned long long* __restrict__ cnt) {
+    __shared__ StageLds L;
+    SideStage<false>    sg{L, out, cap, &cnt[0], &cnt[2]};
+    const uint64_t      e0 = slots * blockIdx.x / gridDim.x, e1 = slots * (blockIdx.x + 1) / gridDim.x;
+    sg.init();
+    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
+        const uint64_t h = t0 + threadIdx.x;
+        if (h < e1) {
+            const unsigned long long e = tab[h];
+            if (e != 0ull && !((rflag[h >> 5] >> (h & 31u)) & 1u))
+                sg.push(make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), null_pay));
+        }
+        sg.end_round();
+    }
+    sg.flush();
+}
+
+// The group joins: a matching entry's R row gets the S tuple in its accumulators (device-scope
+// atomics): a.cnt and a.sum (AGG = GRP_COUNT_SUM, zero on entry) or a.cnt, a.mn and a.mx
+// (GRP_COUNT_MINMAX; mn and mx start at the identities INT32_MAX and INT32_MIN).
+template <class T, uint32_t AGG>
+__global__ __launch_bounds__(256) void k_group_probe(const T* __restrict__ S, uint64_t n, SideTable t, GroupAcc a,
+                                                      const uint32_t* __restrict__ Sv) {
+    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (; i < n; i += stride) {
+        const uint2 st = elem_key_val(S, Sv, i);
+        side_walk(t, st.x, [&](unsigned long long e, uint64_t) {
+            const uint64_t row = (e >> 32) - 1;
+            atomicAdd(&a.cnt[row], 1u);
+            if constexpr (AGG == GRP_COUNT_MINMAX) {
+                atomicMin(&a.mn[row], (int32_t) st.y);
+                atomicMax(&a.mx[row], (int32_t) st.y);
+            } else {
+                atomicAdd(&a.sum[row], (unsigned long long) (long long) (int32_t) st.y);
+            }
+            return false;
+        });
+    }
+}
+
+// One pass over R writes the rows {R.payload, count, sum} or {R.payload, count, min, max}: all of
+// them, or those with a count; a wave takes its output range with one atomic (and adds its counts
+// to the pair total with it). res[0] += rows, res[1] += their counts.
+template <class T, uint32_t AGG>
+__global__ __launch_bounds__(256) void k_group_rows(const T* __restrict__ R, uint64_t n, GroupAcc a, uint32_t all,
+                                                     uint4* __restrict__ out, uint64_t cap,
+                                                     unsigned long long* __restrict__ res) {
+    const int      lane   = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x; i0 < n; i0 += stride) {  // (wave-uniform trip count)
+        const uint64_t i = i0 + threadIdx.x;
+        const uint32_t c = i < n ? a.cnt[i] : 0u;
+        const bool     w = i < n && (all || c);
+        const uint64_t b = __ballot(w);
+        const uint64_t pairs = wave_sum_u64((uint64_t) c);
+        if (b == 0) continue;  // (wave-uniform; no row, so no pair either)
+        unsigned long long base = 0;
+        if (lane == 0) {
+            base = atomicAdd(&res[0], (unsigned long long) __builtin_popcountll(b));
+            if (pairs) atomicAdd(&res[1], (unsigned long long) pairs);
+        }
+        base = __shfl(base, 0, 64);
+        const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (w && o < cap) {
+            if constexpr (AGG == GRP_COUNT_MINMAX) {
+                out[o] = make_uint4(elem_pay(R[i], i), c, (uint32_t) a.mn[i], (uint32_t) a.mx[i]);
+            } else {
+                const unsigned long long sm = a.sum[i];
+                out[o] = make_uint4(elem_pay(R[i], i), c, (uint32_t) sm, (uint32_t) (sm >> 32));
+            }
+        }
+    }
+}
+
+// A side-pass launch on either layout: f(T{}) with T = uint32_t (SRC_KEYS) or uint2 (SRC_TUPLES)
+template <class F>
+static void by_layout(int src, F&& f) {
+    if (src == SRC_KEYS) f(uint32_t{});
+    else f(uint2{});
+}
+
+constexpr uint32_t kSideGrid = 2048;  // workgroups of every probe and row pass
 
 void launch_mat_build(const void* R, int src, uint64_t n, unsigned long long* tab, uint64_t mask, hipStream_t st) {
-    if (src == SRC_KEYS) k_mat_build<uint32_t><<<8192, 256, 0, st>>>((const uint32_t*) R, n, tab, mask);
-    else k_mat_build<uint2><<<8192, 256, 0, st>>>((const uint2*) R, n, tab, mask);
+    by_layout(src, [&](auto e) {
+        using T = decltype(e);
+        k_mat_build<T><<<8192, 256, 0, st>>>((const T*) R, n, tab, mask);
+    });
 }
 
-void launch_mat_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab,
-                      uint64_t mask, uint2* out, uint64_t cap, unsigned long long* count,
-                      const Geometry& g, const uint32_t* slices, const uint32_t* bm,
-                      const CrcTables* tabs, hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_mat_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, (const uint32_t*) R, tab, mask, out, cap,
-                                                    count, g, slices, bm, tabs);
-    else
-        k_mat_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, (const uint2*) R, tab, mask, out, cap, count, g,
-                                                 slices, bm, tabs);
+void launch_pair_probe(const void* S, int src, uint64_t n, const void* R, const SideTable& t, uint32_t keep_s,
+                       uint32_t null_pay, uint32_t* rflag, uint2* out, uint64_t cap, unsigned long long* cnt,
+                       hipStream_t st) {
+    by_layout(src, [&](auto e) {
+        using T = decltype(e);
+        if (keep_s || rflag)
+            k_pair_probe<T, true><<<kSideGrid, 256, 0, st>>>((const T*) S, n, (const T*) R, t, keep_s, null_pay, rflag,
+                                                            out, cap, cnt);
+        else
+            k_pair_probe<T, false><<<kSideGrid, 256, 0, st>>>((const T*) S, n, (const T*) R, t, 0u, 0u, nullptr, out,
+                                                             cap, cnt);
+    });
+}
+
+void launch_semi_probe(const void* S, int src, uint64_t n, const SideTable& t, uint32_t anti, uint2* out,
+                       uint64_t cap, unsigned long long* count, hipStream_t st) {
+    by_layout(src, [&](auto e) {
+        using T = decltype(e);
+        k_semi_probe<T><<<kSideGrid, 256, 0, st>>>((const T*) S, n, t, anti, out, cap, count);
+    });
+}
+
+void launch_outer_rtab(const void* R, int src, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
+                       uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st) {
+    by_layout(src, [&](auto e) {
+        using T = decltype(e);
+        k_outer_rtab<T><<<kSideGrid, 256, 0, st>>>((const T*) R, tab, slots, rflag, null_pay, out, cap, cnt);
+    });
+}
+
+void launch_group_probe(const void* S, const void* Sv, int src, uint64_t n, const SideTable& t, const GroupAcc& a,
+                        uint32_t agg, hipStream_t st) {
+    by_layout(src, [&](auto e) {
+        using T = decltype(e);
+        if (agg == GRP_COUNT_MINMAX)
+            k_group_probe<T, GRP_COUNT_MINMAX><<<kSideGrid, 256, 0, st>>>((const T*) S, n, t, a, (const uint32_t*) Sv);
+        else k_group_probe<T, GRP_COUNT_SUM><<<kSideGrid, 256, 0, st>>>((const T*) S, n, t, a, (const uint32_t*) Sv);
+    });
+}
+
+void launch_group_rows(const void* R, int src, uint64_t n, const GroupAcc& a, uint32_t agg, uint32_t all, uint4* out,
+                       uint64_t cap, unsigned long long* res, hipStream_t st) {
+    by_layout(src, [&](auto e) {
+        using T = decltype(e);
+        if (agg == GRP_COUNT_MINMAX)
+            k_group_rows<T, GRP_COUNT_MINMAX><<<kSideGrid, 256, 0, st>>>((const T*) R, n, a, all, out, cap, res);
+        else k_group_rows<T, GRP_COUNT_SUM><<<kSideGrid, 256, 0, st>>>((const T*) R, n, a, all, out, cap, res);
+    });
 }
 
 // ================================= K13: partitioned multi-GPU join (R and survivors exchanged)
@@ -4338,64 +4547,6 @@ void launch_semi_emit(const SemiEmitParams& p, uint32_t grid, hipStream_t st) {
     k_semi_emit<<<grid, 1024, lds, st>>>(p);
 }
 
-// The side pass of the global-bitmap mode (k_mat_probe's existence form): the walk of R's table
-// stops at the first hit; a tuple the filter rejects is a certain miss. Rows are staged in LDS and
-// appended with one atomic per flush (the stage always has room for a round of the workgroup).
-template <class T>
-__global__ __launch_bounds__(256) void k_semi_probe(const T* __restrict__ S, uint64_t n,
-                                                     const unsigned long long* __restrict__ tab,
-                                                     uint64_t mask, uint32_t anti, uint2* __restrict__ out,
-                                                     uint64_t cap, unsigned long long* __restrict__ count,
-                                                     Geometry g, const uint32_t* __restrict__ slices,
-                                                     const uint32_t* __restrict__ bm,
-                                                     const CrcTables* __restrict__ tabs) {
-    __shared__ uint2              buf[kMatBuf];
-    __shared__ uint32_t           nbuf;
-    __shared__ unsigned long long obase;
-    const uint64_t e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
-    if (threadIdx.x == 0) nbuf = 0;
-    __syncthreads();
-    auto flush = [&]() {
-        const uint32_t c = nbuf;
-        if (threadIdx.x == 0) obase = c ? atomicAdd(count, (unsigned long long) c) : 0ull;
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
-            if (obase + i < cap) out[obase + i] = buf[i];
-        __syncthreads();
-        if (threadIdx.x == 0) nbuf = 0;
-        __syncthreads();
-    };
-    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
-        const uint64_t i = t0 + threadIdx.x;
-        if (i < e1) {
-            const uint2 st  = elem_tuple(S[i], i);
-            uint32_t    hit = 0;
-            if (mat_filter(st.x, g, slices, bm, tabs))
-                for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
-                    const unsigned long long e = tab[h];
-                    if (e == 0ull) break;
-                    if ((uint32_t) e == st.x) {
-                        hit = 1;
-                        break;
-                    }
-                }
-            if (hit != anti) buf[atomicAdd(&nbuf, 1u)] = st;  // (nbuf + 256 <= kMatBuf: the flush below)
-        }
-        __syncthreads();
-        if (nbuf > kMatBuf - 256) flush();  // uniform (read after the barrier)
-    }
-    flush();
-}
-
-void launch_semi_probe(const void* S, int src, uint64_t n, const unsigned long long* tab, uint64_t mask, uint32_t anti,
-                       uint2* out, uint64_t cap, unsigned long long* count, const Geometry& g,
-                       const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_semi_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, tab, mask, anti, out, cap, count, g, slices,
-                                                     bm, tabs);
-    else k_semi_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, tab, mask, anti, out, cap, count, g, slices, bm, tabs);
-}
-
 // ================================================================= K10o: the outer join
 // k_join_mat's job (payload_job) with the pair-writing policy's marks and R flags on (PairPolicy).
 // KR = keep_r at compile time. Without it the kernel is k_join_mat plus the marks and keeps its
@@ -4485,129 +4636,6 @@ void launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st) 
     const size_t lds = (size_t) kSeBatch * 32 * sizeof(uint2);
     (void) hipFuncSetAttribute((const void*) &k_outer_emit, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
     k_outer_emit<<<grid, 1024, lds, st>>>(p);
-}
-
-// The outer join's side pass (global-bitmap mode), k_mat_probe's outer form: the rows of an S tuple
-// are its pairs, or {null, S.payload} when it has none (a tuple the filter rejects has none); a hit
-// table slot gets its bit in rflag. Rows are staged in LDS as in k_mat_probe.
-template <class T>
-__global__ __launch_bounds__(256) void k_outer_probe(const T* __restrict__ S, uint64_t n,
-                                                      const T* __restrict__ R,
-                                                      const unsigned long long* __restrict__ tab,
-                                                      uint64_t mask, uint32_t keep_s, uint32_t null_pay,
-                                                      uint32_t* __restrict__ rflag, uint2* __restrict__ out,
-                                                      uint64_t cap, unsigned long long* __restrict__ cnt,
-                                                      Geometry g, const uint32_t* __restrict__ slices,
-                                                      const uint32_t* __restrict__ bm,
-                                                      const CrcTables* __restrict__ tabs) {
-    __shared__ uint2              buf[kMatBuf];
-    __shared__ uint32_t           nbuf, nso;
-    __shared__ unsigned long long obase;
-    const uint64_t e0 = n * blockIdx.x / gridDim.x, e1 = n * (blockIdx.x + 1) / gridDim.x;
-    if (threadIdx.x == 0) nbuf = nso = 0;
-    __syncthreads();
-    auto flush = [&]() {
-        const uint32_t c = min(nbuf, kMatBuf);
-        if (threadIdx.x == 0) obase = c ? atomicAdd(&cnt[0], (unsigned long long) c) : 0ull;
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
-            if (obase + i < cap) out[obase + i] = buf[i];
-        __syncthreads();
-        if (threadIdx.x == 0) nbuf = 0;
-        __syncthreads();
-    };
-    auto push = [&](uint2 row) {
-        const uint32_t slot = atomicAdd(&nbuf, 1u);
-        if (slot < kMatBuf) {
-            buf[slot] = row;
-        } else {  // burst beyond the stage
-            const unsigned long long o = atomicAdd(&cnt[0], 1ull);
-            if (o < cap) out[o] = row;
-        }
-    };
-    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
-        const uint64_t i = t0 + threadIdx.x;
-        if (i < e1) {
-            const uint2 st  = elem_tuple(S[i], i);
-            bool        any = false;
-            if (mat_filter(st.x, g, slices, bm, tabs)) {
-                for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
-                    const unsigned long long e = tab[h];
-                    if (e == 0ull) break;
-                    if ((uint32_t) e != st.x) continue;
-                    any = true;
-                    if (rflag) atomicOr(&rflag[h >> 5], 1u << (h & 31u));
-                    push(make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), st.y));
-                }
-            }
-            if (!any && keep_s) {
-                atomicAdd(&nso, 1u);
-                push(make_uint2(null_pay, st.y));
-            }
-        }
-        __syncthreads();
-        if (nbuf >= kMatBuf / 2) flush();  // uniform (read after the barrier)
-    }
-    flush();
-    if (threadIdx.x == 0 && nso) atomicAdd(&cnt[1], (unsigned long long) nso);
-}
-
-// {R.payload, null} of the table's entries whose slot no S tuple hit, staged like k_semi_probe's rows
-template <class T>
-__global__ __launch_bounds__(256) void k_outer_rtab(const T* __restrict__ R,
-                                                     const unsigned long long* __restrict__ tab, uint64_t slots,
-                                                     const uint32_t* __restrict__ rflag, uint32_t null_pay,
-                                                     uint2* __restrict__ out, uint64_t cap,
-                                                     unsigned long long* __restrict__ cnt) {
-    __shared__ uint2              buf[kMatBuf];
-    __shared__ uint32_t           nbuf;
-    __shared__ unsigned long long obase;
-    const uint64_t e0 = slots * blockIdx.x / gridDim.x, e1 = slots * (blockIdx.x + 1) / gridDim.x;
-    if (threadIdx.x == 0) nbuf = 0;
-    __syncthreads();
-    auto flush = [&]() {
-        const uint32_t c = nbuf;
-        if (threadIdx.x == 0) {
-            obase = c ? atomicAdd(&cnt[0], (unsigned long long) c) : 0ull;
-            if (c) atomicAdd(&cnt[2], (unsigned long long) c);
-        }
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
-            if (obase + i < cap) out[obase + i] = buf[i];
-        __syncthreads();
-        if (threadIdx.x == 0) nbuf = 0;
-        __syncthreads();
-    };
-    for (uint64_t t0 = e0; t0 < e1; t0 += blockDim.x) {
-        const uint64_t h = t0 + threadIdx.x;
-        if (h < e1) {
-            const unsigned long long e = tab[h];
-            if (e != 0ull && !((rflag[h >> 5] >> (h & 31u)) & 1u))  // (nbuf + 256 <= kMatBuf)
-                buf[atomicAdd(&nbuf, 1u)] = make_uint2(elem_pay(R[(e >> 32) - 1], (e >> 32) - 1), null_pay);
-        }
-        __syncthreads();
-        if (nbuf > kMatBuf - 256) flush();  // uniform (read after the barrier)
-    }
-    flush();
-}
-
-void launch_outer_probe(const void* S, int src, uint64_t n, const void* R, const unsigned long long* tab, uint64_t mask,
-                        uint32_t keep_s, uint32_t null_pay, uint32_t* rflag, uint2* out, uint64_t cap,
-                        unsigned long long* cnt, const Geometry& g, const uint32_t* slices, const uint32_t* bm,
-                        const CrcTables* tabs, hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_outer_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, (const uint32_t*) R, tab, mask, keep_s,
-                                                      null_pay, rflag, out, cap, cnt, g, slices, bm, tabs);
-    else
-        k_outer_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, (const uint2*) R, tab, mask, keep_s, null_pay,
-                                                   rflag, out, cap, cnt, g, slices, bm, tabs);
-}
-
-void launch_outer_rtab(const void* R, int src, const unsigned long long* tab, uint64_t slots, const uint32_t* rflag,
-                       uint32_t null_pay, uint2* out, uint64_t cap, unsigned long long* cnt, hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_outer_rtab<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) R, tab, slots, rflag, null_pay, out, cap, cnt);
-    else k_outer_rtab<uint2><<<2048, 256, 0, st>>>((const uint2*) R, tab, slots, rflag, null_pay, out, cap, cnt);
 }
 
 // ================================================================= K10g: the group join
@@ -4765,169 +4793,6 @@ void launch_join_group(const GroupJoinParams& p0, uint32_t jobs, hipStream_t st)
         if (p.all) k_join_group<true, GRP_COUNT_SUM><<<jobs, kMatThreads, 0, st>>>(p);
         else k_join_group<false, GRP_COUNT_SUM><<<jobs, kMatThreads, 0, st>>>(p);
     }
-}
-
-// The group join's side pass (global-bitmap mode): k_mat_probe's walk with the filter as a pre-test;
-// a matching entry's R row gets the S tuple in its two accumulators (device-scope atomics).
-// T: uint2 tuples, or uint32_t: key columns, S's values in Sv (elem_key_val) and R's payload its row
-// index (elem_pay), as the other side-pass kernels. Sv comes last: the tuple form keeps its arguments.
-template <class T>
-__global__ __launch_bounds__(256) void k_group_probe(const T* __restrict__ S, uint64_t n,
-                                                      const unsigned long long* __restrict__ tab,
-                                                      uint64_t mask, uint32_t* __restrict__ cnt,
-                                                      unsigned long long* __restrict__ sum, Geometry g,
-                                                      const uint32_t* __restrict__ slices,
-                                                      const uint32_t* __restrict__ bm,
-                                                      const CrcTables* __restrict__ tabs,
-                                                      const uint32_t* __restrict__ Sv) {
-    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        const uint2 st = elem_key_val(S, Sv, i);
-        if (!mat_filter(st.x, g, slices, bm, tabs)) continue;
-        for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
-            const unsigned long long e = tab[h];
-            if (e == 0ull) break;
-            if ((uint32_t) e != st.x) continue;
-            const uint64_t row = (e >> 32) - 1;
-            atomicAdd(&cnt[row], 1u);
-            atomicAdd(&sum[row], (unsigned long long) (long long) (int32_t) st.y);
-        }
-    }
-}
-
-// One pass over R writes the rows; a wave takes its output range with one atomic (and adds its
-// counts to the pair total with it).
-template <class T>
-__global__ __launch_bounds__(256) void k_group_rows(const T* __restrict__ R, uint64_t n,
-                                                     const uint32_t* __restrict__ cnt,
-                                                     const unsigned long long* __restrict__ sum, uint32_t all,
-                                                     uint4* __restrict__ out, uint64_t cap,
-                                                     unsigned long long* __restrict__ res) {
-    const int      lane   = threadIdx.x & 63;
-    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
-    for (uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x; i0 < n; i0 += stride) {  // (wave-uniform trip count)
-        const uint64_t i = i0 + threadIdx.x;
-        const uint32_t c = i < n ? cnt[i] : 0u;
-        const bool     w = i < n && (all || c);
-        const uint64_t b = __ballot(w);
-        const uint64_t pairs = wave_sum_u64((uint64_t) c);
-        if (b == 0) continue;  // (wave-uniform; no row, so no pair either)
-        unsigned long long base = 0;
-        if (lane == 0) {
-            base = atomicAdd(&res[0], (unsigned long long) __builtin_popcountll(b));
-            if (pairs) atomicAdd(&res[1], (unsigned long long) pairs);
-        }
-        base = __shfl(base, 0, 64);
-        const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
-        if (w && o < cap) {
-            const unsigned long long sm = sum[i];
-            out[o] = make_uint4(elem_pay(R[i], i), c, (uint32_t) sm, (uint32_t) (sm >> 32));
-        }
-    }
-}
-
-void launch_group_probe(const void* S, const void* Sv, int src, uint64_t n, const unsigned long long* tab,
-                        uint64_t mask, uint32_t* cnt, unsigned long long* sum, const Geometry& g,
-                        const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_group_probe<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, tab, mask, cnt, sum, g, slices, bm, tabs,
-                                                      (const uint32_t*) Sv);
-    else k_group_probe<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, tab, mask, cnt, sum, g, slices, bm, tabs, nullptr);
-}
-
-void launch_group_rows(const void* R, int src, uint64_t n, const uint32_t* cnt, const unsigned long long* sum,
-                       uint32_t all, uint4* out, uint64_t cap, unsigned long long* res, hipStream_t st) {
-    if (src == SRC_KEYS) k_group_rows<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) R, n, cnt, sum, all, out, cap, res);
-    else k_group_rows<uint2><<<2048, 256, 0, st>>>((const uint2*) R, n, cnt, sum, all, out, cap, res);
-}
-
-// The side pass's min/max form: the same walk and the same row pass over {cnt, mn, mx}; mn and mx
-// start at the identities (a byte memset cannot write INT32_MAX).
-__global__ __launch_bounds__(256) void k_group_minmax_init(int32_t* __restrict__ mn, int32_t* __restrict__ mx,
-                                                            uint64_t n) {
-    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        mn[i] = INT32_MAX;
-        mx[i] = INT32_MIN;
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void k_group_probe_minmax(const T* __restrict__ S, uint64_t n,
-                                                             const unsigned long long* __restrict__ tab,
-                                                             uint64_t mask, uint32_t* __restrict__ cnt,
-                                                             int32_t* __restrict__ mn, int32_t* __restrict__ mx,
-                                                             Geometry g, const uint32_t* __restrict__ slices,
-                                                             const uint32_t* __restrict__ bm,
-                                                             const CrcTables* __restrict__ tabs,
-                                                             const uint32_t* __restrict__ Sv) {
-    uint64_t       i      = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x;
-    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        const uint2 st = elem_key_val(S, Sv, i);
-        if (!mat_filter(st.x, g, slices, bm, tabs)) continue;
-        for (uint64_t h = mat_slot(st.x, mask);; h = (h + 1) & mask) {
-            const unsigned long long e = tab[h];
-            if (e == 0ull) break;
-            if ((uint32_t) e != st.x) continue;
-            const uint64_t row = (e >> 32) - 1;
-            atomicAdd(&cnt[row], 1u);
-            atomicMin(&mn[row], (int32_t) st.y);
-            atomicMax(&mx[row], (int32_t) st.y);
-        }
-    }
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void k_group_rows_minmax(const T* __restrict__ R, uint64_t n,
-                                                            const uint32_t* __restrict__ cnt,
-                                                            const int32_t* __restrict__ mn,
-                                                            const int32_t* __restrict__ mx, uint32_t all,
-                                                            uint4* __restrict__ out, uint64_t cap,
-                                                            unsigned long long* __restrict__ res) {
-    const int      lane   = threadIdx.x & 63;
-    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
-    for (uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x; i0 < n; i0 += stride) {  // (wave-uniform trip count)
-        const uint64_t i = i0 + threadIdx.x;
-        const uint32_t c = i < n ? cnt[i] : 0u;
-        const bool     w = i < n && (all || c);
-        const uint64_t b = __ballot(w);
-        const uint64_t pairs = wave_sum_u64((uint64_t) c);
-        if (b == 0) continue;  // (wave-uniform; no row, so no pair either)
-        unsigned long long base = 0;
-        if (lane == 0) {
-            base = atomicAdd(&res[0], (unsigned long long) __builtin_popcountll(b));
-            if (pairs) atomicAdd(&res[1], (unsigned long long) pairs);
-        }
-        base = __shfl(base, 0, 64);
-        const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
-        if (w && o < cap) out[o] = make_uint4(elem_pay(R[i], i), c, (uint32_t) mn[i], (uint32_t) mx[i]);
-    }
-}
-
-void launch_group_minmax_init(int32_t* mn, int32_t* mx, uint64_t n, hipStream_t st) {
-    k_group_minmax_init<<<2048, 256, 0, st>>>(mn, mx, n);
-}
-
-void launch_group_probe_minmax(const void* S, const void* Sv, int src, uint64_t n, const unsigned long long* tab,
-                               uint64_t mask, uint32_t* cnt, int32_t* mn, int32_t* mx, const Geometry& g,
-                               const uint32_t* slices, const uint32_t* bm, const CrcTables* tabs, hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_group_probe_minmax<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) S, n, tab, mask, cnt, mn, mx, g, slices,
-                                                             bm, tabs, (const uint32_t*) Sv);
-    else
-        k_group_probe_minmax<uint2><<<2048, 256, 0, st>>>((const uint2*) S, n, tab, mask, cnt, mn, mx, g, slices, bm,
-                                                          tabs, nullptr);
-}
-
-void launch_group_rows_minmax(const void* R, int src, uint64_t n, const uint32_t* cnt, const int32_t* mn,
-                              const int32_t* mx, uint32_t all, uint4* out, uint64_t cap, unsigned long long* res,
-                              hipStream_t st) {
-    if (src == SRC_KEYS)
-        k_group_rows_minmax<uint32_t><<<2048, 256, 0, st>>>((const uint32_t*) R, n, cnt, mn, mx, all, out, cap, res);
-    else k_group_rows_minmax<uint2><<<2048, 256, 0, st>>>((const uint2*) R, n, cnt, mn, mx, all, out, cap, res);
 }
 
 // ===================================================================== launch wrappers
