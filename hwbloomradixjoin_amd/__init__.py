@@ -19,7 +19,7 @@ import numpy as np
 __all__ = [
     "BASIC", "BLOCKED", "SECTORIZED", "BloomFilterArgs", "Relation", "Result", "Stats",
     "BPRO", "PRO", "join_materialize_device", "semi_join_device", "JOIN_SEMI", "JOIN_ANTI", "outer_join_device", "OUTER_S", "OUTER_R", "OUTER_FULL", "group_join_device", "GROUP_MATCHED", "GROUP_ALL", "GroupRows", "group_minmax_join_device", "GroupMinMaxRows", "group_join_keys_device", "group_minmax_join_keys_device", "set_materialize", "set_gpus", "BPRH", "BPRHO", "BRJ", "PRH", "PRHO", "RJ", "assert_args", "join_device", "join_device_async", "join_keys_device", "join_keys_device_async", "join_keys_pairs_device", "semi_join_keys_device", "outer_join_keys_device", "join_wait", "join_wait_all", "set_async_timing", "generate_device", "generate_device_range",
-    "generate_host", "nonunique_threshold", "create_relation_nonunique",
+    "pack_validity", "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
     "export_filter", "tables_info", "tables_read", "hash_crc", "hash_crapwow", "lib", "LIB_PATH", "shard_range", "write_relation",
@@ -146,6 +146,12 @@ def lib() -> ctypes.CDLL:
             ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
             ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
             ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
+        # the validity-bitmap forms: the counterpart's arguments with d_Rvalid before nR, d_Svalid before nS
+        def with_valid(argtypes):
+            return [argtypes[0], ctypes.c_void_p, argtypes[1], argtypes[2], ctypes.c_void_p] + list(argtypes[3:])
+        for nm in ("hwbrj_join_keys", "hwbrj_join_keys_pairs", "hwbrj_join_keys_semi", "hwbrj_join_keys_outer"):
+            getattr(L, nm + "_nulls_device").restype = ctypes.c_int
+            getattr(L, nm + "_nulls_device").argtypes = with_valid(getattr(L, nm + "_device").argtypes)
         L.hwbrj_join_group_device.restype = ctypes.c_int
         L.hwbrj_join_group_device.argtypes = [
             ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
@@ -551,19 +557,77 @@ def _check_keys(Rk, Sk, stream, Sv=None):
         torch.cuda.current_stream(Rk.device).synchronize()
 
 
+def pack_validity(valid):
+    """The validity bitmap of a 1-D torch.bool tensor (True = valid), packed on its device with torch
+    ops: a torch.uint8 tensor in Arrow's layout (row i is bit i & 7 of byte i >> 3, LSB first),
+    padded with zero bits to a multiple of 4 bytes. What r_valid / s_valid of the join_keys_*
+    functions accept as is."""
+    import torch
+    if not isinstance(valid, torch.Tensor) or valid.dtype != torch.bool or valid.dim() != 1:
+        raise ValueError("pack_validity takes a 1-D torch.bool tensor")
+    n = valid.shape[0]
+    nbytes = (n + 31) // 32 * 4
+    bits = torch.zeros(nbytes * 8, dtype=torch.uint8, device=valid.device)
+    bits[:n] = valid
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=valid.device)
+    return (bits.view(nbytes, 8) * weights).sum(dim=1, dtype=torch.uint8)
+
+
+def _check_valid(name: str, valid, keys):
+    """r_valid / s_valid of a key column `keys`: None, a torch.bool tensor of len(keys) entries (packed
+    here by pack_validity) or a contiguous 1-D torch.uint8 bitmap of at least ceil(len(keys) / 8)
+    bytes on the keys' device, starting at a 4-byte boundary. Returns the bitmap tensor (the caller
+    keeps it alive over the call) or None."""
+    import torch
+    if valid is None:
+        return None
+    n = keys.shape[0] if isinstance(keys, torch.Tensor) and keys.dim() == 1 else 0
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{name} must be a torch.uint8 bitmap or a torch.bool tensor")
+    if valid.dim() != 1 or not valid.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous 1-D tensor")
+    if isinstance(keys, torch.Tensor) and valid.device != keys.device:
+        raise ValueError(f"{name} is on {valid.device} but its key column is on {keys.device}")
+    if valid.dtype == torch.bool:
+        if valid.shape[0] != n:
+            raise ValueError(f"{name} has {valid.shape[0]} entries for {n} keys")
+        return pack_validity(valid)
+    if valid.shape[0] < (n + 7) // 8:
+        raise ValueError(f"{name} has {valid.shape[0]} bytes, {n} keys need {(n + 7) // 8}")
+    if n and valid.data_ptr() % 4:
+        raise ValueError(f"{name} must start at a 4-byte boundary (a slice of a masked column: cut at "
+                         "multiples of 32 rows)")
+    return valid
+
+
+def _vptr(valid):
+    return _ptr(valid) if valid is not None and valid.numel() else None
+
+
 def join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None,
-                     algorithm: int = ALGO_PRO) -> Stats:
+                     algorithm: int = ALGO_PRO, *, r_valid=None, s_valid=None) -> Stats:
     """The counting join of join_device on key columns (hwbrj_join_keys_device): Rk, Sk are
     contiguous 1-D torch.int32 GPU tensors of keys, 16-byte aligned. No payloads are read, so a
     columnar caller needs no (N, 2) interleaving pass. A strided view such as T[:, 0] of a tuple
     tensor is refused: call .contiguous() first. args, stream, algorithm and the returned Stats
     are join_device's. With stream=None the join runs on the library's own stream after torch's
     current stream has finished (the kernel that cut the columns may still be running there); a
-    caller who passes a stream orders the columns' producers before the join on it."""
+    caller who passes a stream orders the columns' producers before the join on it.
+    r_valid, s_valid: the columns' validity (hwbrj_join_keys_nulls_device): None (no NULL keys), a
+    torch.bool tensor with one entry per key (True = valid), or a torch.uint8 bitmap as pack_validity
+    returns it (Arrow's layout, 4-byte aligned). A NULL key matches nothing, and Stats are the join's
+    on the valid rows. Partition-slice filters and no filter only."""
+    vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
     _check_keys(Rk, Sk, stream)
     st = _Stats()
     a = args._c() if args is not None else None
     sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    if vr is not None or vs is not None:
+        rc = lib().hwbrj_join_keys_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs), Sk.shape[0],
+                                                ctypes.byref(a) if a is not None else None, int(algorithm),
+                                                sp, ctypes.byref(st))
+        _err(rc, "hwbrj_join_keys_nulls_device")
+        return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
     rc = lib().hwbrj_join_keys_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0],
                                       ctypes.byref(a) if a is not None else None, int(algorithm),
                                       sp, ctypes.byref(st))
@@ -713,17 +777,20 @@ def _rows_out(call, what: str, capacity: int, n, device):
 
 
 def join_keys_pairs_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None,
-                           capacity: Optional[int] = None):
+                           capacity: Optional[int] = None, *, r_valid=None, s_valid=None):
     """(Stats, pairs, ms): join_materialize_device on key columns (hwbrj_join_keys_pairs_device).
     Rk, Sk are join_keys_device's columns; pairs is a (n, 2) int32 GPU tensor of {R row, S row},
     unordered: the gather maps into the caller's other columns, exactly the pairs
     join_materialize_device returns on {key, arange} tuples, without that interleaving pass. Both
     columns must have fewer than 2^31 rows. The stream rule is join_keys_device's. capacity: output
     rows to allocate (None: sized by a counting join_keys_device first; too small: the pipeline runs
-    again at the exact size)."""
+    again at the exact size). r_valid, s_valid: join_keys_device's (hwbrj_join_keys_pairs_nulls_device):
+    the pairs of the valid rows, as positions in the caller's columns."""
+    vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
+    masked = vr is not None or vs is not None
     _check_keys(Rk, Sk, stream)
     if capacity is None:
-        capacity = join_keys_device(Rk, Sk, args, stream).matches
+        capacity = join_keys_device(Rk, Sk, args, stream, r_valid=vr, s_valid=vs).matches
     a = args._c() if args is not None else None
     ap = ctypes.byref(a) if a is not None else None
     sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
@@ -732,20 +799,30 @@ def join_keys_pairs_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, strea
     ms = ctypes.c_double()
 
     def call(out, cap):
+        if masked:
+            return lib().hwbrj_join_keys_pairs_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs),
+                                                            Sk.shape[0], ap, out, cap, ctypes.byref(n), sp,
+                                                            ctypes.byref(st), ctypes.byref(ms))
         return lib().hwbrj_join_keys_pairs_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, out, cap,
                                                   ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
 
-    out = _rows_out(call, "hwbrj_join_keys_pairs_device", capacity, n, Rk.device)
+    out = _rows_out(call, "hwbrj_join_keys_pairs_nulls_device" if masked else "hwbrj_join_keys_pairs_device",
+                    capacity, n, Rk.device)
     return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_}), out, ms.value
 
 
 def semi_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, anti: bool = False, stream=None,
-                          capacity: Optional[int] = None):
+                          capacity: Optional[int] = None, *, r_valid=None, s_valid=None):
     """(Stats, rows, ms): semi_join_device on key columns (hwbrj_join_keys_semi_device). rows is a
     (n, 2) int32 GPU tensor of {key, S row}, unordered: rows[:, 1] is the gather map of the S rows
     whose key occurs in Rk (anti=True: does not occur). Stats, ms and capacity as in
     semi_join_device (None: one count-only call first); columns and the stream rule as in
-    join_keys_device, fewer than 2^31 rows each."""
+    join_keys_device, fewer than 2^31 rows each. r_valid, s_valid: join_keys_device's
+    (hwbrj_join_keys_semi_nulls_device): the valid S rows with a partner among the valid R rows;
+    anti=True: every other S row, the NULL ones included (their key field is what the column stores)."""
+    vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
+    masked = vr is not None or vs is not None
+    entry = "hwbrj_join_keys_semi_nulls_device" if masked else "hwbrj_join_keys_semi_device"
     _check_keys(Rk, Sk, stream)
     a = args._c() if args is not None else None
     ap = ctypes.byref(a) if a is not None else None
@@ -756,26 +833,35 @@ def semi_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, anti: 
     ms = ctypes.c_double()
 
     def call(out, cap):
+        if masked:
+            return lib().hwbrj_join_keys_semi_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs),
+                                                           Sk.shape[0], ap, kind, out, cap, ctypes.byref(n), sp,
+                                                           ctypes.byref(st), ctypes.byref(ms))
         return lib().hwbrj_join_keys_semi_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, kind, out, cap,
                                                  ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
 
     if capacity is None:
         rc = call(None, 0)  # count only
         if rc not in (0, 7):
-            _err(rc, "hwbrj_join_keys_semi_device")
+            _err(rc, entry)
         capacity = n.value
-    out = _rows_out(call, "hwbrj_join_keys_semi_device", capacity, n, Rk.device)
+    out = _rows_out(call, entry, capacity, n, Rk.device)
     return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_}), out, ms.value
 
 
 def outer_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, kind: int = OUTER_S, stream=None,
-                           capacity: Optional[int] = None):
+                           capacity: Optional[int] = None, *, r_valid=None, s_valid=None):
     """(Stats, rows, (n_inner, n_s_only, n_r_only), ms): outer_join_device on key columns
     (hwbrj_join_keys_outer_device). rows is a (n, 2) int32 GPU tensor of {R row, S row}, unordered,
     the missing side of an S-only or R-only row being -1 (a row index is never negative, so there is
     no null_payload). Stats, the class counts, ms and capacity as in outer_join_device (None: one
     count-only call first); columns and the stream rule as in join_keys_device, fewer than 2^31
-    rows each."""
+    rows each. r_valid, s_valid: join_keys_device's (hwbrj_join_keys_outer_nulls_device): a NULL S row
+    is an S-only row under OUTER_S / OUTER_FULL, a NULL R row an R-only row under OUTER_R / OUTER_FULL,
+    counted in their classes."""
+    vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
+    masked = vr is not None or vs is not None
+    entry = "hwbrj_join_keys_outer_nulls_device" if masked else "hwbrj_join_keys_outer_device"
     _check_keys(Rk, Sk, stream)
     a = args._c() if args is not None else None
     ap = ctypes.byref(a) if a is not None else None
@@ -786,15 +872,19 @@ def outer_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, kind:
     ms = ctypes.c_double()
 
     def call(out, cap):
+        if masked:
+            return lib().hwbrj_join_keys_outer_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs),
+                                                            Sk.shape[0], ap, int(kind), out, cap, ctypes.byref(n),
+                                                            cls, sp, ctypes.byref(st), ctypes.byref(ms))
         return lib().hwbrj_join_keys_outer_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, int(kind), out,
                                                   cap, ctypes.byref(n), cls, sp, ctypes.byref(st), ctypes.byref(ms))
 
     if capacity is None:
         rc = call(None, 0)  # count only
         if rc not in (0, 7):
-            _err(rc, "hwbrj_join_keys_outer_device")
+            _err(rc, entry)
         capacity = n.value
-    out = _rows_out(call, "hwbrj_join_keys_outer_device", capacity, n, Rk.device)
+    out = _rows_out(call, entry, capacity, n, Rk.device)
     stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
     return stats, out, (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
 

@@ -296,10 +296,11 @@ static int publish(const hwbrj_stats_t& st, uint64_t n, uint64_t capacity, hwbrj
 // columns and every payload is the row index).
 static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                              const bloom_filter_args_t* args, tuple_t* d_out, uint64_t cap, uint64_t* n,
-                             hipStream_t stream, hwbrj_stats_t* st, double* ms, int layout = SRC_TUPLES) {
+                             hipStream_t stream, hwbrj_stats_t* st, double* ms, int layout = SRC_TUPLES,
+                             const KeyMasks* masks = nullptr) {
     return pipeline_or_side_pass(
         e, d_R, nR, d_S, nS, args, stream, layout, st, n, ms,
-        [&] { return e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout); },
+        [&] { return e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout, masks); },
         [&] {
             *n = (uint64_t) st->matches;
             if (*n > cap) return 0;  // (the caller reports the capacity)
@@ -316,13 +317,14 @@ static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void
 
 static int join_pairs(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, tuple_t* d_out, uint64_t capacity, uint64_t* n_out,
-                      void* stream, hwbrj_stats_t* stats, double* ms_materialize, int layout) {
+                      void* stream, hwbrj_stats_t* stats, double* ms_materialize, int layout,
+                      const KeyMasks* masks = nullptr) {
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
     hwbrj_stats_t st;
     uint64_t      n  = 0;
     const int     rc = materialize_pairs(e, d_R, nR, d_S, nS, args, d_out, capacity, &n, (hipStream_t) stream,
-                                         &st, ms_materialize, layout);
+                                         &st, ms_materialize, layout, masks);
     return rc ? rc : publish(st, n, capacity, stats, n_out, "match");
 }
 
@@ -361,7 +363,8 @@ int hwbrj_join_keys_pairs_device(const int32_t* d_Rkeys, uint64_t nR, const int3
 // existence side pass.
 static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                      const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
-                     uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms, int layout) {
+                     uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms, int layout,
+                     const KeyMasks* masks = nullptr) {
     if (kind != HWBRJ_JOIN_SEMI && kind != HWBRJ_JOIN_ANTI) {  // (before any device call)
         set_last_error("unknown existence join kind (HWBRJ_JOIN_SEMI, HWBRJ_JOIN_ANTI)");
         return 2;
@@ -377,7 +380,7 @@ static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
     uint64_t      n  = 0;
     const int     rc = pipeline_or_side_pass(
         e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
-        [&] { return e->run_semi(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, layout); },
+        [&] { return e->run_semi(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, layout, masks); },
         [&] { return e->semi_side(d_R, nR, d_S, nS, req, &n, (hipStream_t) stream, ms, layout); });
     return rc ? rc : publish(st, n, capacity, stats, n_out, "row");
 }
@@ -401,7 +404,7 @@ int hwbrj_join_keys_semi_device(const int32_t* d_Rkeys, uint64_t nR, const int32
 static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
                       uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
-                      hwbrj_stats_t* stats, double* ms, int layout) {
+                      hwbrj_stats_t* stats, double* ms, int layout, const KeyMasks* masks = nullptr) {
     if (kind != HWBRJ_OUTER_S && kind != HWBRJ_OUTER_R && kind != HWBRJ_OUTER_FULL) {  // (before any device call)
         set_last_error("unknown outer join kind (HWBRJ_OUTER_S, HWBRJ_OUTER_R, HWBRJ_OUTER_FULL)");
         return 2;
@@ -418,7 +421,7 @@ static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS
     uint64_t      n = 0, cls[3] = {0, 0, 0};
     const int     rc = pipeline_or_side_pass(
         e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
-        [&] { return e->run_outer(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, cls, layout); },
+        [&] { return e->run_outer(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, cls, layout, masks); },
         [&] { return e->outer_side(d_R, nR, d_S, nS, req, &n, cls, (hipStream_t) stream, ms, layout); });
     if (rc) return rc;
     if (n_class)
@@ -442,6 +445,80 @@ int hwbrj_join_keys_outer_device(const int32_t* d_Rkeys, uint64_t nR, const int3
     if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
     return join_outer(d_Rkeys, nR, d_Skeys, nS, args, kind, -1, d_out, capacity, n_out, n_class, stream, stats, ms,
                       SRC_KEYS);
+}
+
+// Key columns with validity bitmaps (hwbrj_join_keys_*_nulls_device). Checked before any device call,
+// after the counterpart's own rules: a bitmap of a non-empty column starts at a 4-byte boundary
+// (k_null_rows reads it a dword at a time), and a bitmap needs a filter whose scatters are the only
+// readers of the columns (masks_supported: 9 otherwise). Both bitmaps NULL: neither check, and the
+// counterpart's call.
+static int masks_ok(const uint8_t* d_Rvalid, uint64_t nR, const uint8_t* d_Svalid, uint64_t nS,
+                    const bloom_filter_args_t* args, bool pl) {
+    if (!d_Rvalid && !d_Svalid) return 0;
+    const bool bad_r = d_Rvalid && nR && ((uintptr_t) d_Rvalid & 3u), bad_s = d_Svalid && nS && ((uintptr_t) d_Svalid & 3u);
+    if (bad_r || bad_s) {
+        set_last_error(std::string("validity bitmap of ") + (bad_r ? "R" : "S") +
+                       " is not 4-byte aligned (shard a masked column at multiples of 32 rows)");
+        return 2;
+    }
+    Geometry    g;
+    std::string err;
+    if (!plan_geometry(args, nR, &g, &err, pl)) {
+        set_last_error(err);
+        return 2;
+    }
+    if (!masks_supported(g)) {
+        set_last_error("validity bitmaps need partition slices (blocked/sectorized, basic k = 1, or no filter)");
+        return kRcMaskFilter;
+    }
+    return 0;
+}
+
+int hwbrj_join_keys_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR, const int32_t* d_Skeys,
+                                 const uint8_t* d_Svalid, uint64_t nS, const bloom_filter_args_t* args, int algorithm,
+                                 void* stream, hwbrj_stats_t* stats) {
+    if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
+    if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, false)) return rc;
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;
+    const KeyMasks km{d_Rvalid, d_Svalid};
+    return e->run(d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream, stats, algorithm, SRC_KEYS, &km);
+}
+
+int hwbrj_join_keys_pairs_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
+                                       const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                       const bloom_filter_args_t* args, tuple_t* d_out, uint64_t capacity,
+                                       uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
+    if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true)) return rc;
+    if (capacity > 0 && !d_out) {  // (after the bitmaps' checks, as in the semi and outer entries)
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    const KeyMasks km{d_Rvalid, d_Svalid};
+    return join_pairs(d_Rkeys, nR, d_Skeys, nS, args, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS, &km);
+}
+
+int hwbrj_join_keys_semi_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
+                                      const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                      const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
+                                      uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
+    if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true)) return rc;
+    const KeyMasks km{d_Rvalid, d_Svalid};
+    return join_semi(d_Rkeys, nR, d_Skeys, nS, args, kind, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS, &km);
+}
+
+int hwbrj_join_keys_outer_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
+                                       const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                       const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
+                                       uint64_t* n_out, uint64_t* n_class, void* stream, hwbrj_stats_t* stats,
+                                       double* ms) {
+    if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
+    if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true)) return rc;
+    const KeyMasks km{d_Rvalid, d_Svalid};
+    return join_outer(d_Rkeys, nR, d_Skeys, nS, args, kind, -1, d_out, capacity, n_out, n_class, stream, stats, ms,
+                      SRC_KEYS, &km);
 }
 
 // The group join: the materializing pipeline up to the join, then per-R-tuple accumulators instead of

@@ -322,8 +322,8 @@ uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
 
 int Engine::run(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                 const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind,
-                int layout) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind, nullptr, nullptr, nullptr, nullptr, layout);
+                int layout, const KeyMasks* masks) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind, nullptr, nullptr, nullptr, nullptr, layout, masks);
     return rc ? rc : wait(st);
 }
 
@@ -355,22 +355,22 @@ int Engine::reserve(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
 
 int Engine::run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
-                    hwbrj_stats_t* st, int layout) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, &mat, nullptr, nullptr, nullptr, layout);
+                    hwbrj_stats_t* st, int layout, const KeyMasks* masks) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, &mat, nullptr, nullptr, nullptr, layout, masks);
     return rc ? rc : wait(st);
 }
 
 int Engine::run_semi(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                      const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
-                     hwbrj_stats_t* st, int layout) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, &semi, nullptr, nullptr, layout);
+                     hwbrj_stats_t* st, int layout, const KeyMasks* masks) {
+    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, &semi, nullptr, nullptr, layout, masks);
     return rc ? rc : wait(st);
 }
 
 int Engine::run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                       const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
-                      hwbrj_stats_t* st, uint64_t cls[3], int layout) {
-    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, &outer, nullptr, layout);
+                      hwbrj_stats_t* st, uint64_t cls[3], int layout, const KeyMasks* masks) {
+    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, &outer, nullptr, layout, masks);
     if (rc == 0) rc = wait(st);
     if (rc) return rc;
     uint64_t c[2];  // (the join has completed; its ring slot is taken again by the next enqueue only)
@@ -400,10 +400,14 @@ int Engine::run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
 // value column group->s_val: the S payload scatter then reads SRC_KEYS_VAL). It selects the kernels
 // that read the relations; the partition words and payloads, and so everything from the pools on, do
 // not depend on it.
+// masks: validity bitmaps of key columns (KeyMasks). A side with a bitmap runs the SRC_KEYS_MASK
+// scatter, the other side the kernel it runs without masks; nothing after the scatters knows: a NULL
+// key is in no partition. The rows that NULL keys contribute themselves (anti, outer) come from
+// k_null_rows after the join's own emit kernels, through the same row counter.
 int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                     const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group,
-                    int layout) {
+                    int layout, const KeyMasks* masks) {
     const MatReq omat{outer ? outer->out : nullptr, outer ? outer->cap : group ? group->cap : 0};
     if (outer || group) mat = &omat;  // (the materializing pipeline up to the join)
     if (jkind < 0 || jkind > 2) {
@@ -428,11 +432,22 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         set_last_error("key columns: row indices are int32 (|R|, |S| < 2^31)");
         return 3;
     }
+    // the bitmap of each non-empty side, or nullptr (an empty column has no NULL rows)
+    const uint8_t* vR = masks && nR ? masks->r : nullptr;
+    const uint8_t* vS = masks && nS ? masks->s : nullptr;
+    if ((vR || vS) && (layout != SRC_KEYS || group)) {
+        set_last_error("validity bitmaps: key columns, not the group joins");
+        return 2;
+    }
     // what the S payload scatter reads: the layout, or S's key column with its value column
     const int layout_s = layout == SRC_KEYS && group ? SRC_KEYS_VAL : layout;
     if (!plan_geometry(args, nR, &g, &err, pl)) {
         set_last_error(err);
         return 2;
+    }
+    if ((vR || vS) && !masks_supported(g)) {  // (hwbrj_api.cpp refuses first, before any device call)
+        set_last_error("validity bitmaps need partition slices (blocked/sectorized, basic k = 1, or no filter)");
+        return kRcMaskFilter;
     }
     if (pl && g.mode == MODE_GLOBAL) {
         set_last_error("global-bitmap mode: materialized by the side pass");
@@ -547,11 +562,12 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
             ss.n     = nS;
             ss.n_dev = nullptr;
             if (layout_s == SRC_KEYS_VAL) ss.src_val = group->s_val;  // (shares seg_cnt's slot: not SRC_CODES)
+            if (vS) ss.valid = vS;                                    // (the same slot: never both)
         }
         S_.bind(&ss, capS);
         ss.ppool = pl ? ppoolS.as<uint32_t>() : nullptr;
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
-        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : layout_s, SIDE_S, G, st);
+        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : vS ? SRC_KEYS_MASK : layout_s, SIDE_S, G, st);
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
         if (marks) HWBRJ_CHECK(mark(4, st));
         index_side(S_, capS, g.log2F, CH, nseg, G, st);
@@ -596,7 +612,9 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     sp.n_dev      = nullptr;
     sp.ppool      = mat ? ppoolR.as<uint32_t>() : nullptr;
     R_.bind(&sp, capR);
-    launch_scatter(sp, layout, SIDE_R, G, stream);
+    if (vR) sp.valid = vR;
+    launch_scatter(sp, vR ? SRC_KEYS_MASK : layout, SIDE_R, G, stream);
+    sp.valid = nullptr;  // (seg_cnt's slot: the basic k >= 2 scatters below read it)
     HWBRJ_CHECK(mark(1, stream));
     index_side(R_, capR, g.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
@@ -769,6 +787,15 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                 oe.n_s_only   = cls + 1;
                 launch_outer_emit(oe, (uint32_t) cus_ * 2, stream);
             }
+            // NULL keys: S-only and R-only rows of the sides that are kept
+            if (outer->keep_s && vS)
+                launch_null_rows(NullRowsParams{vS, nullptr, nS, NULL_ROWS_S, outer->null_pay, outer->out, outer->cap,
+                                                (unsigned long long*) d_result, cls + 1},
+                                 (uint32_t) cus_ * 2, stream);
+            if (outer->keep_r && vR)
+                launch_null_rows(NullRowsParams{vR, nullptr, nR, NULL_ROWS_R, outer->null_pay, outer->out, outer->cap,
+                                                (unsigned long long*) d_result, cls},
+                                 (uint32_t) cus_ * 2, stream);
         } else if (group) {
             // the pair counter: u64 word 6 of the slot (as the outer join's class counters)
             unsigned long long* pairs = (unsigned long long*) sm + 6;
@@ -811,6 +838,10 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
             se.cap        = semi->cap;
             se.count      = (unsigned long long*) d_result;
             launch_semi_emit(se, (uint32_t) cus_ * 2, stream);
+            if (vS)  // a NULL key has no partner: {the stored key, row}
+                launch_null_rows(NullRowsParams{vS, (const uint32_t*) dS, nS, NULL_ROWS_ANTI, 0u, semi->out, semi->cap,
+                                                (unsigned long long*) d_result, nullptr},
+                                 (uint32_t) cus_ * 2, stream);
         }
     } else {
         launch_join(jp, NJ, jparts.as<uint32_t>() + NJ, stream);
@@ -857,6 +888,7 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         r.timed = rtimed;
         r.nS    = nS;
         r.g     = g;
+        r.s_masked = vS != nullptr;
         ring_push(r);
     }
     return 0;
@@ -1143,7 +1175,8 @@ int Engine::ring_collect() {
         const Geometry& g = r.g;
         hwbrj_stats_t   st;
         memset(&st, 0, sizeof(st));
-        st.filtered       = r.args ? h[2] : r.nS;
+        // (no filter: every S row survives, and k_probe's count is the valid rows of a masked S)
+        st.filtered       = r.args || r.s_masked ? h[2] : r.nS;
         st.matches        = (int64_t) h[0];
         st.mode           = g.mode;
         st.format         = g.s_format;

@@ -56,6 +56,23 @@ struct GroupReq {
     const void* s_val = nullptr;
 };
 
+// The validity bitmaps of two key columns (layout SRC_KEYS; include/hwbrj.h "validity bitmaps"): row
+// i of a column is bit i & 7 of byte i >> 3, set = valid; nullptr: that column has no NULL keys and
+// runs the kernels it runs without a KeyMasks. A NULL key joins nothing. Partition-slice modes and no
+// filter only (9 otherwise), and not the group joins.
+struct KeyMasks {
+    const uint8_t* r = nullptr;
+    const uint8_t* s = nullptr;
+};
+
+// The modes whose pass-1 scatters are the only readers of the raw relations (Engine::enqueue): a
+// bitmap beside a key column reaches every reader there. Not the global-bitmap mode (k_build_global,
+// k_probe_global and the side passes read the columns) nor basic k >= 2 (k_bitpos reads R).
+inline bool masks_supported(const Geometry& g) {
+    return g.mode == MODE_NOBLOOM || g.mode == MODE_SLICE_BLOCK || (g.mode == MODE_SLICE_BASIC && g.k == 1);
+}
+constexpr int kRcMaskFilter = 9;  // a validity bitmap with an unsupported filter (hwbrj_join_partitioned's code)
+
 struct DevBuf {
     void*  p     = nullptr;
     size_t bytes = 0;
@@ -106,7 +123,7 @@ class Engine {
     // uint32 key per element, 16-byte aligned). Only the kernels that read the relations differ.
     int  run(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
              const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind = 0,
-             int layout = SRC_TUPLES);
+             int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
     // Enqueue only (wait = false in run): wait() then waits for the last enqueued join.
     int  run_async(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, int jkind = 0,
@@ -137,19 +154,19 @@ class Engine {
     // as in run(), every element's payload its row index (|R|, |S| < 2^31).
     int  run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                  const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
-                 hwbrj_stats_t* st, int layout = SRC_TUPLES);
+                 hwbrj_stats_t* st, int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
     // The existence join (semi / anti) on the materializing pipeline's geometry: S carries its
     // payloads, R does not (k_join_semi, and k_semi_emit for anti). st->matches = rows (all of
     // them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
     int  run_semi(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                   const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
-                  hwbrj_stats_t* st, int layout = SRC_TUPLES);
+                  hwbrj_stats_t* st, int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
     // The outer join on the materializing pipeline (both payloads; k_join_outer, and k_outer_emit
     // when S is preserved). st->matches = rows (all of them, also beyond cap); cls = {inner, S-only,
     // R-only} rows. kRcMatGlobal: not for the global-bitmap mode.
     int  run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
-                   hwbrj_stats_t* st, uint64_t cls[3], int layout = SRC_TUPLES);
+                   hwbrj_stats_t* st, uint64_t cls[3], int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
     // The group join on the materializing pipeline up to the join, then k_join_group. st->matches =
     // rows (all of them, also beyond cap); *pairs = the sum of their counts. kRcMatGlobal: not for the
     // global-bitmap mode. layout SRC_KEYS: R's payload is its row index (|R| < 2^31) and S's payloads
@@ -316,6 +333,7 @@ class Engine {
     struct JoinRec {
         uint32_t slot = 0;
         bool     args = false, fmt = false, slots = false, timed = false;
+        bool     s_masked = false;  // S had a validity bitmap (KeyMasks)
         uint32_t kbits = 0;  // packed join-key bits (0: 32-bit codes)
         uint64_t nS   = 0;
         Geometry g{};
@@ -337,7 +355,7 @@ class Engine {
                          const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                          const MatReq* mat = nullptr, const SemiReq* semi = nullptr,
                          const OuterReq* outer = nullptr, const GroupReq* group = nullptr,
-                         int layout = SRC_TUPLES);
+                         int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
     // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                                   const Geometry& g, hipStream_t stream, int jkind, int layout);

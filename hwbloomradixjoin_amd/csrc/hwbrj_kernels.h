@@ -17,7 +17,11 @@ namespace hwbrj {
 // SRC_KEYS_VAL: a key column with a value column of the same length beside it (ScatterParams::
 // src_val), the payload scatter of S only: element i carries payload src_val[i] (the group joins on
 // key columns).
-enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2, SRC_KEYS_VAL = 3 };
+// SRC_KEYS_MASK: a key column with a validity bitmap beside it (ScatterParams::valid): a row whose
+// bit is clear is a NULL key, which the scatter places nowhere (the counting scatter and the
+// row-index payload scatter, either side; launch_scatter only: the Engine's layouts are the first
+// and the third).
+enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2, SRC_KEYS_VAL = 3, SRC_KEYS_MASK = 4 };
 
 struct ScatterParams {
     const void*      src;          // uint2 tuples {key, payload}, uint32 codes or uint32 keys
@@ -36,6 +40,8 @@ struct ScatterParams {
                                    // src + w * seg_stride (elements), seg_cnt[w] of them; or nullptr
         const void*     src_val;   // SRC_KEYS_VAL: the n uint32 values beside src's keys, 16-byte
                                    // aligned as src
+        const uint8_t*  valid;     // SRC_KEYS_MASK: src's validity bitmap, ceil(n / 8) bytes: row i is
+                                   // bit i & 7 of byte i >> 3, set = valid (bits past n: not read)
     };
     uint64_t         seg_stride;
     uint64_t         vn;           // MODE_BASIC_POS: tuples / keys of src (n = k * vn elements, k <= grid)
@@ -247,6 +253,24 @@ struct OuterEmitParams {
     unsigned long long* n_s_only;
 };
 void   launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st);
+// The NULL rows of a key column with a validity bitmap (k_null_rows): one row for every i < n whose
+// bit is clear, appended to out (up to cap) through the row counter of the join's own emit kernels;
+// *count and, when not nullptr, *n_class += rows. kind: NULL_ROWS_ANTI {keys[i], i} (the anti join:
+// a NULL S row has no partner), NULL_ROWS_S {null_pay, i} and NULL_ROWS_R {i, null_pay} (the outer
+// join's S-only and R-only rows). valid: 4-byte aligned, ceil(n / 8) bytes, no byte past them is read.
+enum NullRowsKind : uint32_t { NULL_ROWS_ANTI = 0, NULL_ROWS_S = 1, NULL_ROWS_R = 2 };
+struct NullRowsParams {
+    const uint8_t*      valid;
+    const uint32_t*     keys;      // NULL_ROWS_ANTI: the column (else not read)
+    uint64_t            n;         // rows (< 2^31)
+    uint32_t            kind;
+    uint32_t            null_pay;
+    uint2*              out;
+    uint64_t            cap;
+    unsigned long long* count;
+    unsigned long long* n_class;
+};
+void   launch_null_rows(const NullRowsParams& p, uint32_t grid, hipStream_t st);
 
 // The group join (k_join_group): the materializing join's inputs (m; m.out is not used), no pairs.
 // Every R tuple of a job accumulates, in LDS, the number of the job's survivors with its key and the

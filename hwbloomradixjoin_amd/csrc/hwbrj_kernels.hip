@@ -533,8 +533,17 @@ __device__ __forceinline__ void sc_word_lds0(uint32_t x, const Geometry& g, cons
     }
 }
 
-template <int SRC>
-struct ScRaw {  // one round's raw loads of this thread (tuples, key columns: keys only; codes: 4 per uint4)
+// MASK: the validity byte of each 16-byte key load of a round (an empty base otherwise: the raw
+// structs keep their layout)
+template <bool MASK>
+struct ScMaskRaw {
+    uint32_t m[kScE / 4];
+};
+template <>
+struct ScMaskRaw<false> {};
+
+template <int SRC, bool MASK = false>
+struct ScRaw : ScMaskRaw<MASK> {  // one round's raw loads of this thread (tuples, key columns: keys only; codes: 4 per uint4)
     uint32_t k[SRC != SRC_CODES ? kScE : 1];
     uint4    v[SRC != SRC_CODES ? 1 : kScE / 4];
     uint32_t jb[SRC != SRC_CODES ? kScE : 1];  // MODE_BASIC_POS: which bit of the key
@@ -545,10 +554,27 @@ struct ScRaw {  // one round's raw loads of this thread (tuples, key columns: ke
     uint32_t y[SRC == SRC_TUPLES && HWBRJ_SC_KEEPY ? kScE : 1];
 };
 
+// MASK (a key column with a validity bitmap, SRC_KEYS_MASK): the four keys of one 16-byte load are
+// rows e0 + i0 .. + 3 of the column with i0 = base + h * 4 T + 4 tid, base + h * 4 T a multiple of 8
+// and e0 a multiple of 4. Their validity bits are the nibble at bit (e0 & 7) + i0 of the bitmap
+// bytes from e0 >> 3 on: byte sc_mask_byte(e0, tid) + (base + h * 4 T) / 8, shifted right by
+// sc_mask_shift(e0, tid), both fixed per thread. One byte load per key load, in full and in partial
+// rounds alike (a partial round still tests i < len per key: the byte's other bits belong to the
+// next workgroup or lie past n).
+__device__ __forceinline__ uint32_t sc_mask_byte(uint64_t e0, int tid) { return (((uint32_t) e0 & 7u) + 4u * tid) >> 3; }
+__device__ __forceinline__ uint32_t sc_mask_shift(uint64_t e0, int tid) { return (((uint32_t) e0 & 7u) + 4u * tid) & 4u; }
+// bytes of the bitmap from byte e0 >> 3 on that hold the rows [e0, e0 + len)
+__device__ __forceinline__ uint32_t sc_mask_bytes(uint64_t e0, uint32_t len) {
+    return len ? (((uint32_t) e0 & 7u) + len + 7u) >> 3 : 0u;
+}
+
 // LDS: static CRC nibble table (512 B, at 0, so its row offsets are immediates); dynamic (words):
 // stage F x 32 | 64 dummy slots | fill F + 4 | ncb 2F | flq F | misc 8 (per-partition totals: registers of the plan thread)
-template <int SRC, int MODE, int FMT, int SAUX = HWBRJ_SC_SAUX>
+// MASK: src is a key column and P.valid its validity bitmap; a row whose bit is clear is ranked on
+// the dummy counter like an element past the range (q = F), in full rounds too.
+template <int SRC, int MODE, int FMT, int SAUX = HWBRJ_SC_SAUX, bool MASK = false>
 __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
+    static_assert(!MASK || (SRC == SRC_KEYS && MODE != MODE_BASIC_POS), "validity bitmaps: key columns");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     __shared__ uint32_t crc_tab[128];
     constexpr int NL = SRC == SRC_TUPLES ? kScE / 2 : kScE / 4;  // uint4 loads per thread per round
@@ -597,6 +623,14 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
     const auto rsrc = buf_rsrc((const uint8_t*) P.src + e0 * EB, len * EB);  // OOB loads return 0
     const auto rpool = buf_rsrc(pool, (uint32_t) (P.cap * CW * 4));
     const auto rmeta = buf_rsrc(meta, (uint32_t) (P.cap * 2));
+    // MASK: the bitmap bytes of [e0, e1) (loads past them return 0: NULL), this thread's byte and shift
+    [[maybe_unused]] auto     rmask = rsrc;
+    [[maybe_unused]] uint32_t mbyte = 0, mshift = 0;
+    if constexpr (MASK) {
+        rmask  = buf_rsrc(P.valid + (e0 >> 3), sc_mask_bytes(e0, len));
+        mbyte  = sc_mask_byte(e0, tid);
+        mshift = sc_mask_shift(e0, tid);
+    }
     __syncthreads();
 
     // MODE_BASIC_POS: element e0 + i is bit jj of tuple e0 + i - jj |R| (a workgroup's range
@@ -607,7 +641,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
     // Loads of the round at `base`: a full round of tuples (two per 16-byte load) or of a key column
     // (four per load) takes the lane offset in voffset and the round offset in soffset (no
     // per-element VALU); a partial round checks every index.
-    auto load_round = [&](uint32_t base, ScRaw<SRC>& R) {
+    auto load_round = [&](uint32_t base, ScRaw<SRC, MASK>& R) {
         if (MODE == MODE_BASIC_POS) {
 #pragma unroll
             for (int j = 0; j < kScE; j++) {
@@ -660,9 +694,19 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
                 R.v[h]      = make_uint4(x.x, x.y, x.z, x.w);
             }
         }
+        if constexpr (MASK) {  // one validity byte per 16-byte key load (read once, as the keys, and
+            // issued after them: the hash consumes the keys first)
+            const bool fullr = base + kScRound <= len;  // uniform
+#pragma unroll
+            for (int h = 0; h < kScE / 4; h++) {
+                const uint32_t b8 = (base + h * 4 * kScThreads) >> 3, i0 = base + h * 4 * kScThreads + 4 * tid;
+                if (fullr) R.m[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask, mbyte, b8, HWBRJ_SC_LAUX);
+                else R.m[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask, i0 < len ? mbyte + b8 : kOob, 0, HWBRJ_SC_LAUX);
+            }
+        }
     };
     // element j of this thread in the round at `base`, and its index inside the workgroup's slice
-    auto elem = [&](const ScRaw<SRC>& R, uint32_t base, int j, uint32_t& x, uint32_t& idx) {
+    auto elem = [&](const ScRaw<SRC, MASK>& R, uint32_t base, int j, uint32_t& x, uint32_t& idx) {
         if (SRC == SRC_TUPLES) {
             x   = R.k[j];
             idx = MODE == MODE_BASIC_POS ? base + j * kScThreads + tid : base + (j >> 1) * 2 * kScThreads + 2 * tid + (j & 1);
@@ -693,7 +737,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         for (uint32_t k = kScK * kScThreads + tid; k < nf * 8; k += kScThreads) task(k);  // rare
     };
 
-    ScRaw<SRC> RA, RB;
+    ScRaw<SRC, MASK> RA, RB;
     load_round(0, RA);
     if (PRE == 2) load_round(kScRound, RB);
     // Overflow words of the previous round (rank >= 32 in their partition's stage), written after
@@ -726,7 +770,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
 
     // The round's words: hash (consumes R) of the round at `base`; q = F marks elements past len.
     uint32_t q[kScE], w[kScE];
-    auto hash = [&](uint32_t base, const ScRaw<SRC>& R) {
+    auto hash = [&](uint32_t base, const ScRaw<SRC, MASK>& R) {
         const bool full = base + kScRound <= len;  // uniform
         if (SRC == SRC_TUPLES && MODE != MODE_BASIC_POS && HWBRJ_SC_KEEPY) {
 #pragma unroll
@@ -758,8 +802,20 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
                 if (idx >= len) q[j] = F;  // invalid: ranked on the dummy counter
             }
         }
+        if constexpr (MASK) {  // NULL keys: invalid too, in every round
+            // (a wave whose nibbles are all 0xF, the usual case of a column with few NULLs, skips the
+            // per-key tests: one and per load, one compare and one ballot)
+            uint32_t allv = R.m[0] >> mshift;
+#pragma unroll
+            for (int h = 1; h < kScE / 4; h++) allv &= R.m[h] >> mshift;
+            if (__builtin_amdgcn_ballot_w64((allv & 15u) != 15u) != 0) {
+#pragma unroll
+                for (int j = 0; j < kScE; j++)
+                    if (!((R.m[j >> 2] >> (mshift + (j & 3))) & 1u)) q[j] = F;
+            }
+        }
     };
-    auto round = [&](uint32_t base, ScRaw<SRC>& R) {
+    auto round = [&](uint32_t base, ScRaw<SRC, MASK>& R) {
         const bool full = base + kScRound <= len;  // uniform
         // ---- A: hash (consumes R), refill R, copy out the last plan, rank
         hash(base, R);
@@ -787,7 +843,7 @@ __device__ __forceinline__ void scatter_body(const ScatterParams& P) {
         for (int j = 0; j < kScE; j++) {
             const uint32_t qq = q[j] & 2047u, sl = q[j] >> 11;
             const uint32_t a  = qq * 32 + sl;
-            const bool     ok = full || qq < F;
+            const bool     ok = (!MASK && full) || qq < F;  // (MASK: a full round has invalid elements too)
             stage[ok && sl < 32 ? a : dummy] = w[j];
             if (!skew) pq[j] = ok && sl >= 32 ? a : kNoPend;
             else pq[j] = ok && sl >= 32 ? q[j] : kNoPend;
@@ -902,8 +958,8 @@ constexpr int      kScKP     = HWBRJ_SC_KP;  // flush tasks per thread per round
                                              // words + of payloads); ~512 halves per round on average
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 
-template <int SRC>
-struct ScPayRaw {  // one round's raw loads of this thread: {key, payload} tuples, or a key column's keys
+template <int SRC, bool MASK = false>
+struct ScPayRaw : ScMaskRaw<MASK> {  // one round's raw loads of this thread: {key, payload} tuples, or a key column's keys
     v2u      t[SRC == SRC_TUPLES ? kScE : 1];
     uint32_t k[SRC == SRC_KEYS || SRC == SRC_KEYS_VAL ? kScE : 1];
     uint32_t v[SRC == SRC_KEYS_VAL ? kScE : 1];  // (and the value column's values at the keys' indices)
@@ -916,9 +972,12 @@ struct ScPayRaw {  // one round's raw loads of this thread: {key, payload} tuple
 // SRC_KEYS_VAL: SRC_KEYS with every payload read from a value column (P.src_val) at the index that
 // addressed the key: each key load has a value load of the same shape, offsets and bound through a
 // resource of its own (DESIGN "Key columns: group joins").
-template <int SRC, int MODE, int FMT>
+// MASK: SRC_KEYS with the validity bitmap P.valid (scatter_body's MASK: the same byte per key load,
+// the same q = F for a NULL key; the payload of a valid row is still its index in the whole column).
+template <int SRC, int MODE, int FMT, bool MASK = false>
 __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     static_assert(SRC == SRC_TUPLES || SRC == SRC_KEYS || SRC == SRC_KEYS_VAL, "tuples or a key column");
+    static_assert(!MASK || SRC == SRC_KEYS, "validity bitmaps: key columns with row-index payloads");
     static_assert(kScE % 4 == 0 && kScPayThreads == kScThreads, "four keys per 16-byte load");
     constexpr bool     KEYS = SRC == SRC_KEYS || SRC == SRC_KEYS_VAL;  // the key column's load and index shape
     constexpr bool     VAL  = SRC == SRC_KEYS_VAL;
@@ -968,9 +1027,16 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     const auto rpool  = buf_rsrc(P.pool + wg * P.cap * 32, (uint32_t) (P.cap * 128));
     const auto rppool = buf_rsrc(P.ppool + wg * P.cap * 32, (uint32_t) (P.cap * 128));
     const auto rmeta  = buf_rsrc(meta, (uint32_t) (P.cap * 2));
+    [[maybe_unused]] auto     rmask = rsrc;  // (as scatter_body)
+    [[maybe_unused]] uint32_t mbyte = 0, mshift = 0;
+    if constexpr (MASK) {
+        rmask  = buf_rsrc(P.valid + (e0 >> 3), sc_mask_bytes(e0, len));
+        mbyte  = sc_mask_byte(e0, tid);
+        mshift = sc_mask_shift(e0, tid);
+    }
     __syncthreads();
 
-    auto hword = [&](uint32_t H) { return H * 16u; };  // word offset of half H in the region
+    auto hword =[&](uint32_t H) { return H * 16u; };  // word offset of half H in the region
     // element j of this thread in the round at `base`: its index inside the workgroup's range.
     // SRC_KEYS: four consecutive keys per thread and load (scatter_body's SRC_KEYS shape); the index
     // addresses the load and, added to e0, is the element's payload (its row), or addresses the
@@ -980,7 +1046,16 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         return base + j * kScPayThreads + tid;
     };
     const uint32_t row0 = (uint32_t) e0;  // (rows < 2^31: hwbrj_join_keys_*_device)
-    auto load_round = [&](uint32_t base, ScPayRaw<SRC>& R) {
+    auto load_round = [&](uint32_t base, ScPayRaw<SRC, MASK>& R) {
+        if constexpr (MASK) {  // one validity byte per 16-byte key load (scatter_body's)
+            const bool fullr = base + kScRound <= len;  // uniform
+#pragma unroll
+            for (int h = 0; h < kScE / 4; h++) {
+                const uint32_t b8 = (base + h * 4 * kScPayThreads) >> 3;
+                if (fullr) R.m[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask, mbyte, b8, HWBRJ_SC_LAUX);
+                else R.m[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask, eidx(base, 4 * h) < len ? mbyte + b8 : kOob, 0, HWBRJ_SC_LAUX);
+            }
+        }
         if (KEYS && base + kScRound <= len) {  // four keys per 16-byte load: eidx(base, 4 h .. 4 h + 3)
 #pragma unroll
             for (int h = 0; h < kScE / 4; h++) {
@@ -1072,7 +1147,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         for (int j = 0; j < kScE; j++) stg[ps[j]] = make_uint2(pw[j], pp[j]);
     };
 
-    ScPayRaw<SRC> RA;
+    ScPayRaw<SRC, MASK> RA;
     load_round(0, RA);
     auto round = [&](uint32_t base) {
         const bool full = base + kScRound <= len;  // uniform
@@ -1087,6 +1162,18 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
 #pragma unroll
             for (int j = 0; j < kScE; j++)
                 if (eidx(base, j) >= len) q[j] = F;  // invalid: ranked on the dummy counter
+        }
+        if constexpr (MASK) {  // NULL keys: invalid too, in every round
+            // (a wave whose nibbles are all 0xF, the usual case of a column with few NULLs, skips the
+            // per-key tests: one and per load, one compare and one ballot)
+            uint32_t allv = RA.m[0] >> mshift;
+#pragma unroll
+            for (int h = 1; h < kScE / 4; h++) allv &= RA.m[h] >> mshift;
+            if (__builtin_amdgcn_ballot_w64((allv & 15u) != 15u) != 0) {
+#pragma unroll
+                for (int j = 0; j < kScE; j++)
+                    if (!((RA.m[j >> 2] >> (mshift + (j & 3))) & 1u)) q[j] = F;
+            }
         }
         load_round(base + kScRound, RA);
         flush_copy();
@@ -1108,7 +1195,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
 #pragma unroll
         for (int j = 0; j < kScE; j++) {
             const uint32_t qq = q[j] & 2047u, sl = q[j] >> 11;
-            const bool     ok = full || qq < F;
+            const bool     ok = (!MASK && full) || qq < F;  // (MASK: a full round has invalid elements too)
             stg[ok && sl < kPayDepth ? qq * kPayDepth + sl : dummy] = make_uint2(w[j], p[j]);
             pq[j]  = ok && sl >= kPayDepth ? q[j] : kNoPend;
             pw[j]  = w[j];
@@ -4638,6 +4725,61 @@ void launch_outer_emit(const OuterEmitParams& p, uint32_t grid, hipStream_t st) 
     k_outer_emit<<<grid, 1024, lds, st>>>(p);
 }
 
+// The NULL rows of a masked key column (NullRowsParams). A lane takes one dword of the bitmap (32
+// rows), a wave 64 consecutive dwords: the NULL rows of the wave are counted (popcount of the
+// inverted dword, rows past n masked off), scanned over the wave, and placed by one atomic on the
+// join's row counter (and one on the class counter), so the capacity rule covers them with the rows
+// of the join's own emit kernels. A lane then writes its rows in index order. The last dword of a
+// bitmap whose byte count is no multiple of 4 is put together from its bytes: nothing past
+// ceil(n / 8) bytes is read.
+__global__ __launch_bounds__(256) void k_null_rows(NullRowsParams P) {
+    const uint32_t lane   = threadIdx.x & 63u;
+    const uint64_t nbytes = (P.n + 7) >> 3, ndw = (nbytes + 3) >> 2;
+    const uint64_t nwave  = (ndw + 63) >> 6;  // (whole waves: every lane reaches the scan)
+    const uint64_t wave0  = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t waves  = ((uint64_t) gridDim.x * blockDim.x) >> 6;
+    for (uint64_t wv = wave0; wv < nwave; wv += waves) {
+        const uint64_t d = wv * 64 + lane;
+        uint32_t       v = 0xFFFFFFFFu;  // (a dword past the bitmap: no NULL rows)
+        if (d < ndw) {
+            if (d * 4 + 4 <= nbytes) {
+                v = ((const uint32_t*) P.valid)[d];
+            } else {
+                v = 0;
+                for (uint64_t b = d * 4; b < nbytes; b++) v |= (uint32_t) P.valid[b] << (8 * (b - d * 4));
+            }
+        }
+        const uint64_t r0   = d * 32;  // first row of the dword
+        const uint32_t rows = r0 >= P.n ? 0u : P.n - r0 >= 32 ? 32u : (uint32_t) (P.n - r0);
+        uint32_t       inv  = ~v & (rows == 32 ? 0xFFFFFFFFu : (1u << rows) - 1u);
+        const uint32_t cnt  = (uint32_t) __builtin_popcount(inv);
+        const uint32_t incl = wave_incl_scan(cnt);
+        const uint32_t tot  = __shfl(incl, 63, 64);
+        if (tot == 0) continue;  // (uniform)
+        unsigned long long ob = 0;
+        if (lane == 0) {
+            ob = atomicAdd(P.count, (unsigned long long) tot);
+            if (P.n_class) atomicAdd(P.n_class, (unsigned long long) tot);
+        }
+        ob = __shfl(ob, 0, 64);
+        uint64_t o = ob + incl - cnt;
+        while (inv) {
+            const uint32_t i = (uint32_t) r0 + (uint32_t) __builtin_ctz(inv);
+            inv &= inv - 1u;
+            if (o < P.cap) {
+                P.out[o] = P.kind == NULL_ROWS_ANTI ? make_uint2(P.keys[i], i)
+                           : P.kind == NULL_ROWS_S  ? make_uint2(P.null_pay, i)
+                                                    : make_uint2(i, P.null_pay);
+            }
+            o++;
+        }
+    }
+}
+
+void launch_null_rows(const NullRowsParams& p, uint32_t grid, hipStream_t st) {
+    if (p.n) k_null_rows<<<grid, 256, 0, st>>>(p);
+}
+
 // ================================================================= K10g: the group join
 // k_join_mat's job (payload_job) with a policy that writes no pairs (GroupPolicy; under ALL its early
 // returns are k_join_outer<true>'s): every R tuple of the job owns an accumulator {count (u32), sum
@@ -4887,8 +5029,41 @@ static void scatter_sp_inst(const ScatterParams& p, uint32_t grid, hipStream_t s
     k_scatter_sp<SRC, MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
 }
 
+// SRC_KEYS_MASK: kernels of their own (scatter_body / scatter_body_pay with MASK) beside the
+// SRC_KEYS ones, which keep their names and code; the partition-slice modes and no filter.
+template <int MODE, int FMT>
+__global__ __launch_bounds__(kScThreads) void k_scatter_rm(ScatterParams P) { scatter_body<SRC_KEYS, MODE, FMT, HWBRJ_SC_SAUX_R, true>(P); }
+template <int MODE, int FMT>
+__global__ __launch_bounds__(kScThreads) void k_scatter_sm(ScatterParams P) { scatter_body<SRC_KEYS, MODE, FMT, HWBRJ_SC_SAUX, true>(P); }
+template <int MODE, int FMT>
+__global__ __launch_bounds__(kScPayThreads) void k_scatter_rpm(ScatterParams P) { scatter_body_pay<SRC_KEYS, MODE, FMT, true>(P); }
+template <int MODE, int FMT>
+__global__ __launch_bounds__(kScPayThreads) void k_scatter_spm(ScatterParams P) { scatter_body_pay<SRC_KEYS, MODE, FMT, true>(P); }
+
+template <int MODE, int FMT>
+static void scatter_mask_inst(const ScatterParams& p, int side, uint32_t grid, hipStream_t st) {
+    const bool   pay = p.ppool != nullptr;
+    const size_t lds = pay ? scatter_pay_lds_bytes(p.g.log2F) : scatter_lds_bytes(p.g.log2F);
+    const void*  fn  = pay ? (side == SIDE_R ? (const void*) &k_scatter_rpm<MODE, FMT> : (const void*) &k_scatter_spm<MODE, FMT>)
+                           : (side == SIDE_R ? (const void*) &k_scatter_rm<MODE, FMT> : (const void*) &k_scatter_sm<MODE, FMT>);
+    (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    if (pay && side == SIDE_R) k_scatter_rpm<MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
+    else if (pay) k_scatter_spm<MODE, FMT><<<grid, kScPayThreads, lds, st>>>(p);
+    else if (side == SIDE_R) k_scatter_rm<MODE, FMT><<<grid, kScThreads, lds, st>>>(p);
+    else k_scatter_sm<MODE, FMT><<<grid, kScThreads, lds, st>>>(p);
+}
+
 void launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hipStream_t st) {
     const Geometry& g = p.g;
+    if (src == SRC_KEYS_MASK) {  // a key column with p.valid: counting (no ppool) or row-index payloads
+        switch (g.mode) {        // (the Engine refuses the other modes before it gets here)
+            case MODE_SLICE_BLOCK:
+                if (g.format == FMT_PACKED) return scatter_mask_inst<MODE_SLICE_BLOCK, FMT_PACKED>(p, side, grid, st);
+                return scatter_mask_inst<MODE_SLICE_BLOCK, FMT_CODE>(p, side, grid, st);
+            case MODE_SLICE_BASIC: return scatter_mask_inst<MODE_SLICE_BASIC, FMT_CODE>(p, side, grid, st);
+            default: return scatter_mask_inst<MODE_NOBLOOM, FMT_CODE>(p, side, grid, st);
+        }
+    }
     if (p.ppool && src == SRC_KEYS_VAL && side == SIDE_S) {  // S's key column, its value column as payloads
         switch (g.mode) {
             case MODE_SLICE_BLOCK:

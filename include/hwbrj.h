@@ -202,7 +202,10 @@ int hwbrj_set_async_timing(int on);
  * columns aggregate a value column of S (hwbrj_join_keys_group_device,
  * hwbrj_join_keys_group_minmax_device, below). Not offered on key columns: a value column for R or
  * more than one for S, values other than int32, async forms of the row-index and group joins, the
- * host BPRO family and the partitioned joins; those take tuples only. */
+ * host BPRO family and the partitioned joins; those take tuples only. Validity bitmaps (NULL keys)
+ * are offered by the hwbrj_join_keys_*_nulls_device entries below, and not for the group joins or
+ * their value column, the async form, a bit offset into the bitmap, or the global-bitmap and basic
+ * k >= 2 configurations. */
 int hwbrj_join_keys_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys, uint64_t nS,
                            const bloom_filter_args_t * args, int algorithm, void * stream,
                            hwbrj_stats_t * stats);
@@ -303,6 +306,60 @@ int hwbrj_join_keys_outer_device(const int32_t * d_Rkeys, uint64_t nR, const int
                                  tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
                                  uint64_t * n_class /* [3], optional */, void * stream,
                                  hwbrj_stats_t * stats, double * ms);
+/* Key columns with validity bitmaps: the counting, pair, existence and outer joins on key columns
+ * (above) with one bitmap per side, the second half of a columnar key column. A NULL key matches
+ * nothing (SQL), so no compaction pass and no index map are needed before the join: row indices are
+ * always positions in the caller's columns.
+ * The bitmap: d_Rvalid / d_Svalid are device memory in Arrow's layout, row i is bit i & 7 of byte
+ * i >> 3 and a set bit means valid. A bitmap holds ceil(n / 8) bytes; no byte past them is read, and
+ * the bits past n in the last byte are ignored whatever they hold. A NULL pointer means that side has
+ * no NULL keys. With both pointers NULL an entry runs exactly what its counterpart runs (the same
+ * kernels, no further loads). There is no bit offset: row 0 is bit 0 of byte 0.
+ * Alignment: a non-NULL bitmap of a non-empty column must start at a 4-byte boundary (the NULL-row
+ * pass reads it a dword at a time). Otherwise 2 is returned before any device call, "align" is in
+ * hwbrj_last_error(), and nothing is written. A caller sharding a masked column must therefore cut it
+ * at multiples of 32 rows (which also keeps the key column's multiple of 4).
+ * Each result is what the counterpart returns on the valid rows only, with their original row
+ * indices, plus:
+ *  - count, pairs: nothing more. stats->filtered and stats->matches are the counting join's on the
+ *    valid rows; the filter is built from the valid R keys only.
+ *  - semi: the valid S rows with a partner among the valid R rows.
+ *  - anti: every other S row, each NULL S row included (NOT EXISTS); the key field of a NULL row's
+ *    output is whatever the column stores at that position. NULL R rows play no part.
+ *  - outer: NULL S rows are S-only rows {-1, S row} under HWBRJ_OUTER_S and HWBRJ_OUTER_FULL, NULL R
+ *    rows are R-only rows {R row, -1} under HWBRJ_OUTER_R and HWBRJ_OUTER_FULL, and n_class counts
+ *    them in its S-only and R-only entries.
+ * The NULL rows are subject to the capacity rule like any others. Every other clause is the
+ * counterpart's (capacity, kinds, the 16-byte alignment of the key columns, the 2^31 limits, args ==
+ * NULL running PRO, HWBRJ_ALGO_*, synchronous, collecting pending async joins, hwbrj_tables_*).
+ * Filters: with a non-NULL bitmap the partition-slice configurations (blocked and sectorized with
+ * B >= 8, basic k = 1) and args == NULL are supported, the ones where the pass-1 scatters are the
+ * only readers of the columns; the global-bitmap configurations and basic k >= 2 return 9 before any
+ * device call (hwbrj_join_partitioned's code for an unsupported filter). With both bitmaps NULL those
+ * configurations behave as the counterpart does.
+ * Not offered with validity bitmaps: the group joins and NULL values of a value column, an async
+ * form, tuple relations, a bit offset into the bitmap, the global-bitmap and basic k >= 2
+ * configurations, the host BPRO family and the partitioned joins. */
+int hwbrj_join_keys_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
+                                 const int32_t * d_Skeys, const uint8_t * d_Svalid, uint64_t nS,
+                                 const bloom_filter_args_t * args, int algorithm, void * stream,
+                                 hwbrj_stats_t * stats);
+int hwbrj_join_keys_pairs_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
+                                       const int32_t * d_Skeys, const uint8_t * d_Svalid, uint64_t nS,
+                                       const bloom_filter_args_t * args, tuple_t * d_out,
+                                       uint64_t capacity, uint64_t * n_out, void * stream,
+                                       hwbrj_stats_t * stats, double * ms);
+int hwbrj_join_keys_semi_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
+                                      const int32_t * d_Skeys, const uint8_t * d_Svalid, uint64_t nS,
+                                      const bloom_filter_args_t * args, int kind, tuple_t * d_out,
+                                      uint64_t capacity, uint64_t * n_out, void * stream,
+                                      hwbrj_stats_t * stats, double * ms);
+int hwbrj_join_keys_outer_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
+                                       const int32_t * d_Skeys, const uint8_t * d_Svalid, uint64_t nS,
+                                       const bloom_filter_args_t * args, int kind, tuple_t * d_out,
+                                       uint64_t capacity, uint64_t * n_out,
+                                       uint64_t * n_class /* [3], optional */, void * stream,
+                                       hwbrj_stats_t * stats, double * ms);
 /* The group join of R and S (join and aggregate per build-side row: SELECT R.payload, COUNT(*),
  * SUM(S.payload) ... GROUP BY R-row): d_out receives one row per R row, not per key, in no
  * particular order. count is the number of S rows whose key equals the R row's key, sum the sum of
