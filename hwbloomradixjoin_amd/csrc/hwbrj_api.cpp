@@ -291,7 +291,8 @@ static int publish(const hwbrj_stats_t& st, uint64_t n, uint64_t capacity, hwbrj
 
 // The materializing join (Engine::run_mat, or Engine::materialize after the counting join).
 // *n = all pairs (also beyond cap); *ms = the device time of the pairs' production. In the
-// global-bitmap mode a count above cap returns before the side pass: no pair is written.
+// global-bitmap mode the side pass writes the first cap pairs whatever the count (k_pair_probe's row
+// stage holds every store to out[0, cap)); only the count-only form, cap = 0, stays a count.
 // layout (here and in join_semi / join_outer below): SRC_TUPLES, or SRC_KEYS (d_R, d_S are int32 key
 // columns and every payload is the row index).
 static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
@@ -303,7 +304,7 @@ static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void
         [&] { return e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout, masks); },
         [&] {
             *n = (uint64_t) st->matches;
-            if (*n > cap) return 0;  // (the caller reports the capacity)
+            if (cap == 0) return 0;  // (count only: nothing could be written)
             uint64_t  m  = 0;
             const int rc = e->materialize(d_R, nR, d_S, nS, (uint2*) d_out, cap, &m, stream, ms, layout);
             if (rc) return rc;

@@ -196,10 +196,8 @@ def test_capacity_contract_global(hw, cuda, args, kind_of, kind_name, keys):
     """capacity = 1000 below every class's row count, a 4096-row guard behind it (a whole LDS stage
     of 4096 rows flushed past the capacity would land there): code 7, the full counts in *n_out,
     stats.matches and n_class / n_pairs, the guard untouched, every row in [0, capacity) a row of
-    the result; and the count-only form (capacity 0, d_out NULL) with the same count.
-    Pairs: code 7, the match count, the guard untouched. In this mode the pairs' side pass is not run
-    when the count exceeds the capacity, so a row in [0, capacity) is either still the sentinel or a
-    pair: all that is guaranteed there."""
+    the result (pairs included: the first `capacity` pairs are written); and the count-only form
+    (capacity 0, d_out NULL) with the same count."""
     rel = _cap_case(cuda)
     inner, s_only, r_only = join_classes(rel.Rk, rel.Rp, rel.Sk, rel.Sp, NULL)
     matched = int(np.isin(rel.Rk, rel.Sk).sum())
@@ -219,10 +217,7 @@ def test_capacity_contract_global(hw, cuda, args, kind_of, kind_name, keys):
     host = buf.cpu().numpy()
     assert (host[cap:] == GUARD).all()  # nothing past the capacity
     rows = set(r.tobytes() for r in want)
-    if kind_of == "pairs":
-        rows.add(np.full(2, GUARD, dtype=np.int32).tobytes())  # (not written)
-    else:
-        assert st.matches == want.shape[0]
+    assert st.matches == want.shape[0]
     assert all(r.tobytes() in rows for r in host[:cap])  # the first `capacity` rows are rows
     rc, n0, _, cls0, pairs0 = call.run(None, 0)  # count only
     assert (rc, n0, cls0, pairs0) == (7, want.shape[0], want_cls, want_pairs)
