@@ -168,6 +168,11 @@ def lib() -> ctypes.CDLL:
             ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
         L.hwbrj_join_keys_group_minmax_device.restype = ctypes.c_int
         L.hwbrj_join_keys_group_minmax_device.argtypes = L.hwbrj_join_keys_group_device.argtypes
+        # (their validity-bitmap forms: d_Rvalid before nR, d_Svalid before d_Svals, d_Svals_valid before nS)
+        g = L.hwbrj_join_keys_group_device.argtypes
+        for nm in ("hwbrj_join_keys_group_nulls_device", "hwbrj_join_keys_group_minmax_nulls_device"):
+            getattr(L, nm).restype = ctypes.c_int
+            getattr(L, nm).argtypes = [g[0], ctypes.c_void_p, g[1], g[2], ctypes.c_void_p, g[3], ctypes.c_void_p] + list(g[4:])
         L.hwbrj_set_materialize.restype = None
         L.hwbrj_set_materialize.argtypes = [ctypes.c_int]
         L.hwbrj_set_gpus.restype = ctypes.c_int
@@ -1013,11 +1018,18 @@ def group_minmax_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind:
     return stats, rows, int(pairs.value), ms.value
 
 
-def _group_keys(entry: str, minmax: bool, Rk, Sk, Sv, args, kind, stream, capacity):
+def _group_keys(entry: str, minmax: bool, Rk, Sk, Sv, args, kind, stream, capacity, r_valid=None, s_valid=None,
+                sv_valid=None):
     """group_join_keys_device / group_minmax_join_keys_device: (Stats, raw rows, n_pairs, ms) of
-    `entry`, with the capacity behaviour of the tuple wrappers."""
+    `entry`, with the capacity behaviour of the tuple wrappers. With a validity argument the entry is
+    its _nulls_ form (hwbrj_join_keys_group_nulls_device / _minmax_nulls_device)."""
     import torch
+    vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
+    vv = _check_valid("sv_valid", sv_valid, Sk)  # (a value per key: the key column's length)
     _check_keys(Rk, Sk, stream, Sv)
+    masked = vr is not None or vs is not None or vv is not None
+    if masked:
+        entry = entry.replace("_device", "_nulls_device")
     a = args._c() if args is not None else None
     ap = ctypes.byref(a) if a is not None else None
     sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
@@ -1027,6 +1039,9 @@ def _group_keys(entry: str, minmax: bool, Rk, Sk, Sv, args, kind, stream, capaci
     fn = getattr(lib(), entry)
 
     def call(out, cap):
+        if masked:
+            return fn(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs), _ptr(Sv), _vptr(vv), Sk.shape[0], ap,
+                      int(kind), out, cap, ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
         return fn(_ptr(Rk), Rk.shape[0], _ptr(Sk), _ptr(Sv), Sk.shape[0], ap, int(kind), out, cap, ctypes.byref(n),
                   ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
 
@@ -1051,28 +1066,37 @@ def _group_keys(entry: str, minmax: bool, Rk, Sk, Sv, args, kind, stream, capaci
 
 
 def group_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED, stream=None,
-                           capacity: Optional[int] = None):
+                           capacity: Optional[int] = None, *, r_valid=None, s_valid=None, sv_valid=None):
     """(Stats, GroupRows, n_pairs, ms): group_join_device on key columns with S's aggregated value in
     a third column (hwbrj_join_keys_group_device). Rk, Sk are join_keys_device's columns and Sv a
     column of Sk's length and kind: Sv[i] is the value of S row i. GroupRows.r_payload is the R row
     index (the gather map for R's other columns), count and sum are over Sv of the S rows with the R
     row's key: exactly group_join_device's rows on stack(Rk, arange) and stack(Sk, Sv), without that
     interleaving pass. len(Rk) < 2^31, len(Sk) < 2^32. kind, capacity, n_pairs, Stats and ms are
-    group_join_device's; the stream rule is join_keys_device's."""
+    group_join_device's; the stream rule is join_keys_device's.
+    r_valid, s_valid, sv_valid: the validity of Rk, Sk and Sv (hwbrj_join_keys_group_nulls_device), each
+    in join_keys_device's forms (None, a torch.bool tensor, a torch.uint8 bitmap). An S row takes part
+    iff its key and its value are valid: count is COUNT(Sv), sum over the same rows, and n_pairs their
+    total. A NULL R row matches nothing and, under GROUP_ALL, still gets its row with count 0.
+    r_payload stays the position in the caller's column. Partition-slice filters and no filter only."""
     import torch
-    stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_device", False, Rk, Sk, Sv, args, kind, stream, capacity)
+    stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_device", False, Rk, Sk, Sv, args, kind, stream, capacity,
+                                        r_valid, s_valid, sv_valid)
     rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
     return stats, rows, pairs, ms
 
 
 def group_minmax_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED,
-                                  stream=None, capacity: Optional[int] = None):
+                                  stream=None, capacity: Optional[int] = None, *, r_valid=None, s_valid=None,
+                                  sv_valid=None):
     """(Stats, GroupMinMaxRows, n_pairs, ms): group_minmax_join_device on key columns
     (hwbrj_join_keys_group_minmax_device): group_join_keys_device's arguments, r_payload the R row
-    index, min and max over Sv of the S rows with the R row's key, compared as signed int32."""
+    index, min and max over Sv of the S rows with the R row's key, compared as signed int32.
+    r_valid, s_valid, sv_valid: group_join_keys_device's (hwbrj_join_keys_group_minmax_nulls_device); a
+    row with count 0 carries min = INT32_MAX and max = INT32_MIN."""
     import torch
     stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_minmax_device", True, Rk, Sk, Sv, args, kind, stream,
-                                        capacity)
+                                        capacity, r_valid, s_valid, sv_valid)
     rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
     return stats, rows, pairs, ms
 

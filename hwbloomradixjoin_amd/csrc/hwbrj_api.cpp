@@ -453,12 +453,14 @@ int hwbrj_join_keys_outer_device(const int32_t* d_Rkeys, uint64_t nR, const int3
 // (k_null_rows reads it a dword at a time), and a bitmap needs a filter whose scatters are the only
 // readers of the columns (masks_supported: 9 otherwise). Both bitmaps NULL: neither check, and the
 // counterpart's call.
+// d_Svvalid: the bitmap of S's value column (the group joins on key columns), under the same rules.
 static int masks_ok(const uint8_t* d_Rvalid, uint64_t nR, const uint8_t* d_Svalid, uint64_t nS,
-                    const bloom_filter_args_t* args, bool pl) {
-    if (!d_Rvalid && !d_Svalid) return 0;
+                    const bloom_filter_args_t* args, bool pl, const uint8_t* d_Svvalid = nullptr) {
+    if (!d_Rvalid && !d_Svalid && !d_Svvalid) return 0;
     const bool bad_r = d_Rvalid && nR && ((uintptr_t) d_Rvalid & 3u), bad_s = d_Svalid && nS && ((uintptr_t) d_Svalid & 3u);
-    if (bad_r || bad_s) {
-        set_last_error(std::string("validity bitmap of ") + (bad_r ? "R" : "S") +
+    const bool bad_v = d_Svvalid && nS && ((uintptr_t) d_Svvalid & 3u);
+    if (bad_r || bad_s || bad_v) {
+        set_last_error(std::string("validity bitmap of ") + (bad_r ? "R" : bad_s ? "S" : "S's value column") +
                        " is not 4-byte aligned (shard a masked column at multiples of 32 rows)");
         return 2;
     }
@@ -531,7 +533,7 @@ int hwbrj_join_keys_outer_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_
 static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void* d_Svals, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, uint32_t agg, void* d_out, uint64_t capacity,
                       uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms,
-                      int layout) {
+                      int layout, const KeyMasks* masks = nullptr) {
     static_assert(sizeof(hwbrj_group_row_t) == 16 && sizeof(hwbrj_group_minmax_row_t) == 16,
                   "a row is one 16-byte store");
     if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {  // (before any device call)
@@ -557,7 +559,7 @@ static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void*
     uint64_t       n = 0, pairs = 0;
     const int      rc = pipeline_or_side_pass(
         e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
-        [&] { return e->run_group(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, &pairs, layout); },
+        [&] { return e->run_group(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, &pairs, layout, masks); },
         [&] { return e->group_side(d_R, nR, d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms, layout); });
     if (rc) return rc;
     if (n_pairs) *n_pairs = pairs;
@@ -620,6 +622,39 @@ int hwbrj_join_keys_group_minmax_device(const int32_t* d_Rkeys, uint64_t nR, con
     if (const int rc = keys_group_ok(d_Rkeys, nR, d_Skeys, d_Svals, nS)) return rc;
     return join_group(d_Rkeys, nR, d_Skeys, d_Svals, nS, args, kind, GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs,
                       stream, stats, ms, SRC_KEYS);
+}
+
+// The group joins on key columns with validity bitmaps: the counterpart's rules, then the bitmaps'
+// (masks_ok), then join_group's; all three bitmaps NULL: the counterpart's call.
+static int join_keys_group_nulls(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR, const int32_t* d_Skeys,
+                                 const uint8_t* d_Svalid, const int32_t* d_Svals, const uint8_t* d_Svals_valid,
+                                 uint64_t nS, const bloom_filter_args_t* args, int kind, uint32_t agg, void* d_out,
+                                 uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream,
+                                 hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = keys_group_ok(d_Rkeys, nR, d_Skeys, d_Svals, nS)) return rc;
+    if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true, d_Svals_valid)) return rc;
+    const KeyMasks km{d_Rvalid, d_Svalid, d_Svals_valid};
+    return join_group(d_Rkeys, nR, d_Skeys, d_Svals, nS, args, kind, agg, d_out, capacity, n_out, n_pairs, stream,
+                      stats, ms, SRC_KEYS, &km);
+}
+
+int hwbrj_join_keys_group_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
+                                       const int32_t* d_Skeys, const uint8_t* d_Svalid, const int32_t* d_Svals,
+                                       const uint8_t* d_Svals_valid, uint64_t nS, const bloom_filter_args_t* args,
+                                       int kind, hwbrj_group_row_t* d_out, uint64_t capacity, uint64_t* n_out,
+                                       uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms) {
+    return join_keys_group_nulls(d_Rkeys, d_Rvalid, nR, d_Skeys, d_Svalid, d_Svals, d_Svals_valid, nS, args, kind,
+                                 GRP_COUNT_SUM, d_out, capacity, n_out, n_pairs, stream, stats, ms);
+}
+
+int hwbrj_join_keys_group_minmax_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
+                                              const int32_t* d_Skeys, const uint8_t* d_Svalid, const int32_t* d_Svals,
+                                              const uint8_t* d_Svals_valid, uint64_t nS,
+                                              const bloom_filter_args_t* args, int kind,
+                                              hwbrj_group_minmax_row_t* d_out, uint64_t capacity, uint64_t* n_out,
+                                              uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms) {
+    return join_keys_group_nulls(d_Rkeys, d_Rvalid, nR, d_Skeys, d_Svalid, d_Svals, d_Svals_valid, nS, args, kind,
+                                 GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs, stream, stats, ms);
 }
 
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE

@@ -383,8 +383,8 @@ int Engine::run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
 
 int Engine::run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                       const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
-                      hwbrj_stats_t* st, uint64_t* pairs, int layout) {
-    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, nullptr, &group, layout);
+                      hwbrj_stats_t* st, uint64_t* pairs, int layout, const KeyMasks* masks) {
+    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, nullptr, &group, layout, masks);
     if (rc == 0) rc = wait(st);
     if (rc) return rc;
     // (the join has completed; its ring slot is taken again by the next enqueue only)
@@ -404,6 +404,10 @@ int Engine::run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
 // scatter, the other side the kernel it runs without masks; nothing after the scatters knows: a NULL
 // key is in no partition. The rows that NULL keys contribute themselves (anti, outer) come from
 // k_null_rows after the join's own emit kernels, through the same row counter.
+// A group join on key columns takes them too, with a third bitmap for S's value column (masks->sv):
+// R runs the SRC_KEYS_MASK row-index scatter, S the SRC_KEYS_VAL_MASK scatter with one bitmap or two
+// (a row is placed iff every bit is set), k_join_group sees only what was placed, and under `all`
+// the NULL R rows' identity rows come from k_null_group_rows after it, through the same row counter.
 int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                     const bloom_filter_args_t* args, hipStream_t stream, int jkind,
                     const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group,
@@ -435,8 +439,13 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     // the bitmap of each non-empty side, or nullptr (an empty column has no NULL rows)
     const uint8_t* vR = masks && nR ? masks->r : nullptr;
     const uint8_t* vS = masks && nS ? masks->s : nullptr;
-    if ((vR || vS) && (layout != SRC_KEYS || group)) {
-        set_last_error("validity bitmaps: key columns, not the group joins");
+    const uint8_t* vV = masks && nS ? masks->sv : nullptr;  // (S's value column: the group joins)
+    if ((vR || vS || vV) && layout != SRC_KEYS) {
+        set_last_error("validity bitmaps: key columns");
+        return 2;
+    }
+    if (vV && !group) {
+        set_last_error("validity bitmaps: a value column's belongs to the group joins");
         return 2;
     }
     // what the S payload scatter reads: the layout, or S's key column with its value column
@@ -445,7 +454,7 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         set_last_error(err);
         return 2;
     }
-    if ((vR || vS) && !masks_supported(g)) {  // (hwbrj_api.cpp refuses first, before any device call)
+    if ((vR || vS || vV) && !masks_supported(g)) {  // (hwbrj_api.cpp refuses first, before any device call)
         set_last_error("validity bitmaps need partition slices (blocked/sectorized, basic k = 1, or no filter)");
         return kRcMaskFilter;
     }
@@ -547,8 +556,14 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     sp.zero_word  = jparts.as<uint32_t>() + 2 * NJ;
 
     // S pass-1 and its lists (below; async joins: on a second stream, concurrent with the R side)
+    // (a group join on key columns with a bitmap on S: the value-column scatter's masked form, one
+    // bitmap or both, whichever column they belong to)
+    const bool val_masked = layout_s == SRC_KEYS_VAL && (vS || vV);
     auto s_pass = [&](hipStream_t st, bool marks, hipEvent_t* tev = nullptr) -> int {
-        ScatterParams ss = sp;
+        ScatterValParams ss{};
+        (ScatterParams&) ss = sp;
+        ss.vmask[0]      = !val_masked ? nullptr : vS ? vS : vV;
+        ss.vmask[1]      = val_masked && vS ? vV : nullptr;
         ss.zero_small    = nullptr;
         ss.zero_word     = nullptr;
         if (g.mode == MODE_GLOBAL) {
@@ -562,12 +577,13 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
             ss.n     = nS;
             ss.n_dev = nullptr;
             if (layout_s == SRC_KEYS_VAL) ss.src_val = group->s_val;  // (shares seg_cnt's slot: not SRC_CODES)
-            if (vS) ss.valid = vS;                                    // (the same slot: never both)
+            else if (vS) ss.valid = vS;                               // (the same slot: never both)
         }
         S_.bind(&ss, capS);
         ss.ppool = pl ? ppoolS.as<uint32_t>() : nullptr;
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
-        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : vS ? SRC_KEYS_MASK : layout_s, SIDE_S, G, st);
+        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : val_masked ? SRC_KEYS_VAL_MASK : vS ? SRC_KEYS_MASK : layout_s,
+                       SIDE_S, G, st);
         if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
         if (marks) HWBRJ_CHECK(mark(4, st));
         index_side(S_, capS, g.log2F, CH, nseg, G, st);
@@ -807,6 +823,12 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
             gp.out     = group->out;
             gp.n_pairs = pairs;
             launch_join_group(gp, NJ, stream);
+            // NULL keys of R are in no partition, so no job saw them: under ALL their identity rows
+            // come from here, through the same row counter
+            if (group->all && vR)
+                launch_null_group_rows(NullGroupRowsParams{vR, nR, group->agg, group->out, group->cap,
+                                                           (unsigned long long*) d_result},
+                                       (uint32_t) cus_ * 2, stream);
         } else {
             launch_join_mat(mp, NJ, stream);
         }
@@ -888,7 +910,7 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         r.timed = rtimed;
         r.nS    = nS;
         r.g     = g;
-        r.s_masked = vS != nullptr;
+        r.s_masked = vS != nullptr || vV != nullptr;
         ring_push(r);
     }
     return 0;

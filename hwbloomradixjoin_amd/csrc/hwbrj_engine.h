@@ -59,10 +59,14 @@ struct GroupReq {
 // The validity bitmaps of two key columns (layout SRC_KEYS; include/hwbrj.h "validity bitmaps"): row
 // i of a column is bit i & 7 of byte i >> 3, set = valid; nullptr: that column has no NULL keys and
 // runs the kernels it runs without a KeyMasks. A NULL key joins nothing. Partition-slice modes and no
-// filter only (9 otherwise), and not the group joins.
+// filter only (9 otherwise).
+// sv: the group joins on key columns only (GroupReq::s_val), the bitmap of S's value column in the
+// same layout: an S row takes part iff its key bit and its value bit are set, so count is COUNT(S.val)
+// and sum / min / max are over the same rows. Under GROUP_ALL a NULL R row still gets its identity row.
 struct KeyMasks {
-    const uint8_t* r = nullptr;
-    const uint8_t* s = nullptr;
+    const uint8_t* r  = nullptr;
+    const uint8_t* s  = nullptr;
+    const uint8_t* sv = nullptr;
 };
 
 // The modes whose pass-1 scatters are the only readers of the raw relations (Engine::enqueue): a
@@ -170,10 +174,11 @@ class Engine {
     // The group join on the materializing pipeline up to the join, then k_join_group. st->matches =
     // rows (all of them, also beyond cap); *pairs = the sum of their counts. kRcMatGlobal: not for the
     // global-bitmap mode. layout SRC_KEYS: R's payload is its row index (|R| < 2^31) and S's payloads
-    // are group.s_val (GroupReq), the only payloads of S that are read.
+    // are group.s_val (GroupReq), the only payloads of S that are read. masks: SRC_KEYS only (KeyMasks,
+    // sv included).
     int  run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
                    const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
-                   hwbrj_stats_t* st, uint64_t* pairs, int layout = SRC_TUPLES);
+                   hwbrj_stats_t* st, uint64_t* pairs, int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
     // The side passes after a counting join (global-bitmap mode; one skeleton: side_pass). *n = rows
     // (all of them, also beyond the capacity); *pairs, cls as above; materialize: (R.payload, S.payload)
     // of every match into out[0, cap). *ms = the side pass's device time.

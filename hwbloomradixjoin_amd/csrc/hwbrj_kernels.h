@@ -21,7 +21,12 @@ namespace hwbrj {
 // bit is clear is a NULL key, which the scatter places nowhere (the counting scatter and the
 // row-index payload scatter, either side; launch_scatter only: the Engine's layouts are the first
 // and the third).
-enum Source : int { SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2, SRC_KEYS_VAL = 3, SRC_KEYS_MASK = 4 };
+// SRC_KEYS_VAL_MASK: SRC_KEYS_VAL with one or two validity bitmaps (ScatterValParams::vmask: the key
+// column's, the value column's, or both): a row is placed iff its bit is set in each (the group joins
+// on key columns with NULL keys and NULL values; launch_scatter only, as SRC_KEYS_MASK).
+enum Source : int {
+    SRC_TUPLES = 0, SRC_CODES = 1, SRC_KEYS = 2, SRC_KEYS_VAL = 3, SRC_KEYS_MASK = 4, SRC_KEYS_VAL_MASK = 5
+};
 
 struct ScatterParams {
     const void*      src;          // uint2 tuples {key, payload}, uint32 codes or uint32 keys
@@ -51,6 +56,16 @@ struct ScatterParams {
     uint32_t*        zero_word;
     Geometry         g;
     const CrcTables* tabs;
+};
+// SRC_KEYS_VAL_MASK: the value-column scatter's bitmaps, which cannot use `valid` (src_val's slot).
+// They stand behind the last field of ScatterParams in a type of their own, the argument of the
+// k_scatter_spvm kernels alone: appended to ScatterParams itself they would grow every scatter
+// kernel's argument block and move the hidden arguments (the grid size) behind it, that is, change
+// the code of every existing scatter. launch_scatter(p, SRC_KEYS_VAL_MASK, ...) takes p as this type.
+// vmask[0]: a bitmap of the n rows (ScatterParams::valid's layout), never nullptr; vmask[1]: a second
+// one, or nullptr (one bitmap: the key column's or the value column's, the kernel cannot tell).
+struct ScatterValParams : ScatterParams {
+    const uint8_t* vmask[2];
 };
 
 // Packed join keys between the build / probe and the join (BuildParams::kbits): on when the join
@@ -289,6 +304,20 @@ struct GroupJoinParams {
     unsigned long long* n_pairs;  // zero on entry
 };
 void   launch_join_group(const GroupJoinParams& p, uint32_t jobs, hipStream_t st);
+// The group join's rows of R's NULL keys (k_null_group_rows; GROUP_ALL with a bitmap on R's key
+// column): the identity row {i, 0, 0} (GRP_COUNT_SUM) or {i, 0, INT32_MAX, INT32_MIN}
+// (GRP_COUNT_MINMAX) of every row i < n whose bit is clear, appended to out (up to cap) through the row
+// counter k_join_group adds to (GroupJoinParams::m.count); *count += rows, no pairs. valid: 4-byte
+// aligned, ceil(n / 8) bytes, no byte past them is read.
+struct NullGroupRowsParams {
+    const uint8_t*      valid;
+    uint64_t            n;    // rows (< 2^31)
+    uint32_t            agg;  // GroupAgg
+    uint4*              out;
+    uint64_t            cap;
+    unsigned long long* count;
+};
+void   launch_null_group_rows(const NullGroupRowsParams& p, uint32_t grid, hipStream_t st);
 
 void   launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                   hipStream_t st);
@@ -308,7 +337,8 @@ void   launch_slice_fill(const uint32_t* pool, const uint32_t* list, const uint3
 size_t scatter_lds_bytes(uint32_t log2F);
 size_t scatter_pay_lds_bytes(uint32_t log2F);  // (ScatterParams::ppool set)
 enum { SIDE_R = 0, SIDE_S = 1 };  // which relation a scatter partitions (kernel name; S uses g.s_format)
-// (src = SRC_KEYS_VAL: SIDE_S with p.ppool and p.src_val set, nothing else)
+// (src = SRC_KEYS_VAL: SIDE_S with p.ppool and p.src_val set, nothing else; SRC_KEYS_VAL_MASK: the
+// same with p a ScatterValParams)
 void   launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hipStream_t st);
 // k_plan: per-(wg, q) list offsets + per-partition chunk / element totals (colc, cole);
 // k_list_fill: scans the totals into list / element / item starts [F + 1] and fills the lists.

@@ -958,8 +958,16 @@ constexpr int      kScKP     = HWBRJ_SC_KP;  // flush tasks per thread per round
                                              // words + of payloads); ~512 halves per round on average
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 
-template <int SRC, bool MASK = false>
-struct ScPayRaw : ScMaskRaw<MASK> {  // one round's raw loads of this thread: {key, payload} tuples, or a key column's keys
+// NM = 2 (a key column and a value column with a bitmap each): the second bitmap's byte of each key load
+template <bool TWO>
+struct ScMask2Raw {
+    uint32_t m2[kScE / 4];
+};
+template <>
+struct ScMask2Raw<false> {};
+
+template <int SRC, int NM = 0>
+struct ScPayRaw : ScMaskRaw<(NM > 0)>, ScMask2Raw<(NM > 1)> {  // one round's raw loads of this thread: {key, payload} tuples, or a key column's keys
     v2u      t[SRC == SRC_TUPLES ? kScE : 1];
     uint32_t k[SRC == SRC_KEYS || SRC == SRC_KEYS_VAL ? kScE : 1];
     uint32_t v[SRC == SRC_KEYS_VAL ? kScE : 1];  // (and the value column's values at the keys' indices)
@@ -974,10 +982,19 @@ struct ScPayRaw : ScMaskRaw<MASK> {  // one round's raw loads of this thread: {k
 // resource of its own (DESIGN "Key columns: group joins").
 // MASK: SRC_KEYS with the validity bitmap P.valid (scatter_body's MASK: the same byte per key load,
 // the same q = F for a NULL key; the payload of a valid row is still its index in the whole column).
-template <int SRC, int MODE, int FMT, bool MASK = false>
-__device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
+// NM: the number of validity bitmaps, 0 (no MASK), 1 (SRC_KEYS: P.valid) or, SRC_KEYS_VAL only, 1 or 2
+// bitmaps vm0 / vm1 (ScatterValParams::vmask: the key column's, the value column's, or both; P.valid
+// lies in src_val's slot). Both cover the same rows, so one byte offset and one shift per thread
+// address both, each through a resource of its own; a row is placed iff its bit is set in every
+// bitmap (the nibbles are ANDed before the per-key tests), and the byte loads of a round are issued
+// behind its key and value loads.
+template <int SRC, int MODE, int FMT, int NM = 0>
+__device__ __forceinline__ void scatter_body_pay(const ScatterParams& P, const uint8_t* vm0 = nullptr,
+                                                 const uint8_t* vm1 = nullptr) {
+    constexpr bool MASK = NM > 0;
     static_assert(SRC == SRC_TUPLES || SRC == SRC_KEYS || SRC == SRC_KEYS_VAL, "tuples or a key column");
-    static_assert(!MASK || SRC == SRC_KEYS, "validity bitmaps: key columns with row-index payloads");
+    static_assert(!MASK || SRC == SRC_KEYS || SRC == SRC_KEYS_VAL, "validity bitmaps: key columns");
+    static_assert(NM >= 0 && NM <= 2 && (NM < 2 || SRC == SRC_KEYS_VAL), "two bitmaps: a key and a value column");
     static_assert(kScE % 4 == 0 && kScPayThreads == kScThreads, "four keys per 16-byte load");
     constexpr bool     KEYS = SRC == SRC_KEYS || SRC == SRC_KEYS_VAL;  // the key column's load and index shape
     constexpr bool     VAL  = SRC == SRC_KEYS_VAL;
@@ -1030,9 +1047,17 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
     [[maybe_unused]] auto     rmask = rsrc;  // (as scatter_body)
     [[maybe_unused]] uint32_t mbyte = 0, mshift = 0;
     if constexpr (MASK) {
-        rmask  = buf_rsrc(P.valid + (e0 >> 3), sc_mask_bytes(e0, len));
+        rmask  = buf_rsrc((VAL ? vm0 : P.valid) + (e0 >> 3), sc_mask_bytes(e0, len));
         mbyte  = sc_mask_byte(e0, tid);
         mshift = sc_mask_shift(e0, tid);
+    }
+    [[maybe_unused]] auto rmask2 = rsrc;  // NM = 2: the second bitmap's bytes of [e0, e1)
+    if constexpr (NM == 2) rmask2 = buf_rsrc(vm1 + (e0 >> 3), sc_mask_bytes(e0, len));
+    if constexpr (MASK && VAL) {
+        // (byte and shift as two opaque values: left to itself the compiler keeps their common term
+        // (e0 & 7) + 4 tid alive for the partial round's offsets as well, a third register, which the
+        // two-bitmap packed form spills)
+        asm volatile("" : "+v"(mbyte), "+v"(mshift));
     }
     __syncthreads();
 
@@ -1046,8 +1071,8 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         return base + j * kScPayThreads + tid;
     };
     const uint32_t row0 = (uint32_t) e0;  // (rows < 2^31: hwbrj_join_keys_*_device)
-    auto load_round = [&](uint32_t base, ScPayRaw<SRC, MASK>& R) {
-        if constexpr (MASK) {  // one validity byte per 16-byte key load (scatter_body's)
+    auto load_round = [&](uint32_t base, ScPayRaw<SRC, NM>& R) {
+        if constexpr (MASK && !VAL) {  // one validity byte per 16-byte key load (scatter_body's)
             const bool fullr = base + kScRound <= len;  // uniform
 #pragma unroll
             for (int h = 0; h < kScE / 4; h++) {
@@ -1056,6 +1081,21 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
                 else R.m[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask, eidx(base, 4 * h) < len ? mbyte + b8 : kOob, 0, HWBRJ_SC_LAUX);
             }
         }
+        // SRC_KEYS_VAL with bitmaps: the same byte of each bitmap per key load, behind the key and the
+        // value loads (the hash consumes the keys first)
+        auto load_val_masks = [&]() {
+            if constexpr (MASK && VAL) {
+                const bool fullr = base + kScRound <= len;  // uniform
+#pragma unroll
+                for (int h = 0; h < kScE / 4; h++) {
+                    const uint32_t b8 = (base + h * 4 * kScPayThreads) >> 3;
+                    const uint32_t vo = fullr ? mbyte : eidx(base, 4 * h) < len ? mbyte + b8 : kOob;
+                    const uint32_t so = fullr ? b8 : 0u;
+                    R.m[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask, vo, so, HWBRJ_SC_LAUX);
+                    if constexpr (NM == 2) R.m2[h] = __builtin_amdgcn_raw_buffer_load_b8(rmask2, vo, so, HWBRJ_SC_LAUX);
+                }
+            }
+        };
         if (KEYS && base + kScRound <= len) {  // four keys per 16-byte load: eidx(base, 4 h .. 4 h + 3)
 #pragma unroll
             for (int h = 0; h < kScE / 4; h++) {
@@ -1072,6 +1112,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
                     R.v[4 * h + 3] = y.w;
                 }
             }
+            load_val_masks();
         } else if (KEYS) {
 #pragma unroll
             for (int j = 0; j < kScE; j++) {
@@ -1079,6 +1120,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
                 R.k[j] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, i < len ? i * EB : kOob, 0, 0);
                 if (VAL) R.v[j] = __builtin_amdgcn_raw_buffer_load_b32(rval, i < len ? i * EB : kOob, 0, 0);
             }
+            load_val_masks();
         } else if (base + kScRound <= len) {  // {key, payload} as one 8-byte load
 #pragma unroll
             for (int j = 0; j < kScE; j++)
@@ -1147,7 +1189,7 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         for (int j = 0; j < kScE; j++) stg[ps[j]] = make_uint2(pw[j], pp[j]);
     };
 
-    ScPayRaw<SRC, MASK> RA;
+    ScPayRaw<SRC, NM> RA;
     load_round(0, RA);
     auto round = [&](uint32_t base) {
         const bool full = base + kScRound <= len;  // uniform
@@ -1166,6 +1208,10 @@ __device__ __forceinline__ void scatter_body_pay(const ScatterParams& P) {
         if constexpr (MASK) {  // NULL keys: invalid too, in every round
             // (a wave whose nibbles are all 0xF, the usual case of a column with few NULLs, skips the
             // per-key tests: one and per load, one compare and one ballot)
+            if constexpr (NM == 2) {  // a row takes part iff both bits are set
+#pragma unroll
+                for (int h = 0; h < kScE / 4; h++) RA.m[h] &= RA.m2[h];
+            }
             uint32_t allv = RA.m[0] >> mshift;
 #pragma unroll
             for (int h = 1; h < kScE / 4; h++) allv &= RA.m[h] >> mshift;
@@ -4780,6 +4826,53 @@ void launch_null_rows(const NullRowsParams& p, uint32_t grid, hipStream_t st) {
     if (p.n) k_null_rows<<<grid, 256, 0, st>>>(p);
 }
 
+// The group join's rows of R's NULL keys under GROUP_ALL (NullGroupRowsParams): k_null_rows' walk (a
+// bitmap dword per lane, rows past n masked off, a wave scan, the last dword from its bytes), one
+// atomic on the row counter k_join_group adds to, then one 16-byte identity row per NULL row below
+// the capacity, in index order: {i, 0, 0, 0} (hwbrj_group_row_t: count 0, sum 0) or {i, 0, INT32_MAX,
+// INT32_MIN} (hwbrj_group_minmax_row_t). No pair is counted.
+__global__ __launch_bounds__(256) void k_null_group_rows(NullGroupRowsParams P) {
+    const uint32_t lane   = threadIdx.x & 63u;
+    const uint64_t nbytes = (P.n + 7) >> 3, ndw = (nbytes + 3) >> 2;
+    const uint64_t nwave  = (ndw + 63) >> 6;  // (whole waves: every lane reaches the scan)
+    const uint64_t wave0  = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint64_t waves  = ((uint64_t) gridDim.x * blockDim.x) >> 6;
+    const bool     mm     = P.agg == GRP_COUNT_MINMAX;
+    for (uint64_t wv = wave0; wv < nwave; wv += waves) {
+        const uint64_t d = wv * 64 + lane;
+        uint32_t       v = 0xFFFFFFFFu;  // (a dword past the bitmap: no NULL rows)
+        if (d < ndw) {
+            if (d * 4 + 4 <= nbytes) {
+                v = ((const uint32_t*) P.valid)[d];
+            } else {
+                v = 0;
+                for (uint64_t b = d * 4; b < nbytes; b++) v |= (uint32_t) P.valid[b] << (8 * (b - d * 4));
+            }
+        }
+        const uint64_t r0   = d * 32;  // first row of the dword
+        const uint32_t rows = r0 >= P.n ? 0u : P.n - r0 >= 32 ? 32u : (uint32_t) (P.n - r0);
+        uint32_t       inv  = ~v & (rows == 32 ? 0xFFFFFFFFu : (1u << rows) - 1u);
+        const uint32_t cnt  = (uint32_t) __builtin_popcount(inv);
+        const uint32_t incl = wave_incl_scan(cnt);
+        const uint32_t tot  = __shfl(incl, 63, 64);
+        if (tot == 0) continue;  // (uniform)
+        unsigned long long ob = 0;
+        if (lane == 0) ob = atomicAdd(P.count, (unsigned long long) tot);
+        ob = __shfl(ob, 0, 64);
+        uint64_t o = ob + incl - cnt;
+        while (inv) {
+            const uint32_t i = (uint32_t) r0 + (uint32_t) __builtin_ctz(inv);
+            inv &= inv - 1u;
+            if (o < P.cap) P.out[o] = make_uint4(i, 0u, mm ? 0x7FFFFFFFu : 0u, mm ? 0x80000000u : 0u);
+            o++;
+        }
+    }
+}
+
+void launch_null_group_rows(const NullGroupRowsParams& p, uint32_t grid, hipStream_t st) {
+    if (p.n) k_null_group_rows<<<grid, 256, 0, st>>>(p);
+}
+
 // ================================================================= K10g: the group join
 // k_join_mat's job (payload_job) with a policy that writes no pairs (GroupPolicy; under ALL its early
 // returns are k_join_outer<true>'s): every R tuple of the job owns an accumulator {count (u32), sum
@@ -5053,8 +5146,35 @@ static void scatter_mask_inst(const ScatterParams& p, int side, uint32_t grid, h
     else k_scatter_sm<MODE, FMT><<<grid, kScThreads, lds, st>>>(p);
 }
 
+// SRC_KEYS_VAL_MASK: the value-column payload scatter of S with NM = 1 or 2 bitmaps
+// (ScatterValParams::vmask behind the ScatterParams every other scatter takes, which keeps its size)
+template <int MODE, int FMT, int NM>
+__global__ __launch_bounds__(kScPayThreads) void k_scatter_spvm(ScatterValParams P) {
+    scatter_body_pay<SRC_KEYS_VAL, MODE, FMT, NM>(P, P.vmask[0], P.vmask[1]);
+}
+
+template <int MODE, int FMT>
+static void scatter_spvm_inst(const ScatterValParams& p, uint32_t grid, hipStream_t st) {
+    const size_t lds = scatter_pay_lds_bytes(p.g.log2F);
+    const bool   two = p.vmask[1] != nullptr;
+    const void*  fn  = two ? (const void*) &k_scatter_spvm<MODE, FMT, 2> : (const void*) &k_scatter_spvm<MODE, FMT, 1>;
+    (void) hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
+    if (two) k_scatter_spvm<MODE, FMT, 2><<<grid, kScPayThreads, lds, st>>>(p);
+    else k_scatter_spvm<MODE, FMT, 1><<<grid, kScPayThreads, lds, st>>>(p);
+}
+
 void launch_scatter(const ScatterParams& p, int src, int side, uint32_t grid, hipStream_t st) {
     const Geometry& g = p.g;
+    if (src == SRC_KEYS_VAL_MASK) {  // S's key and value columns with bitmaps (p: a ScatterValParams)
+        const ScatterValParams& pv = static_cast<const ScatterValParams&>(p);
+        switch (g.mode) {            // (the Engine refuses the other modes before it gets here)
+            case MODE_SLICE_BLOCK:
+                if (g.format == FMT_PACKED) return scatter_spvm_inst<MODE_SLICE_BLOCK, FMT_PACKED>(pv, grid, st);
+                return scatter_spvm_inst<MODE_SLICE_BLOCK, FMT_CODE>(pv, grid, st);
+            case MODE_SLICE_BASIC: return scatter_spvm_inst<MODE_SLICE_BASIC, FMT_CODE>(pv, grid, st);
+            default: return scatter_spvm_inst<MODE_NOBLOOM, FMT_CODE>(pv, grid, st);
+        }
+    }
     if (src == SRC_KEYS_MASK) {  // a key column with p.valid: counting (no ppool) or row-index payloads
         switch (g.mode) {        // (the Engine refuses the other modes before it gets here)
             case MODE_SLICE_BLOCK:

@@ -203,9 +203,10 @@ int hwbrj_set_async_timing(int on);
  * hwbrj_join_keys_group_minmax_device, below). Not offered on key columns: a value column for R or
  * more than one for S, values other than int32, async forms of the row-index and group joins, the
  * host BPRO family and the partitioned joins; those take tuples only. Validity bitmaps (NULL keys)
- * are offered by the hwbrj_join_keys_*_nulls_device entries below, and not for the group joins or
- * their value column, the async form, a bit offset into the bitmap, or the global-bitmap and basic
- * k >= 2 configurations. */
+ * are offered by the hwbrj_join_keys_*_nulls_device entries below, the group joins with a bitmap for
+ * S's value column among them (hwbrj_join_keys_group_nulls_device,
+ * hwbrj_join_keys_group_minmax_nulls_device), and not for the async form, a bit offset into the
+ * bitmap, or the global-bitmap and basic k >= 2 configurations. */
 int hwbrj_join_keys_device(const int32_t * d_Rkeys, uint64_t nR, const int32_t * d_Skeys, uint64_t nS,
                            const bloom_filter_args_t * args, int algorithm, void * stream,
                            hwbrj_stats_t * stats);
@@ -337,9 +338,11 @@ int hwbrj_join_keys_outer_device(const int32_t * d_Rkeys, uint64_t nR, const int
  * only readers of the columns; the global-bitmap configurations and basic k >= 2 return 9 before any
  * device call (hwbrj_join_partitioned's code for an unsupported filter). With both bitmaps NULL those
  * configurations behave as the counterpart does.
- * Not offered with validity bitmaps: the group joins and NULL values of a value column, an async
- * form, tuple relations, a bit offset into the bitmap, the global-bitmap and basic k >= 2
- * configurations, the host BPRO family and the partitioned joins. */
+ * The group joins take bitmaps too, one more for S's value column: hwbrj_join_keys_group_nulls_device
+ * and hwbrj_join_keys_group_minmax_nulls_device, after the group joins on key columns below.
+ * Not offered with validity bitmaps: COUNT(*) beside the aggregates of a nullable value column, the
+ * tuple group joins, an async form, tuple relations, a bit offset into the bitmap, the global-bitmap
+ * and basic k >= 2 configurations, the host BPRO family and the partitioned joins. */
 int hwbrj_join_keys_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
                                  const int32_t * d_Skeys, const uint8_t * d_Svalid, uint64_t nS,
                                  const bloom_filter_args_t * args, int algorithm, void * stream,
@@ -450,6 +453,51 @@ int hwbrj_join_keys_group_minmax_device(const int32_t * d_Rkeys, uint64_t nR, co
                                         hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
                                         uint64_t * n_out, uint64_t * n_pairs /* optional */,
                                         void * stream, hwbrj_stats_t * stats, double * ms);
+/* The group joins on key columns with validity bitmaps: NULL keys on either side and NULL values in
+ * S's value column. Three optional bitmaps in the layout of the hwbrj_join_keys_*_nulls_device entries
+ * above (row i is bit i & 7 of byte i >> 3, set = valid, ceil(n / 8) bytes, bits past n ignored, no
+ * byte past them read, a NULL pointer = no NULLs, no bit offset): d_Rvalid for R's keys, d_Svalid for
+ * S's keys and d_Svals_valid for S's values.
+ *  - An S row takes part in the join iff its key bit and its value bit are both set. A NULL key
+ *    matches nothing; a NULL value is ignored by SUM / MIN / MAX, as in SQL, and is not counted: count
+ *    is COUNT(S.val), sum / min / max are over the same rows, count == 0 (and min > max) means the
+ *    aggregate is NULL, and n_pairs is the sum of the counts. COUNT(*) over a nullable value column
+ *    is what the same call returns without d_Svals_valid; it is not produced beside the aggregates,
+ *    because a 16-byte row has no field for it.
+ *  - A NULL R row matches nothing. Under HWBRJ_GROUP_ALL it still gets its row, {R row, 0, 0}, or
+ *    {R row, 0, INT32_MAX, INT32_MIN} in the MIN / MAX form, so the row count stays nR; under
+ *    HWBRJ_GROUP_MATCHED it gets none. These rows are subject to the capacity rule like any others.
+ *  - r_payload is the row's position in the caller's column: no compaction pass, no index map.
+ *  - stats->filtered and stats->matches are the group join's values on the participating rows:
+ *    filtered is the counting join's value on the compacted columns (the filter is built from the
+ *    valid R keys only), and with args == NULL and any S bitmap it is the number of participating S
+ *    rows.
+ * Filters as for the other bitmap entries: the partition-slice configurations (blocked / sectorized
+ * with B >= 8, basic k = 1) and args == NULL; the global-bitmap and basic k >= 2 configurations return
+ * 9 before any device call when any bitmap is non-NULL. With all three bitmaps NULL an entry runs
+ * exactly what hwbrj_join_keys_group_device / hwbrj_join_keys_group_minmax_device run (the same
+ * kernels, no further loads). A non-NULL bitmap of a non-empty column must start at a 4-byte boundary:
+ * otherwise 2, "align" in hwbrj_last_error(), nothing written. Every other clause is the
+ * counterpart's: the kinds (2 for an unknown one, *n_out unwritten), capacity in rows, *n_out always
+ * the full row count, 7 above capacity, capacity 0 with d_out NULL as the count-only form, d_out and
+ * the three columns 16-byte aligned, nR < 2^31, nS < 2^32, synchronous, collecting pending async
+ * joins, hwbrj_tables_* answering 13 afterwards.
+ * Not offered: the tuple group joins with NULLs, an async form, a bit offset into a bitmap. */
+int hwbrj_join_keys_group_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
+                                       const int32_t * d_Skeys, const uint8_t * d_Svalid,
+                                       const int32_t * d_Svals, const uint8_t * d_Svals_valid,
+                                       uint64_t nS, const bloom_filter_args_t * args, int kind,
+                                       hwbrj_group_row_t * d_out, uint64_t capacity, uint64_t * n_out,
+                                       uint64_t * n_pairs /* optional */, void * stream,
+                                       hwbrj_stats_t * stats, double * ms);
+int hwbrj_join_keys_group_minmax_nulls_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid,
+                                              uint64_t nR, const int32_t * d_Skeys,
+                                              const uint8_t * d_Svalid, const int32_t * d_Svals,
+                                              const uint8_t * d_Svals_valid, uint64_t nS,
+                                              const bloom_filter_args_t * args, int kind,
+                                              hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
+                                              uint64_t * n_out, uint64_t * n_pairs /* optional */,
+                                              void * stream, hwbrj_stats_t * stats, double * ms);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
