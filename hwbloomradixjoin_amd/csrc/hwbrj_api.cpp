@@ -7,7 +7,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <functional>
 #include <mutex>
 #include <set>
 #include <string>
@@ -169,11 +168,20 @@ int hwbrj_copy_bandwidth(uint64_t bytes, int reps, double* gbps) {
 uint32_t hwbrj_hash_crc(uint32_t seed, int32_t key) { return crc_f_bitwise(seed ^ (uint32_t) key); }
 uint32_t hwbrj_hash_crapwow(uint32_t seed, int32_t key) { return crapwow(seed, (uint32_t) key); }
 
+// A counting join's request
+static JoinReq count_req(int algorithm, int layout, const KeyMasks& masks = KeyMasks{}) {
+    JoinReq q;
+    q.jkind  = algorithm;
+    q.layout = layout;
+    q.masks  = masks;
+    return q;
+}
+
 int hwbrj_join_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, void* stream, hwbrj_stats_t* stats) {
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
-    return e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, stats);
+    return e->run(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, count_req(0, SRC_TUPLES), stats);
 }
 
 int hwbrj_join_device_algo(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -181,14 +189,14 @@ int hwbrj_join_device_algo(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, 
                            hwbrj_stats_t* stats) {
     Engine* e = engine_for_current_device();
     if (!e) return 10;
-    return e->run((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream, stats, algorithm);
+    return e->run(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, count_req(algorithm, SRC_TUPLES), stats);
 }
 
 int hwbrj_join_device_async(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
                             const bloom_filter_args_t* args, void* stream) {
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
-    return e->run_async((const uint2*) d_R, nR, (const uint2*) d_S, nS, args, (hipStream_t) stream);
+    return e->run_async(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream});
 }
 
 // Key columns: a non-empty column starts at a 16-byte boundary (the scatter's 16-byte loads and its
@@ -207,7 +215,7 @@ int hwbrj_join_keys_device(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d
     if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
     Engine* e = engine_for_current_device();
     if (!e) return 10;
-    return e->run(d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream, stats, algorithm, SRC_KEYS);
+    return e->run(JoinIn{d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream}, count_req(algorithm, SRC_KEYS), stats);
 }
 
 int hwbrj_join_keys_device_async(const int32_t* d_Rkeys, uint64_t nR, const int32_t* d_Skeys,
@@ -215,7 +223,7 @@ int hwbrj_join_keys_device_async(const int32_t* d_Rkeys, uint64_t nR, const int3
     if (!keys_aligned(d_Rkeys, nR, d_Skeys, nS)) return 2;
     Engine* e = engine_for_current_device();
     if (!e) return 10;
-    return e->run_async(d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream, 0, SRC_KEYS);
+    return e->run_async(JoinIn{d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream}, 0, SRC_KEYS);
 }
 
 int hwbrj_join_partitioned(const hwbrj_exchange_t* x, int rank, int world, const tuple_t* d_R,
@@ -254,79 +262,82 @@ int hwbrj_join_wait_all(hwbrj_stats_t* stats, int capacity, int* n_joins) {
     return e->wait_all(stats, capacity, n_joins);
 }
 
-// Every payload join runs its partitioned pipeline (pipe(): st->matches rows, st->ms_total); the
+// Every payload join runs its partitioned pipeline (Engine::run: st->matches rows, st->ms_total); the
 // global-bitmap mode (basic k = 0 or B < 8: kRcMatGlobal) falls back to the counting join (its
-// filter and its "S-tuples after filter") plus the kind's side pass (side(): *n rows, *ms its device
-// time). *n = all rows (also beyond the capacity), and st->matches with it.
-static int pipeline_or_side_pass(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
-                                 const bloom_filter_args_t* args, hipStream_t stream, int layout, hwbrj_stats_t* st,
-                                 uint64_t* n, double* ms, const std::function<int()>& pipe,
-                                 const std::function<int()>& side) {
-    int rc = pipe();
+// filter and its "S-tuples after filter") plus the kind's side pass (Engine::side: *n rows, *ms its
+// device time). *n = all rows (also beyond the capacity), and st->matches with it; *x: the kind's
+// extra counts.
+// Pairs in the global-bitmap mode: the side pass writes the first cap pairs whatever the count
+// (k_pair_probe's row stage holds every store to out[0, cap)); only the count-only form, cap = 0,
+// stays a count.
+static int pipeline_or_side_pass(Engine* e, const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, uint64_t* n,
+                                 JoinExtras* x, double* ms) {
+    int rc = e->run(in, req, st, x);
     if (rc == 0) {
         *n = (uint64_t) st->matches;
         if (ms) *ms = st->ms_total;
         return 0;
     }
     if (rc != kRcMatGlobal) return rc;
-    rc = e->run(d_R, nR, d_S, nS, args, stream, st, 0, layout);
+    rc = e->run(in, count_req(0, req.layout), st);
     if (rc) return rc;
-    rc = side();
+    if (req.kind == JOIN_PAIRS) {
+        *n = (uint64_t) st->matches;
+        if (req.cap == 0) return 0;  // (count only: nothing could be written)
+        uint64_t m = 0;
+        rc         = e->side(in, req, &m, x, ms);
+        if (rc == 0 && m != *n) {
+            set_last_error("materialized pairs differ from the counted matches");
+            return 8;
+        }
+        return rc;
+    }
+    rc = e->side(in, req, n, x, ms);
     if (rc) return rc;
     st->matches = (int64_t) *n;
     return 0;
 }
 
-// The caller's outputs of a payload join and its capacity rule (what: "match" or "row")
-static int publish(const hwbrj_stats_t& st, uint64_t n, uint64_t capacity, hwbrj_stats_t* stats, uint64_t* n_out,
-                   const char* what) {
+// The shared tail of the payload joins' entries, after their argument checks: the join, the kind's
+// extra counts (n_class: the outer join's three; n_pairs: the group join's), then the caller's outputs
+// and the capacity rule (what: "match" or "row"). *ms = the device time of the rows' production.
+static int payload_join(const JoinIn& in, const JoinReq& req, const char* what, uint64_t* n_out, hwbrj_stats_t* stats,
+                        double* ms, uint64_t* n_class = nullptr, uint64_t* n_pairs = nullptr) {
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;  // (last error set by engine_for_current_device)
+    hwbrj_stats_t st;
+    uint64_t      n = 0;
+    JoinExtras    x;
+    if (const int rc = pipeline_or_side_pass(e, in, req, &st, &n, &x, ms)) return rc;
+    if (n_class)
+        for (int i = 0; i < 3; i++) n_class[i] = x.cls[i];
+    if (n_pairs) *n_pairs = x.pairs;
     if (stats) *stats = st;
     if (n_out) *n_out = n;
-    if (n > capacity) {
+    if (n > req.cap) {
         set_last_error(std::string("output capacity below the ") + what + " count (*n_out holds the count)");
         return 7;
     }
     return 0;
 }
 
-// The materializing join (Engine::run_mat, or Engine::materialize after the counting join).
-// *n = all pairs (also beyond cap); *ms = the device time of the pairs' production. In the
-// global-bitmap mode the side pass writes the first cap pairs whatever the count (k_pair_probe's row
-// stage holds every store to out[0, cap)); only the count-only form, cap = 0, stays a count.
-// layout (here and in join_semi / join_outer below): SRC_TUPLES, or SRC_KEYS (d_R, d_S are int32 key
-// columns and every payload is the row index).
-static int materialize_pairs(Engine* e, const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
-                             const bloom_filter_args_t* args, tuple_t* d_out, uint64_t cap, uint64_t* n,
-                             hipStream_t stream, hwbrj_stats_t* st, double* ms, int layout = SRC_TUPLES,
-                             const KeyMasks* masks = nullptr) {
-    return pipeline_or_side_pass(
-        e, d_R, nR, d_S, nS, args, stream, layout, st, n, ms,
-        [&] { return e->run_mat(d_R, nR, d_S, nS, args, stream, MatReq{(uint2*) d_out, cap}, st, layout, masks); },
-        [&] {
-            *n = (uint64_t) st->matches;
-            if (cap == 0) return 0;  // (count only: nothing could be written)
-            uint64_t  m  = 0;
-            const int rc = e->materialize(d_R, nR, d_S, nS, (uint2*) d_out, cap, &m, stream, ms, layout);
-            if (rc) return rc;
-            if (m != *n) {
-                set_last_error("materialized pairs differ from the counted matches");
-                return 8;
-            }
-            return 0;
-        });
+// What every payload request shares: the kind, the output, the layout (SRC_TUPLES, or SRC_KEYS: d_R
+// and d_S are int32 key columns and every payload is the row index) and the bitmaps
+static JoinReq payload_req(JoinKind kind, void* d_out, uint64_t capacity, int layout, const KeyMasks& masks) {
+    JoinReq q = count_req(0, layout, masks);
+    q.kind    = kind;
+    q.out     = d_out;
+    q.cap     = capacity;
+    return q;
 }
 
+// The materializing join (JOIN_PAIRS).
 static int join_pairs(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, tuple_t* d_out, uint64_t capacity, uint64_t* n_out,
                       void* stream, hwbrj_stats_t* stats, double* ms_materialize, int layout,
-                      const KeyMasks* masks = nullptr) {
-    Engine* e = engine_for_current_device();
-    if (!e) return 10;  // (last error set by engine_for_current_device)
-    hwbrj_stats_t st;
-    uint64_t      n  = 0;
-    const int     rc = materialize_pairs(e, d_R, nR, d_S, nS, args, d_out, capacity, &n, (hipStream_t) stream,
-                                         &st, ms_materialize, layout, masks);
-    return rc ? rc : publish(st, n, capacity, stats, n_out, "match");
+                      const KeyMasks& masks = KeyMasks{}) {
+    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream},
+                        payload_req(JOIN_PAIRS, d_out, capacity, layout, masks), "match", n_out, stats, ms_materialize);
 }
 
 int hwbrj_join_materialize_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -359,13 +370,13 @@ int hwbrj_join_keys_pairs_device(const int32_t* d_Rkeys, uint64_t nR, const int3
     return join_pairs(d_Rkeys, nR, d_Skeys, nS, args, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS);
 }
 
-// The existence join: the partitioned pipeline with S's payloads (Engine::run_semi); the
+// The existence join: the partitioned pipeline with S's payloads (JOIN_SEMI); the
 // global-bitmap mode runs the counting join (its filter and its "S-tuples after filter") and the
 // existence side pass.
 static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                      const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
                      uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms, int layout,
-                     const KeyMasks* masks = nullptr) {
+                     const KeyMasks& masks = KeyMasks{}) {
     if (kind != HWBRJ_JOIN_SEMI && kind != HWBRJ_JOIN_ANTI) {  // (before any device call)
         set_last_error("unknown existence join kind (HWBRJ_JOIN_SEMI, HWBRJ_JOIN_ANTI)");
         return 2;
@@ -374,16 +385,9 @@ static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
         set_last_error("d_out must hold capacity rows");
         return 2;
     }
-    Engine* e = engine_for_current_device();
-    if (!e) return 10;  // (last error set by engine_for_current_device)
-    const SemiReq req{(uint2*) d_out, capacity, kind == HWBRJ_JOIN_ANTI};
-    hwbrj_stats_t st;
-    uint64_t      n  = 0;
-    const int     rc = pipeline_or_side_pass(
-        e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
-        [&] { return e->run_semi(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, layout, masks); },
-        [&] { return e->semi_side(d_R, nR, d_S, nS, req, &n, (hipStream_t) stream, ms, layout); });
-    return rc ? rc : publish(st, n, capacity, stats, n_out, "row");
+    JoinReq req = payload_req(JOIN_SEMI, d_out, capacity, layout, masks);
+    req.anti    = kind == HWBRJ_JOIN_ANTI;
+    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms);
 }
 
 int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -400,12 +404,12 @@ int hwbrj_join_keys_semi_device(const int32_t* d_Rkeys, uint64_t nR, const int32
 }
 
 // The outer join: the materializing pipeline with marks over S and matched flags over R
-// (Engine::run_outer); the global-bitmap mode runs the counting join (its filter and its "S-tuples
+// (JOIN_OUTER); the global-bitmap mode runs the counting join (its filter and its "S-tuples
 // after filter") and the outer side pass.
 static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
                       uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
-                      hwbrj_stats_t* stats, double* ms, int layout, const KeyMasks* masks = nullptr) {
+                      hwbrj_stats_t* stats, double* ms, int layout, const KeyMasks& masks = KeyMasks{}) {
     if (kind != HWBRJ_OUTER_S && kind != HWBRJ_OUTER_R && kind != HWBRJ_OUTER_FULL) {  // (before any device call)
         set_last_error("unknown outer join kind (HWBRJ_OUTER_S, HWBRJ_OUTER_R, HWBRJ_OUTER_FULL)");
         return 2;
@@ -414,20 +418,11 @@ static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS
         set_last_error("d_out must hold capacity rows");
         return 2;
     }
-    Engine* e = engine_for_current_device();
-    if (!e) return 10;  // (last error set by engine_for_current_device)
-    const OuterReq req{(uint2*) d_out, capacity, kind != HWBRJ_OUTER_R, kind != HWBRJ_OUTER_S,
-                       (uint32_t) null_payload};
-    hwbrj_stats_t st;
-    uint64_t      n = 0, cls[3] = {0, 0, 0};
-    const int     rc = pipeline_or_side_pass(
-        e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
-        [&] { return e->run_outer(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, cls, layout, masks); },
-        [&] { return e->outer_side(d_R, nR, d_S, nS, req, &n, cls, (hipStream_t) stream, ms, layout); });
-    if (rc) return rc;
-    if (n_class)
-        for (int i = 0; i < 3; i++) n_class[i] = cls[i];
-    return publish(st, n, capacity, stats, n_out, "row");
+    JoinReq req  = payload_req(JOIN_OUTER, d_out, capacity, layout, masks);
+    req.keep_s   = kind != HWBRJ_OUTER_R;
+    req.keep_r   = kind != HWBRJ_OUTER_S;
+    req.null_pay = (uint32_t) null_payload;
+    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms, n_class);
 }
 
 int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -484,8 +479,8 @@ int hwbrj_join_keys_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid
     if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, false)) return rc;
     Engine* e = engine_for_current_device();
     if (!e) return 10;
-    const KeyMasks km{d_Rvalid, d_Svalid};
-    return e->run(d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream, stats, algorithm, SRC_KEYS, &km);
+    return e->run(JoinIn{d_Rkeys, nR, d_Skeys, nS, args, (hipStream_t) stream},
+                  count_req(algorithm, SRC_KEYS, KeyMasks{d_Rvalid, d_Svalid}), stats);
 }
 
 int hwbrj_join_keys_pairs_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
@@ -498,8 +493,8 @@ int hwbrj_join_keys_pairs_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_
         set_last_error("d_out must hold capacity rows");
         return 2;
     }
-    const KeyMasks km{d_Rvalid, d_Svalid};
-    return join_pairs(d_Rkeys, nR, d_Skeys, nS, args, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS, &km);
+    return join_pairs(d_Rkeys, nR, d_Skeys, nS, args, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS,
+                      KeyMasks{d_Rvalid, d_Svalid});
 }
 
 int hwbrj_join_keys_semi_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
@@ -508,8 +503,8 @@ int hwbrj_join_keys_semi_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_R
                                       uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms) {
     if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
     if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true)) return rc;
-    const KeyMasks km{d_Rvalid, d_Svalid};
-    return join_semi(d_Rkeys, nR, d_Skeys, nS, args, kind, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS, &km);
+    return join_semi(d_Rkeys, nR, d_Skeys, nS, args, kind, d_out, capacity, n_out, stream, stats, ms, SRC_KEYS,
+                     KeyMasks{d_Rvalid, d_Svalid});
 }
 
 int hwbrj_join_keys_outer_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
@@ -519,13 +514,12 @@ int hwbrj_join_keys_outer_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_
                                        double* ms) {
     if (const int rc = keys_rows_ok(d_Rkeys, nR, d_Skeys, nS)) return rc;
     if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true)) return rc;
-    const KeyMasks km{d_Rvalid, d_Svalid};
     return join_outer(d_Rkeys, nR, d_Skeys, nS, args, kind, -1, d_out, capacity, n_out, n_class, stream, stats, ms,
-                      SRC_KEYS, &km);
+                      SRC_KEYS, KeyMasks{d_Rvalid, d_Svalid});
 }
 
 // The group join: the materializing pipeline up to the join, then per-R-tuple accumulators instead of
-// pairs (Engine::run_group); the global-bitmap mode runs the counting join (its filter and its
+// pairs (JOIN_GROUP); the global-bitmap mode runs the counting join (its filter and its
 // "S-tuples after filter") and the group side pass. Both aggregate sets (agg: GroupAgg) share it:
 // their rows are 16 bytes and every clause of the contract is the same.
 // layout SRC_KEYS: d_R, d_S are int32 key columns, R's payload is its row index and the aggregated S
@@ -533,7 +527,7 @@ int hwbrj_join_keys_outer_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_
 static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void* d_Svals, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, uint32_t agg, void* d_out, uint64_t capacity,
                       uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms,
-                      int layout, const KeyMasks* masks = nullptr) {
+                      int layout, const KeyMasks& masks = KeyMasks{}) {
     static_assert(sizeof(hwbrj_group_row_t) == 16 && sizeof(hwbrj_group_minmax_row_t) == 16,
                   "a row is one 16-byte store");
     if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {  // (before any device call)
@@ -552,18 +546,12 @@ static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void*
         set_last_error("group join: |S| must be below 2^32 rows (32-bit counts)");
         return 3;
     }
-    Engine* e = engine_for_current_device();
-    if (!e) return 10;  // (last error set by engine_for_current_device)
-    const GroupReq req{(uint4*) d_out, capacity, kind == HWBRJ_GROUP_ALL, agg, d_Svals};
-    hwbrj_stats_t  st;
-    uint64_t       n = 0, pairs = 0;
-    const int      rc = pipeline_or_side_pass(
-        e, d_R, nR, d_S, nS, args, (hipStream_t) stream, layout, &st, &n, ms,
-        [&] { return e->run_group(d_R, nR, d_S, nS, args, (hipStream_t) stream, req, &st, &pairs, layout, masks); },
-        [&] { return e->group_side(d_R, nR, d_S, nS, req, &n, &pairs, (hipStream_t) stream, ms, layout); });
-    if (rc) return rc;
-    if (n_pairs) *n_pairs = pairs;
-    return publish(st, n, capacity, stats, n_out, "row");
+    JoinReq req = payload_req(JOIN_GROUP, d_out, capacity, layout, masks);
+    req.all     = kind == HWBRJ_GROUP_ALL;
+    req.agg     = agg;
+    req.s_val   = d_Svals;
+    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms, nullptr,
+                        n_pairs);
 }
 
 int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -633,9 +621,8 @@ static int join_keys_group_nulls(const int32_t* d_Rkeys, const uint8_t* d_Rvalid
                                  hwbrj_stats_t* stats, double* ms) {
     if (const int rc = keys_group_ok(d_Rkeys, nR, d_Skeys, d_Svals, nS)) return rc;
     if (const int rc = masks_ok(d_Rvalid, nR, d_Svalid, nS, args, true, d_Svals_valid)) return rc;
-    const KeyMasks km{d_Rvalid, d_Svalid, d_Svals_valid};
     return join_group(d_Rkeys, nR, d_Skeys, d_Svals, nS, args, kind, agg, d_out, capacity, n_out, n_pairs, stream,
-                      stats, ms, SRC_KEYS, &km);
+                      stats, ms, SRC_KEYS, KeyMasks{d_Rvalid, d_Svalid, d_Svals_valid});
 }
 
 int hwbrj_join_keys_group_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
@@ -828,7 +815,9 @@ static threadresult_t* materialize_to_host(const tuple_t* dR, uint64_t nR, const
     Engine*       e = engine_for_current_device();
     uint64_t      n = 0;
     hwbrj_stats_t st;
-    if (!e || materialize_pairs(e, dR, nR, dS, nS, args, dout, matches, &n, nullptr, &st, nullptr) != 0 ||
+    if (!e || pipeline_or_side_pass(e, JoinIn{dR, nR, dS, nS, args, nullptr},
+                                    payload_req(JOIN_PAIRS, dout, matches, SRC_TUPLES, KeyMasks{}), &st, &n, nullptr,
+                                    nullptr) != 0 ||
         n != matches)
         fatal("BPRO (materialize)");
     std::vector<tuple_t> host(matches ? matches : 1);

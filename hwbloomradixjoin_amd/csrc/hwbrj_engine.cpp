@@ -320,19 +320,31 @@ uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
     return (per + 31) / 32 + F + 1;
 }
 
-int Engine::run(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind,
-                int layout, const KeyMasks* masks) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind, nullptr, nullptr, nullptr, nullptr, layout, masks);
-    return rc ? rc : wait(st);
+int Engine::run(const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, JoinExtras* x) {
+    int rc = enqueue(in, req);
+    if (rc == 0) rc = wait(st);
+    if (rc || !x) return rc;
+    // (the join has completed; its ring slot is taken again by the next enqueue only)
+    if (req.kind == JOIN_OUTER) {
+        uint64_t c[2];  // {R-only, S-only}; inner = rows - both
+        HWBRJ_CHECK(hipMemcpy(c, last_slot_ + 6, sizeof(c), hipMemcpyDeviceToHost));
+        x->cls[0] = (uint64_t) st->matches - c[0] - c[1];
+        x->cls[1] = c[1];
+        x->cls[2] = c[0];
+    } else if (req.kind == JOIN_GROUP) {
+        HWBRJ_CHECK(hipMemcpy(&x->pairs, last_slot_ + 6, sizeof(x->pairs), hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 
-int Engine::run_async(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                      const bloom_filter_args_t* args, hipStream_t stream, int jkind, int layout) {
+int Engine::run_async(const JoinIn& in, int jkind, int layout) {
     // back-to-back joins: no phase events (each marker idles the GPU ~6 us between the kernels
     // around it, profiles/r03/gaps_*), so hwbrj_join_wait reports counts only
+    JoinReq req;
+    req.jkind    = jkind;
+    req.layout   = layout;
     phase_ev_    = false;
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, jkind, nullptr, nullptr, nullptr, nullptr, layout);
+    const int rc = enqueue(in, req);
     phase_ev_    = true;
     return rc;
 }
@@ -346,252 +358,438 @@ hipError_t Engine::mark(int i, hipStream_t stream) {
 
 int Engine::reserve(const uint2* dR, uint64_t nR, const uint2* dS, uint64_t nS,
                     const bloom_filter_args_t* args, int jkind) {
+    JoinReq req;
+    req.jkind    = jkind;
     alloc_only_  = true;
-    const int rc = enqueue(dR, nR, dS, nS, args, nullptr, jkind);
+    const int rc = enqueue(JoinIn{dR, nR, dS, nS, args, nullptr}, req);
     alloc_only_  = false;
     last_nj_     = 0;  // buffers may be new: the next join clears its job table
     return rc;
 }
 
-int Engine::run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                    const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
-                    hwbrj_stats_t* st, int layout, const KeyMasks* masks) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, &mat, nullptr, nullptr, nullptr, layout, masks);
-    return rc ? rc : wait(st);
+// ------------------------------------------------------------------- shape and limits
+JoinShape JoinShape::make(uint32_t F, uint32_t NSUB, uint32_t NJ, uint32_t nseg, uint32_t G, uint64_t capR,
+                          uint64_t capS, bool slice_mode) {
+    JoinShape s;
+    s.F = F, s.NSUB = NSUB, s.NJ = NJ, s.nseg = nseg, s.G = G;
+    s.CH         = probe_chunks_per_item();  // chunks per probe item
+    s.capR = capR, s.capS = capS;
+    s.LR = (uint64_t) G * capR, s.LS = (uint64_t) G * capS;  // max chunks
+    s.items_max  = (s.LS / s.CH + F + 1) * nseg;
+    s.BSW        = build_chunks_per_sweep();
+    s.SLOT       = build_sweep_slot();
+    s.sweeps_max = s.LR / s.BSW + F + 1;  // build sweeps over all R partitions
+    s.slice_mode = slice_mode;
+    return s;
 }
 
-int Engine::run_semi(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                     const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
-                     hwbrj_stats_t* st, int layout, const KeyMasks* masks) {
-    const int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, &semi, nullptr, nullptr, layout, masks);
-    return rc ? rc : wait(st);
+// the existence and payload joins' bitmap path: job keys v = code >> hash_shift < 2^17 (k_join_mat's condition)
+static bool pay_bitmap(const Geometry& g) { return g.sub_shift > 0 && 32 - g.hash_shift <= 17; }
+// the marks over S (one bit per chunk position): the anti join and the hash-set path's jobs of several
+// R pieces; the outer join that keeps S
+static bool semi_marks(const Geometry& g, const JoinReq& q) {
+    return q.kind == JOIN_SEMI && (q.anti || !pay_bitmap(g));
+}
+static bool uses_smark(const Geometry& g, const JoinReq& q) {
+    return semi_marks(g, q) || (q.kind == JOIN_OUTER && q.keep_s);
 }
 
-int Engine::run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                      const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
-                      hwbrj_stats_t* st, uint64_t cls[3], int layout, const KeyMasks* masks) {
-    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, &outer, nullptr, layout, masks);
-    if (rc == 0) rc = wait(st);
-    if (rc) return rc;
-    uint64_t c[2];  // (the join has completed; its ring slot is taken again by the next enqueue only)
-    HWBRJ_CHECK(hipMemcpy(c, outer_cls_, sizeof(c), hipMemcpyDeviceToHost));
-    cls[0] = (uint64_t) st->matches - c[0] - c[1];
-    cls[1] = c[1];
-    cls[2] = c[0];
-    return 0;
+// Pass-1 limits of a shape under a request: nullptr, or why it is refused (code 3)
+static const char* shape_limits(const JoinShape& s, const JoinReq& q) {
+    if (s.G > 512) return "more than 512 scatter workgroups (k_plan row groups)";
+    if (!part_fits(s.G, s.capR, s.capS))
+        return "relation too large for 27-bit chunk ids (|S| or |R| > ~4.2e9 tuples per GPU)";
+    if (q.carries_s_payloads() && (s.capS >= (1u << 21) || s.capR >= (1u << 21)))  // half indices (scatter_body_pay) < 2^22
+        return "relation too large for the materializing scatter's 22-bit half indices";
+    return nullptr;
 }
 
-int Engine::run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                      const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
-                      hwbrj_stats_t* st, uint64_t* pairs, int layout, const KeyMasks* masks) {
-    int rc = enqueue(dR, nR, dS, nS, args, stream, 0, nullptr, nullptr, nullptr, &group, layout, masks);
-    if (rc == 0) rc = wait(st);
-    if (rc) return rc;
-    // (the join has completed; its ring slot is taken again by the next enqueue only)
-    HWBRJ_CHECK(hipMemcpy(pairs, group_pairs_, sizeof(*pairs), hipMemcpyDeviceToHost));
-    return 0;
+// What both pipelines keep: the sides, the build sweeps' runs, the survivor runs of surv_segs segments,
+// the result ring and the job table.
+// jparts: nparts [NJ] | job_surv [NJ] | nextra; jtask: extra parts {job, part}
+// (job_surv is left zero by k_join_split for the NJ jobs it saw: a join with another NJ clears the
+// whole buffer, *jnew, so no stale count of an earlier job layout is read; last_nj_ moves whether or
+// not an allocation fails)
+bool Engine::ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew) {
+    *jnew    = jparts.bytes < (size_t) (2 * s.NJ + 1) * 4 || s.NJ != last_nj_;
+    last_nj_ = s.NJ;
+    return R_.ensure(s.LR, s.G, s.F) && S_.ensure(s.LS, s.G, s.F) && rjoin.ensure(s.sweeps_max * s.SLOT * 4) &&
+           rrun.ensure(2 * s.sweeps_max * s.NSUB * 4) && surv.ensure(surv_segs * s.LS * 128) &&
+           survcnt.ensure(s.items_max * s.NSUB * 4) && survoff.ensure(s.items_max * s.NSUB * 4) &&
+           jring_.ensure(kJoinRing * ring_slot_bytes()) && jtask.ensure((size_t) join_extra_tasks() * 8) &&
+           jparts.ensure((size_t) (2 * s.NJ + 1) * 4);
 }
 
-// mat / semi / outer / group: the payload-carrying pipeline (pl below). mat carries both relations'
-// payloads, and so do outer and group (from the join on they have kernels of their own); semi only
-// S's: its R side runs the counting join's scatter and build (32-bit codes, no payloads).
-// layout: what dR and dS point to, SRC_TUPLES or SRC_KEYS (key columns: the counting join; mat /
-// semi / outer with the row index as the payload; group with R's row index and, as S's payloads, its
-// value column group->s_val: the S payload scatter then reads SRC_KEYS_VAL). It selects the kernels
-// that read the relations; the partition words and payloads, and so everything from the pools on, do
-// not depend on it.
-// masks: validity bitmaps of key columns (KeyMasks). A side with a bitmap runs the SRC_KEYS_MASK
-// scatter, the other side the kernel it runs without masks; nothing after the scatters knows: a NULL
-// key is in no partition. The rows that NULL keys contribute themselves (anti, outer) come from
-// k_null_rows after the join's own emit kernels, through the same row counter.
-// A group join on key columns takes them too, with a third bitmap for S's value column (masks->sv):
-// R runs the SRC_KEYS_MASK row-index scatter, S the SRC_KEYS_VAL_MASK scatter with one bitmap or two
-// (a row is placed iff every bit is set), k_join_group sees only what was placed, and under `all`
-// the NULL R rows' identity rows come from k_null_group_rows after it, through the same row counter.
-int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                    const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                    const MatReq* mat, const SemiReq* semi, const OuterReq* outer, const GroupReq* group,
-                    int layout, const KeyMasks* masks) {
-    const MatReq omat{outer ? outer->out : nullptr, outer ? outer->cap : group ? group->cap : 0};
-    if (outer || group) mat = &omat;  // (the materializing pipeline up to the join)
-    if (jkind < 0 || jkind > 2) {
+bool Engine::ensure_buffers(JoinCtx* c) {
+    const JoinShape& s = c->s;
+    const Geometry&  g = c->g;
+    bool ok = ensure_common(s, s.nseg, &c->jnew);
+    if (s.slice_mode) ok = ok && slices.ensure((uint64_t) s.F * s.nseg * g.seg_words * 4);
+    if (g.mode == MODE_GLOBAL) ok = ok && bitmap.ensure(((g.m + 31) / 32) * 4) && dense.ensure(c->in.nS * 4);
+    if (c->basic_kk) ok = ok && bpos.ensure(c->nRk * 4);
+    if (c->q.carries_s_payloads()) ok = ok && ppoolS.ensure(s.LS * 128) && survpos.ensure(s.nseg * s.LS * 128);
+    if (c->q.carries_r_payloads()) ok = ok && ppoolR.ensure(s.LR * 128) && rpay.ensure(s.sweeps_max * s.SLOT * 4);
+    if (uses_smark(g, c->q)) ok = ok && smark.ensure(s.LS * 4);
+    return ok;
+}
+
+// ------------------------------------------------------------------- parameter blocks
+ScatterParams Engine::scatter_params(const Geometry& g, const PartSide& side, uint64_t cap) const {
+    ScatterParams sp{};
+    sp.tabs = d_tabs_;
+    sp.g    = g;
+    side.bind(&sp, cap);
+    return sp;
+}
+
+// k_build over R's lists (R items = build sweeps); no slices, no payloads, 32-bit codes
+BuildParams Engine::build_params(const Geometry& g, const JoinShape& s) const {
+    BuildParams bp{};
+    bp.g           = g;
+    bp.tabs        = d_tabs_;
+    bp.pool        = R_.pool.as<uint32_t>();
+    bp.list        = R_.list.as<uint32_t>();
+    bp.list_start  = R_.lstart.as<uint32_t>();
+    bp.elem_start  = R_.estart.as<uint64_t>();
+    bp.sweep_start = R_.istart.as<uint32_t>();
+    bp.out_codes   = rjoin.as<uint32_t>();
+    bp.run_cnt     = rrun.as<uint32_t>();
+    bp.run_off     = rrun.as<uint32_t>() + s.sweeps_max * s.NSUB;
+    return bp;
+}
+
+// k_probe / k_probe_bitj over S's lists; no slices, no counter, no chunk positions, 32-bit codes
+ProbeParams Engine::probe_params(const Geometry& g, const JoinShape& s) const {
+    ProbeParams pp{};
+    pp.g               = g;
+    pp.tabs            = d_tabs_;
+    pp.pool            = S_.pool.as<uint32_t>();
+    pp.list            = S_.list.as<uint32_t>();
+    pp.list_start      = S_.lstart.as<uint32_t>();
+    pp.item_start      = S_.istart.as<uint32_t>();
+    pp.surv            = surv.as<uint32_t>();
+    pp.surv_seg_stride = s.seg_stride();
+    pp.surv_cnt        = survcnt.as<uint32_t>();
+    pp.surv_off        = survoff.as<uint32_t>();
+    pp.job_surv        = jparts.as<uint32_t>() + s.NJ;
+    return pp;
+}
+
+// k_join over the build's and the probe's runs, its partial sums in the ring slot; 32-bit codes
+JoinParams Engine::join_params(const Geometry& g, const JoinShape& s, char* slot, int jkind) const {
+    JoinParams jp{};
+    jp.r_codes         = rjoin.as<uint32_t>();
+    jp.r_sweep_start   = R_.istart.as<uint32_t>();
+    jp.r_cnt           = rrun.as<uint32_t>();
+    jp.r_off           = rrun.as<uint32_t>() + s.sweeps_max * s.NSUB;
+    jp.slot            = (uint32_t) s.SLOT;
+    jp.surv            = surv.as<uint32_t>();
+    jp.surv_cnt        = survcnt.as<uint32_t>();
+    jp.surv_off        = survoff.as<uint32_t>();
+    jp.item_start      = S_.istart.as<uint32_t>();
+    jp.list_start      = S_.lstart.as<uint32_t>();
+    jp.surv_seg_stride = s.seg_stride();
+    jp.nseg            = s.nseg;
+    jp.CH              = s.CH;
+    jp.log2NSUB        = g.log2NSUB;
+    jp.hash_shift      = g.hash_shift;
+    jp.bitmap          = join_uses_bitmap(g) ? 1u : 0u;
+    jp.jsum            = (uint64_t*) (slot + 128);  // 64 partial sums, one per 128-B line
+    jp.nparts          = jparts.as<uint32_t>();
+    jp.extra           = jtask.as<uint2>();
+    jp.nextra          = jparts.as<uint32_t>() + 2 * s.NJ;
+    jp.jkind           = (uint32_t) jkind;
+    jp.split_surv      = test_hooks().join_split;  // (tests: force the skew split)
+    jp.timing          = phase_ev_ ? 1u : 0u;      // (back-to-back joins: counts only)
+    return jp;
+}
+
+// what the jobs of the payload joins share with k_join's (xcd8: the launch wrappers)
+static JobInputs job_inputs(const JoinParams& jp, const uint32_t* surv_pos) {
+    JobInputs ji{};
+    ji.r_codes = jp.r_codes, ji.r_sweep_start = jp.r_sweep_start, ji.r_cnt = jp.r_cnt, ji.r_off = jp.r_off;
+    ji.slot = jp.slot, ji.surv = jp.surv, ji.surv_pos = surv_pos, ji.surv_cnt = jp.surv_cnt, ji.surv_off = jp.surv_off;
+    ji.item_start = jp.item_start, ji.list_start = jp.list_start, ji.surv_seg_stride = jp.surv_seg_stride;
+    ji.nseg = jp.nseg, ji.CH = jp.CH, ji.log2NSUB = jp.log2NSUB, ji.hash_shift = jp.hash_shift;
+    return ji;
+}
+
+// ------------------------------------------------------------------- Engine::enqueue
+// The host sequence behind every single-GPU join (JoinReq), stage by stage: validate, plan, ensure
+// buffers, take the ring slot, the S pass / R pass / build in their order rules (passes), probe, the
+// kind's join stage, finish.
+
+// 1. The refusals, in this order (the C ABI tests pin codes and messages), and the geometry.
+int Engine::validate(JoinCtx* c) {
+    const JoinReq& q  = c->q;
+    const JoinIn&  in = c->in;
+    if (q.jkind < 0 || q.jkind > 2) {
         set_last_error("unknown per-partition join algorithm");
         return 2;
     }
     HWBRJ_CHECK(hipSetDevice(device_));
     tab_.state = kTabNone;  // (buffers may grow or be rewritten from here on: tables_read)
-    Geometry    g;
-    std::string err;
-    const bool  pl = mat || semi;  // S payloads beside the words, the materializing geometry
-    if (layout != SRC_TUPLES && layout != SRC_KEYS) {
+    const bool group = q.kind == JOIN_GROUP;
+    if (q.layout != SRC_TUPLES && q.layout != SRC_KEYS) {
         set_last_error("relations are tuples or key columns");
         return 2;
     }
-    if (layout == SRC_KEYS && group && nS && !group->s_val) {
+    if (q.layout == SRC_KEYS && group && in.nS && !q.s_val) {
         set_last_error("key columns: a group join needs S's value column");
         return 2;
     }
     // (hwbrj_api.cpp refuses first; a group join produces no S row index, so S is not held to 2^31)
-    if (layout == SRC_KEYS && pl && (nR >= (1ull << 31) || (!group && nS >= (1ull << 31)))) {
+    if (q.layout == SRC_KEYS && q.carries_s_payloads() &&
+        (in.nR >= (1ull << 31) || (!group && in.nS >= (1ull << 31)))) {
         set_last_error("key columns: row indices are int32 (|R|, |S| < 2^31)");
         return 3;
     }
-    // the bitmap of each non-empty side, or nullptr (an empty column has no NULL rows)
-    const uint8_t* vR = masks && nR ? masks->r : nullptr;
-    const uint8_t* vS = masks && nS ? masks->s : nullptr;
-    const uint8_t* vV = masks && nS ? masks->sv : nullptr;  // (S's value column: the group joins)
-    if ((vR || vS || vV) && layout != SRC_KEYS) {
+    c->vR = in.nR ? q.masks.r : nullptr;
+    c->vS = in.nS ? q.masks.s : nullptr;
+    c->vV = in.nS ? q.masks.sv : nullptr;
+    const bool masked = c->vR || c->vS || c->vV;
+    if (masked && q.layout != SRC_KEYS) {
         set_last_error("validity bitmaps: key columns");
         return 2;
     }
-    if (vV && !group) {
+    if (c->vV && !group) {
         set_last_error("validity bitmaps: a value column's belongs to the group joins");
         return 2;
     }
-    // what the S payload scatter reads: the layout, or S's key column with its value column
-    const int layout_s = layout == SRC_KEYS && group ? SRC_KEYS_VAL : layout;
-    if (!plan_geometry(args, nR, &g, &err, pl)) {
+    std::string err;
+    if (!plan_geometry(in.args, in.nR, &c->g, &err, q.carries_s_payloads())) {
         set_last_error(err);
         return 2;
     }
-    if ((vR || vS || vV) && !masks_supported(g)) {  // (hwbrj_api.cpp refuses first, before any device call)
+    if (masked && !masks_supported(c->g)) {  // (hwbrj_api.cpp refuses first, before any device call)
         set_last_error("validity bitmaps need partition slices (blocked/sectorized, basic k = 1, or no filter)");
         return kRcMaskFilter;
     }
-    if (pl && g.mode == MODE_GLOBAL) {
+    if (q.carries_s_payloads() && c->g.mode == MODE_GLOBAL) {
         set_last_error("global-bitmap mode: materialized by the side pass");
         return kRcMatGlobal;
     }
-    if (!pl && g.mode == MODE_SLICE_BASIC && g.k > 1 && (uint64_t) g.k * nR <= (1ull << 31)) {
-        if (!stream) stream = own_stream_;
-        if (pending_ && stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(stream, ev_[8], 0));
-        return enqueue_basic_kk(dR, nR, dS, nS, g, stream, jkind, layout);
-    }
-    if (!stream) stream = own_stream_;
-    // Every join on this device shares this Engine's scratch (pools, lists, slices, counters):
-    // a join enqueued on another stream than a still-pending one must run after it (on the same
-    // stream, stream order does it: no wait packet between back-to-back joins).
-    if (pending_ && stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(stream, ev_[8], 0));
-    const uint32_t F = 1u << g.log2F, NSUB = 1u << g.log2NSUB, NJ = F * NSUB;
-    const bool     slice_mode = g.mode == MODE_SLICE_BLOCK || g.mode == MODE_SLICE_BASIC;
-    const uint32_t nseg       = slice_mode ? g.nseg : 1;
-    const uint32_t CH         = probe_chunks_per_item();  // chunks per probe item
-    const size_t   sc_lds     = pl ? scatter_pay_lds_bytes(g.log2F) : scatter_lds_bytes(g.log2F);
-    const uint32_t G          = (uint32_t) cus_ * wg_per_cu(sc_lds);
+    return 0;
+}
+
+// 2. The shape, and whether this join is a collective.
+void Engine::plan(JoinCtx* c) {
+    const Geometry& g  = c->g;
+    const bool      pl = c->q.carries_s_payloads();
+    const uint32_t  F = 1u << g.log2F, NSUB = 1u << g.log2NSUB;
+    const bool      slice_mode = g.mode == MODE_SLICE_BLOCK || g.mode == MODE_SLICE_BASIC;
+    const size_t    sc_lds     = pl ? scatter_pay_lds_bytes(g.log2F) : scatter_lds_bytes(g.log2F);
+    const uint32_t  G          = (uint32_t) cus_ * wg_per_cu(sc_lds);
     // basic k >= 2: the S-side buffers first partition the R keys' k * |R| bit positions
-    const bool     basic_kk = g.mode == MODE_SLICE_BASIC && g.k > 1;
-    const uint64_t nRk      = basic_kk ? (uint64_t) g.k * nR : 0;
+    c->basic_kk = g.mode == MODE_SLICE_BASIC && g.k > 1;
+    c->nRk      = c->basic_kk ? (uint64_t) g.k * c->in.nR : 0;
+    c->s = JoinShape::make(F, NSUB, F * NSUB, slice_mode ? g.nseg : 1, G, region_cap(c->in.nR, G, F),
+                           region_cap(std::max(c->in.nS, c->nRk), G, F), slice_mode);
     // the north_star's bitmap broadcast (opt-in, hwbrj_set_filter_broadcast) makes this join a
     // collective: from here on a failure of this rank alone must not leave its peers waiting in
     // ncclBroadcast, so every return before the first kernel goes through one status agreement
-    // (argument errors above fail alike on every rank)
-    const bool bcast = bcast_ && comm_ && slice_mode && !basic_kk;
+    // (enqueue's pre(); argument errors before it fail alike on every rank)
+    c->bcast = bcast_ && comm_ && slice_mode && !c->basic_kk;
+}
+
+int Engine::enqueue(const JoinIn& in, const JoinReq& req) {
+    JoinCtx c{in, req};
+    if (const int rc = validate(&c)) return rc;
+    // Every join on this device shares this Engine's scratch (pools, lists, slices, counters):
+    // a join enqueued on another stream than a still-pending one must run after it (on the same
+    // stream, stream order does it: no wait packet between back-to-back joins).
+    if (!c.in.stream) c.in.stream = own_stream_;
+    if (pending_ && c.in.stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(c.in.stream, ev_[8], 0));
+    if (!req.carries_s_payloads() && c.g.mode == MODE_SLICE_BASIC && c.g.k > 1 &&
+        (uint64_t) c.g.k * in.nR <= (1ull << 31))
+        return enqueue_basic_kk(c.in, c.g, req);
+    plan(&c);
     auto pre = [&](int rc) -> int {
-        if (!bcast || alloc_only_) return rc;
-        return rccl_agree_status(comm_, comm_world_, comm_rank_, rc, stream, &agree_);
+        if (!c.bcast || alloc_only_) return rc;
+        return rccl_agree_status(comm_, comm_world_, comm_rank_, rc, c.in.stream, &agree_);
     };
-    const uint64_t capR = region_cap(nR, G, F), capS = region_cap(std::max(nS, nRk), G, F);
-    const uint64_t LR = (uint64_t) G * capR, LS = (uint64_t) G * capS;  // max chunks
-    const uint64_t items_max = (LS / CH + F + 1) * nseg;
-    if (G > 512) {
-        set_last_error("more than 512 scatter workgroups (k_plan row groups)");
+    if (const char* why = shape_limits(c.s, req)) {
+        set_last_error(why);
         return pre(3);
     }
-    if (!part_fits(G, capR, capS)) {
-        set_last_error("relation too large for 27-bit chunk ids (|S| or |R| > ~4.2e9 tuples per GPU)");
-        return pre(3);
-    }
-    if (pl && (capS >= (1u << 21) || capR >= (1u << 21))) {  // half indices (scatter_body_pay) < 2^22
-        set_last_error("relation too large for the materializing scatter's 22-bit half indices");
-        return pre(3);
-    }
-    bool ok = R_.ensure(LR, G, F) && S_.ensure(LS, G, F);
-    const uint64_t BSW = build_chunks_per_sweep(), SLOT = build_sweep_slot();
-    const uint64_t sweeps_max = LR / BSW + F + 1;  // build sweeps over all R partitions
-    ok &= rjoin.ensure(sweeps_max * SLOT * 4) && rrun.ensure(2 * sweeps_max * NSUB * 4);
-    ok &= surv.ensure(nseg * LS * 128) && survcnt.ensure(items_max * NSUB * 4) &&
-          survoff.ensure(items_max * NSUB * 4);
-    ok &= jring_.ensure(kJoinRing * ring_slot_bytes());
-    // jparts: nparts [NJ] | job_surv [NJ] | nextra; jtask: extra parts {job, part}
-    // (job_surv is left zero by k_join_split for the NJ jobs it saw: a join with another NJ
-    // clears the whole buffer, so no stale count of an earlier job layout is read)
-    const bool jnew = jparts.bytes < (size_t) (2 * NJ + 1) * 4 || NJ != last_nj_;
-    last_nj_ = NJ;
-    ok &= jtask.ensure((size_t) join_extra_tasks() * 8) && jparts.ensure((size_t) (2 * NJ + 1) * 4);
-    if (slice_mode) ok &= slices.ensure((uint64_t) F * nseg * g.seg_words * 4);
-    if (g.mode == MODE_GLOBAL) ok &= bitmap.ensure(((g.m + 31) / 32) * 4) && dense.ensure(nS * 4);
-    if (basic_kk) ok &= bpos.ensure(nRk * 4);
-    if (pl) ok &= ppoolS.ensure(LS * 128) && survpos.ensure(nseg * LS * 128);
-    if (mat) ok &= ppoolR.ensure(LR * 128) && rpay.ensure(sweeps_max * SLOT * 4);
-    // the existence join's marks (one bit per S chunk position): anti, and the hash-set path's jobs
-    // of several R pieces
-    const bool semi_bm   = g.sub_shift > 0 && 32 - g.hash_shift <= 17;  // (k_join_mat's bitmap condition)
-    const bool semi_mark = semi && (semi->anti || !semi_bm);
-    if (semi_mark || (outer && outer->keep_s)) ok &= smark.ensure(LS * 4);
-    if (!ok) {
+    if (!ensure_buffers(&c)) {
         set_last_error("hipMalloc failed (device memory)");
         return pre(4);
     }
     if (alloc_only_) return 0;
     if (const int rc = pre(0)) return rc;
     // this join's result slot (ring_take collects a full ring first)
-    uint32_t  rslot      = 0;
-    bool      rtimed     = false;  // (the S scatter's timing events, below)
-    char*     sm         = (char*) ring_take(&rslot);
-    if (!sm) return 1;
-    uint64_t* d_result   = (uint64_t*) sm;      // [0] matches
-    uint64_t* d_dcount   = (uint64_t*) sm + 1;  // [1] dense survivor count (global mode)
-    uint64_t* d_filtered = (uint64_t*) sm + 2;  // [2] S-tuples after filter
+    if (!(c.sm = (char*) ring_take(&c.rslot))) return 1;
+    if (const int rc = passes(&c)) return rc;
+    ProbeParams pp;
+    if (const int rc = probe(c, &pp)) return rc;
+    JoinParams jp = join_params(c.g, c.s, c.sm, req.jkind);
+    jp.r_kbits    = c.kbits;
+    jp.fmt_cnt    = pp.fmt_cnt;
+    const JobInputs ji = job_inputs(jp, survpos.as<uint32_t>());
+    int rc = 0;
+    switch (req.kind) {
+        case JOIN_COUNT: rc = join_count(c, jp); break;
+        case JOIN_PAIRS: rc = join_pairs(c, ji); break;
+        case JOIN_SEMI: rc = join_semi(c, ji); break;
+        case JOIN_OUTER: rc = join_outer(c, ji); break;
+        case JOIN_GROUP: rc = join_group(c, ji); break;
+    }
+    if (rc) return rc;
+    TabRec t;  // the shape of this join's tables (tables_info / tables_read)
+    // (the existence / outer / group join's tables: not read back)
+    t.state = req.kind == JOIN_COUNT || req.kind == JOIN_PAIRS ? kTabJoin : kTabOther;
+    t.mat   = req.carries_r_payloads();
+    t.s     = c.s;
+    (void) probe_lds_bytes(c.g, &t.stage_cap, req.carries_s_payloads());
+    t.jkind  = (uint32_t) req.jkind;
+    t.kbits  = c.kbits;
+    t.bitmap = t.mat ? (pay_bitmap(c.g) ? 1u : 0u) : jp.bitmap;
+    t.split  = jp.split_surv;
+    JoinRec r;
+    r.slot     = c.rslot;
+    r.fmt      = pp.fmt_cnt != nullptr;
+    r.kbits    = c.kbits;
+    r.slots    = !req.carries_s_payloads();  // (the matches are in k_join's partial sums)
+    r.timed    = c.rtimed;
+    r.s_masked = c.vS != nullptr || c.vV != nullptr;
+    return finish(c.in, c.g, c.s_first, t, r);
+}
 
+// 8. The epilogue of both enqueue paths: the join's completion event, what wait() and the next
+// enqueue need of it, its tables' shape and its record in the ring.
+int Engine::finish(const JoinIn& in, const Geometry& g, bool s_first, const TabRec& tab, JoinRec rec) {
+    HWBRJ_CHECK(hipEventRecord(ev_[8], in.stream));
+    HWBRJ_CHECK(hipGetLastError());
+    pending_        = true;
+    pending_rc_     = 0;
+    pending_ev_     = phase_ev_;
+    pending_sfirst_ = s_first;
+    pending_stream_ = in.stream;
+    have_filter_    = in.args != nullptr;
+    last_g_         = g;
+    tab_            = tab;
+    tab_.sync       = phase_ev_;
+    tab_.g          = g;
+    rec.args = in.args != nullptr;
+    rec.nS   = in.nS;
+    rec.g    = g;
+    jr_.push_back(rec);
+    return 0;
+}
+
+// S pass-1 and its lists (async joins: on a second stream, concurrent with the R side). It starts
+// from a clear block: no zeroing (the R scatter's alone), and the shared slot of seg_cnt / src_val /
+// valid holds only what this source reads.
+// (a group join on key columns with a bitmap on S: the value-column scatter's masked form, one
+// bitmap or both, whichever column they belong to: vmask = {vS ? vS : vV, vS ? vV : nullptr})
+int Engine::s_pass(const JoinCtx& c, hipStream_t st, bool marks, hipEvent_t* tev) {
+    const Geometry&  g  = c.g;
+    // what the S payload scatter reads: the layout, or S's key column with its value column
+    const int        layout_s   = c.q.layout == SRC_KEYS && c.q.kind == JOIN_GROUP ? SRC_KEYS_VAL : c.q.layout;
+    const bool       val_masked = layout_s == SRC_KEYS_VAL && (c.vS || c.vV);
+    ScatterValParams ss{};
+    (ScatterParams&) ss = scatter_params(g, S_, c.s.capS);
+    ss.vmask[0] = !val_masked ? nullptr : c.vS ? c.vS : c.vV;
+    ss.vmask[1] = val_masked && c.vS ? c.vV : nullptr;
+    ss.n        = c.in.nS;
+    if (g.mode == MODE_GLOBAL) {
+        launch_probe_global(c.in.dS, c.q.layout, c.in.nS, g, d_tabs_, bitmap.as<uint32_t>(), dense.as<uint32_t>(),
+                            c.result() + 1, st);
+        ss.src   = dense.p;
+        ss.n_dev = c.result() + 1;
+    } else {
+        ss.src = c.in.dS;
+        if (layout_s == SRC_KEYS_VAL) ss.src_val = c.q.s_val;  // (shares seg_cnt's slot: not SRC_CODES)
+        else if (c.vS) ss.valid = c.vS;                          // (the same slot: never both)
+    }
+    ss.ppool = c.q.carries_s_payloads() ? ppoolS.as<uint32_t>() : nullptr;
+    if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
+    launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : val_masked ? SRC_KEYS_VAL_MASK : c.vS ? SRC_KEYS_MASK : layout_s,
+                   SIDE_S, c.s.G, st);
+    if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
+    if (marks) HWBRJ_CHECK(mark(4, st));
+    index_side(S_, c.s.capS, g.log2F, c.s.CH, c.s.nseg, c.s.G, st);
+    if (marks) HWBRJ_CHECK(mark(5, st));
+    return 0;
+}
+
+// R: pass-1 (+ filter), its lists, the build sweeps; then the slices' broadcast, or their build from
+// bit positions (basic k >= 2).
+int Engine::r_side(const JoinCtx& c) {
+    const Geometry&  g = c.g;
+    const JoinShape& s = c.s;
+    const JoinIn&    in = c.in;
+    hipStream_t      stream = in.stream;
+    const bool       rpay_on = c.q.carries_r_payloads();
+    if (g.mode == MODE_GLOBAL)
+        launch_build_global(in.dR, c.q.layout, in.nR, g, d_tabs_, bitmap.as<uint32_t>(), stream);
     // zeroing (the reference callocs before its timer, :1583, :1601): the counts and the join's
-    // extra-task count are zeroed by the R scatter's workgroup 0 (two memset dispatches less per
-    // join); job_surv is left zero by every join's k_join_split, so it is cleared only when new
-    if (jnew) HWBRJ_CHECK(hipMemsetAsync(jparts.p, 0, jparts.bytes, stream));
-    if (g.mode == MODE_GLOBAL) HWBRJ_CHECK(hipMemsetAsync(bitmap.p, 0, bitmap.bytes, stream));
-
-    ScatterParams sp{};
-    sp.tabs = d_tabs_;
-    sp.g    = g;
-    sp.zero_small = (uint32_t*) sm;  // (the R scatter only: cleared below)
-    sp.zero_word  = jparts.as<uint32_t>() + 2 * NJ;
-
-    // S pass-1 and its lists (below; async joins: on a second stream, concurrent with the R side)
-    // (a group join on key columns with a bitmap on S: the value-column scatter's masked form, one
-    // bitmap or both, whichever column they belong to)
-    const bool val_masked = layout_s == SRC_KEYS_VAL && (vS || vV);
-    auto s_pass = [&](hipStream_t st, bool marks, hipEvent_t* tev = nullptr) -> int {
-        ScatterValParams ss{};
-        (ScatterParams&) ss = sp;
-        ss.vmask[0]      = !val_masked ? nullptr : vS ? vS : vV;
-        ss.vmask[1]      = val_masked && vS ? vV : nullptr;
-        ss.zero_small    = nullptr;
-        ss.zero_word     = nullptr;
-        if (g.mode == MODE_GLOBAL) {
-            launch_probe_global(dS, layout, nS, g, d_tabs_, bitmap.as<uint32_t>(), dense.as<uint32_t>(),
-                                d_dcount, st);
-            ss.src   = dense.p;
-            ss.n     = nS;
-            ss.n_dev = d_dcount;
-        } else {
-            ss.src   = dS;
-            ss.n     = nS;
-            ss.n_dev = nullptr;
-            if (layout_s == SRC_KEYS_VAL) ss.src_val = group->s_val;  // (shares seg_cnt's slot: not SRC_CODES)
-            else if (vS) ss.valid = vS;                               // (the same slot: never both)
+    // extra-task count are zeroed by this scatter's workgroup 0 (two memset dispatches less per join)
+    ScatterParams sp = scatter_params(g, R_, s.capR);
+    sp.src        = in.dR;
+    sp.n          = in.nR;
+    sp.ppool      = rpay_on ? ppoolR.as<uint32_t>() : nullptr;
+    sp.zero_small = (uint32_t*) c.sm;
+    sp.zero_word  = jparts.as<uint32_t>() + 2 * s.NJ;
+    if (c.vR) sp.valid = c.vR;
+    launch_scatter(sp, c.vR ? SRC_KEYS_MASK : c.q.layout, SIDE_R, s.G, stream);
+    HWBRJ_CHECK(mark(1, stream));
+    index_side(R_, s.capR, g.log2F, (uint32_t) s.BSW, 1, s.G, stream);
+    HWBRJ_CHECK(mark(2, stream));
+    BuildParams bp = build_params(g, s);
+    bp.slices  = s.slice_mode ? slices.as<uint32_t>() : nullptr;
+    bp.ppool   = rpay_on ? ppoolR.as<uint32_t>() : nullptr;
+    bp.out_pay = rpay_on ? rpay.as<uint32_t>() : nullptr;
+    bp.kbits   = c.kbits;
+    // the broadcast: rank 0 builds the slices, the other ranks only sub-partition R for the join
+    // and receive them over RCCL (HWBRJ_HOOK_BCAST_NONROOT: this rank takes the non-root side, for
+    // tests at world 1; value 2 zeroes the slices first, so the counts show whether k_build wrote any)
+    const int nonroot_hook = c.bcast && comm_world_ == 1 ? test_hooks().bcast_nonroot : 0;  // (tests only: world 1)
+    bp.no_slices = c.bcast && (comm_rank_ != 0 || nonroot_hook) ? 1u : 0u;
+    if (nonroot_hook == 2) HWBRJ_CHECK(hipMemsetAsync(slices.p, 0, slices.bytes, stream));
+    launch_build(bp, s.F, stream);
+    if (c.bcast) {
+        const int rc = rccl_broadcast(comm_, slices.p, (size_t) s.F * s.nseg * g.seg_words * 4, 0, stream);
+        if (rc) {  // kernels of this join are enqueued: later joins must still order after them
+            (void) hipEventRecord(ev_[8], stream);
+            pending_        = true;
+            pending_stream_ = stream;
+            pending_rc_     = rc;
+            pending_err_    = hwbrj_last_error();
+            return rc;
         }
-        S_.bind(&ss, capS);
-        ss.ppool = pl ? ppoolS.as<uint32_t>() : nullptr;
-        if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
-        launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : val_masked ? SRC_KEYS_VAL_MASK : vS ? SRC_KEYS_MASK : layout_s,
-                       SIDE_S, G, st);
-        if (tev) HWBRJ_CHECK(hipEventRecord(tev[1], st));
-        if (marks) HWBRJ_CHECK(mark(4, st));
-        index_side(S_, capS, g.log2F, CH, nseg, G, st);
-        if (marks) HWBRJ_CHECK(mark(5, st));
-        return 0;
-    };
+    }
+    if (c.basic_kk) {
+        // basic k >= 2: the k bit positions of every R key, partitioned by slice with the S-side
+        // scatter buffers (free until the S pass), then one LDS slice build per partition
+        launch_bitpos(in.dR, c.q.layout, in.nR, g, bpos.as<uint32_t>(), stream);
+        ScatterParams sb = scatter_params(g, S_, s.capS);  // (a clear block: seg_cnt's slot is read)
+        sb.src = bpos.p;
+        sb.n   = c.nRk;
+        launch_scatter(sb, SRC_CODES, SIDE_R, s.G, stream);
+        index_side(S_, s.capS, g.log2F, (uint32_t) s.BSW, 1, s.G, stream);
+        launch_slice_fill(S_.pool.as<uint32_t>(), S_.list.as<uint32_t>(), S_.lstart.as<uint32_t>(), g,
+                          slices.as<uint32_t>(), stream);
+    }
+    HWBRJ_CHECK(mark(3, stream));
+    return 0;
+}
+
+// 5. The S pass, the R side and the build, in their order rules.
+int Engine::passes(JoinCtx* c) {
+    const Geometry& g      = c->g;
+    hipStream_t     stream = c->in.stream;
+    const bool      pl     = c->q.carries_s_payloads();
+    // job_surv is left zero by every counting join's k_join_split, so the job table is cleared only when new
+    if (c->jnew) HWBRJ_CHECK(hipMemsetAsync(jparts.p, 0, jparts.bytes, stream));
+    if (g.mode == MODE_GLOBAL) HWBRJ_CHECK(hipMemsetAsync(bitmap.p, 0, bitmap.bytes, stream));
+    // 3-byte join keys from build / probe to k_join, unless the last join this Engine waited for had
+    // probe items too large for the stage (their 32-bit survivor runs make the join read two formats,
+    // k_join_mixed): a performance hint only, both paths give the same counts
+    c->kbits = !pl && join_pack3(g) && pack3_hint_ ? join_key_bits(g) : 0u;  // 18 at the north star
     HWBRJ_CHECK(mark(0, stream));
-    const bool ovl = HWBRJ_OVL_ASYNC && !phase_ev_ && g.mode != MODE_GLOBAL && !basic_kk && !pl && !bcast;
+    const bool ovl = HWBRJ_OVL_ASYNC && !phase_ev_ && g.mode != MODE_GLOBAL && !c->basic_kk && !pl && !c->bcast;
     if (ovl) {  // S pass on the side stream (with phase events, its phases would show inside the R side's)
         if (!ovl_stream_) {
             HWBRJ_CHECK(hipStreamCreateWithFlags(&ovl_stream_, hipStreamNonBlocking));
@@ -605,11 +803,11 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
         hipEvent_t* tev = nullptr;
         if (async_timing_) {
             for (int i = 0; i < 2; i++)
-                if (!tev_[rslot][i]) HWBRJ_CHECK(hipEventCreateWithFlags(&tev_[rslot][i], hipEventDisableSystemFence));
-            tev = tev_[rslot];
+                if (!tev_[c->rslot][i]) HWBRJ_CHECK(hipEventCreateWithFlags(&tev_[c->rslot][i], hipEventDisableSystemFence));
+            tev = tev_[c->rslot];
         }
-        rtimed = tev != nullptr;
-        if (const int rc = s_pass(ovl_stream_, false, tev)) return rc;
+        c->rtimed = tev != nullptr;
+        if (const int rc = s_pass(*c, ovl_stream_, false, tev)) return rc;
         HWBRJ_CHECK(hipEventRecord(ovl_ev_[1], ovl_stream_));
     }
     // The S pass runs first: then the filter slices (written by k_build) and the R pool (written by
@@ -617,302 +815,162 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     // Cache still holds much of them. Not in the global mode (the R scatter's workgroup 0 zeroes the
     // dense count the S pass's global probe adds to) nor for basic k >= 2 (the R side borrows the
     // S-side buffers).
-    const bool s_first = !ovl && g.mode != MODE_GLOBAL && !basic_kk;
-    if (s_first)
-        if (const int rc = s_pass(stream, true)) return rc;
-    // ---------------------------------------------------------------- R: pass-1 (+ filter)
-    if (g.mode == MODE_GLOBAL)
-        launch_build_global(dR, layout, nR, g, d_tabs_, bitmap.as<uint32_t>(), stream);
-    sp.src        = dR;
-    sp.n          = nR;
-    sp.n_dev      = nullptr;
-    sp.ppool      = mat ? ppoolR.as<uint32_t>() : nullptr;
-    R_.bind(&sp, capR);
-    if (vR) sp.valid = vR;
-    launch_scatter(sp, vR ? SRC_KEYS_MASK : layout, SIDE_R, G, stream);
-    sp.valid = nullptr;  // (seg_cnt's slot: the basic k >= 2 scatters below read it)
-    HWBRJ_CHECK(mark(1, stream));
-    index_side(R_, capR, g.log2F, (uint32_t) BSW, 1, G, stream);
-    HWBRJ_CHECK(mark(2, stream));
-    sp.ppool      = nullptr;
-    sp.zero_small = nullptr;
-    sp.zero_word  = nullptr;
-    BuildParams bp{};
-    bp.g          = g;
-    bp.tabs       = d_tabs_;
-    bp.pool       = R_.pool.as<uint32_t>();
-    bp.list       = R_.list.as<uint32_t>();
-    bp.list_start = R_.lstart.as<uint32_t>();
-    bp.elem_start = R_.estart.as<uint64_t>();
-    bp.slices     = slice_mode ? slices.as<uint32_t>() : nullptr;
-    bp.sweep_start = R_.istart.as<uint32_t>();  // (R items = build sweeps)
-    bp.out_codes   = rjoin.as<uint32_t>();
-    bp.run_cnt     = rrun.as<uint32_t>();
-    bp.run_off     = rrun.as<uint32_t>() + sweeps_max * NSUB;
-    bp.ppool       = mat ? ppoolR.as<uint32_t>() : nullptr;
-    bp.out_pay     = mat ? rpay.as<uint32_t>() : nullptr;
-    // 3-byte join keys from build / probe to k_join, unless the last join this Engine waited for had
-    // probe items too large for the stage (their 32-bit survivor runs make the join read two formats,
-    // k_join_mixed): a performance hint only, both paths give the same counts
-    const bool     pack3 = !pl && join_pack3(g) && pack3_hint_;
-    const uint32_t kbits = pack3 ? join_key_bits(g) : 0u;  // 18 at the north star
-    bp.kbits       = kbits;
-    // the broadcast: rank 0 builds the slices, the other ranks only sub-partition R for the join
-    // and receive them over RCCL (HWBRJ_HOOK_BCAST_NONROOT: this rank takes the non-root side, for
-    // tests at world 1; value 2 zeroes the slices first, so the counts show whether k_build wrote any)
-    const int nonroot_hook = bcast && comm_world_ == 1 ? test_hooks().bcast_nonroot : 0;  // (tests only: world 1)
-    bp.no_slices = bcast && (comm_rank_ != 0 || nonroot_hook) ? 1u : 0u;
-    if (nonroot_hook == 2) HWBRJ_CHECK(hipMemsetAsync(slices.p, 0, slices.bytes, stream));
-    launch_build(bp, F, stream);
-    if (bcast) {
-        const int rc = rccl_broadcast(comm_, slices.p, (size_t) F * nseg * g.seg_words * 4, 0, stream);
-        if (rc) {  // kernels of this join are enqueued: later joins must still order after them
-            (void) hipEventRecord(ev_[8], stream);
-            pending_        = true;
-            pending_stream_ = stream;
-            pending_rc_     = rc;
-            pending_err_    = hwbrj_last_error();
-            return rc;
-        }
-    }
-    if (basic_kk) {
-        // basic k >= 2: the k bit positions of every R key, partitioned by slice with the S-side
-        // scatter buffers (free until the S pass), then one LDS slice build per partition
-        launch_bitpos(dR, layout, nR, g, bpos.as<uint32_t>(), stream);
-        sp.src        = bpos.p;
-        sp.n          = nRk;
-        sp.n_dev      = nullptr;
-        S_.bind(&sp, capS);
-        launch_scatter(sp, SRC_CODES, SIDE_R, G, stream);
-        index_side(S_, capS, g.log2F, (uint32_t) BSW, 1, G, stream);
-        launch_slice_fill(S_.pool.as<uint32_t>(), S_.list.as<uint32_t>(), S_.lstart.as<uint32_t>(), g,
-                          slices.as<uint32_t>(), stream);
-    }
-    HWBRJ_CHECK(mark(3, stream));
-    // ---------------------------------------------------------------- S: pass-1 (+ probe)
+    c->s_first = !ovl && g.mode != MODE_GLOBAL && !c->basic_kk;
+    if (c->s_first)
+        if (const int rc = s_pass(*c, stream, true, nullptr)) return rc;
+    if (const int rc = r_side(*c)) return rc;
     if (ovl) {
         HWBRJ_CHECK(hipStreamWaitEvent(stream, ovl_ev_[1], 0));
         HWBRJ_CHECK(mark(4, stream));
         HWBRJ_CHECK(mark(5, stream));
-    } else if (!s_first) {
-        if (const int rc = s_pass(stream, true)) return rc;
+    } else if (!c->s_first) {
+        if (const int rc = s_pass(*c, stream, true, nullptr)) return rc;
     }
-    ProbeParams pp{};
-    pp.g               = g;
-    pp.tabs            = d_tabs_;
-    pp.pool            = S_.pool.as<uint32_t>();
-    pp.list            = S_.list.as<uint32_t>();
-    pp.list_start      = S_.lstart.as<uint32_t>();
-    pp.item_start      = S_.istart.as<uint32_t>();
-    pp.slices          = slice_mode ? slices.as<uint32_t>() : nullptr;
-    pp.surv            = surv.as<uint32_t>();
-    pp.surv_seg_stride = LS * 32;
-    pp.surv_cnt        = survcnt.as<uint32_t>();
-    pp.surv_off        = survoff.as<uint32_t>();
-    pp.filtered        = d_filtered;
-    pp.job_surv        = jparts.as<uint32_t>() + NJ;
-    pp.surv_pos        = pl ? survpos.as<uint32_t>() : nullptr;
-    pp.kbits           = kbits;
-    pp.fmt_cnt         = pl ? nullptr : (uint32_t*) sm + 10;  // (u64 word 5 of the slot: zeroed by the R scatter)
-    const size_t   pl_lds = probe_lds_bytes(g, nullptr, pl);
-    launch_probe(pp, (uint32_t) cus_ * wg_per_cu(pl_lds), stream);
-    HWBRJ_CHECK(mark(6, stream));  // (survivor sub-partitioning is fused into k_probe: no ev_[7])
+    return 0;
+}
+
+// 6. The probe (survivor sub-partitioning is fused into k_probe: no ev_[7]).
+int Engine::probe(const JoinCtx& c, ProbeParams* pp) {
+    const bool pl = c.q.carries_s_payloads();
+    *pp           = probe_params(c.g, c.s);
+    pp->slices    = c.s.slice_mode ? slices.as<uint32_t>() : nullptr;
+    pp->filtered  = c.result() + 2;
+    pp->surv_pos  = pl ? survpos.as<uint32_t>() : nullptr;
+    pp->kbits     = c.kbits;
+    pp->fmt_cnt   = pl ? nullptr : (uint32_t*) c.sm + 10;  // (u64 word 5 of the slot: zeroed by the R scatter)
+    launch_probe(*pp, (uint32_t) cus_ * wg_per_cu(probe_lds_bytes(c.g, nullptr, pl)), c.in.stream);
+    HWBRJ_CHECK(mark(6, c.in.stream));
     surv_fused_ = true;
-    // -------------------------------------------------------------------------- join
-    JoinParams jp{};
-    jp.r_codes         = rjoin.as<uint32_t>();
-    jp.r_sweep_start   = R_.istart.as<uint32_t>();
-    jp.r_cnt           = rrun.as<uint32_t>();
-    jp.r_off           = rrun.as<uint32_t>() + sweeps_max * NSUB;
-    jp.slot            = (uint32_t) SLOT;
-    jp.surv            = surv.as<uint32_t>();
-    jp.surv_cnt        = survcnt.as<uint32_t>();
-    jp.surv_off        = survoff.as<uint32_t>();
-    jp.item_start      = S_.istart.as<uint32_t>();
-    jp.list_start      = S_.lstart.as<uint32_t>();
-    jp.surv_seg_stride = LS * 32;
-    jp.nseg            = nseg;
-    jp.CH              = CH;
-    jp.log2NSUB        = g.log2NSUB;
-    jp.hash_shift      = g.hash_shift;
-    jp.bitmap          = join_uses_bitmap(g) ? 1u : 0u;
-    jp.jsum            = (uint64_t*) (sm + 128);  // 64 partial sums, one per 128-B line
-    jp.nparts          = jparts.as<uint32_t>();
-    jp.extra           = jtask.as<uint2>();
-    jp.nextra          = jparts.as<uint32_t>() + 2 * NJ;
-    jp.jkind           = (uint32_t) jkind;
-    jp.split_surv      = test_hooks().join_split;  // (tests: force the skew split)
-    jp.r_kbits         = kbits;
-    jp.fmt_cnt         = pp.fmt_cnt;
-    jp.timing          = phase_ev_ ? 1u : 0u;  // (back-to-back joins: counts only)
-    JobInputs ji{};  // what the jobs of the payload joins share (xcd8: the launch wrappers)
-    if (mat || semi) {
-        ji.r_codes         = jp.r_codes;
-        ji.r_sweep_start   = jp.r_sweep_start;
-        ji.r_cnt           = jp.r_cnt;
-        ji.r_off           = jp.r_off;
-        ji.slot            = jp.slot;
-        ji.surv            = jp.surv;
-        ji.surv_pos        = survpos.as<uint32_t>();
-        ji.surv_cnt        = jp.surv_cnt;
-        ji.surv_off        = jp.surv_off;
-        ji.item_start      = jp.item_start;
-        ji.list_start      = jp.list_start;
-        ji.surv_seg_stride = jp.surv_seg_stride;
-        ji.nseg            = nseg;
-        ji.CH              = CH;
-        ji.log2NSUB        = g.log2NSUB;
-        ji.hash_shift      = g.hash_shift;
+    return 0;
+}
+
+// 7. The join stage, by kind: each owns its memsets, its emit kernel and its NULL-row kernels. Rows
+// and matches are counted in word 0 of the ring slot.
+int Engine::join_count(const JoinCtx& c, const JoinParams& jp) {
+    launch_join(jp, c.s.NJ, jparts.as<uint32_t>() + c.s.NJ, c.in.stream);
+    return 0;
+}
+
+// (k_join_split, which leaves job_surv zero for the next join, runs in no payload join)
+int Engine::clear_job_surv(const JoinCtx& c) {
+    HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + c.s.NJ, 0, (size_t) c.s.NJ * 4, c.in.stream));
+    return 0;
+}
+
+MatJoinParams Engine::mat_params(const JoinCtx& c, const JobInputs& ji) const {
+    MatJoinParams mp{};
+    mp.j     = ji;
+    mp.r_pay = rpay.as<uint32_t>();
+    mp.bm    = pay_bitmap(c.g) ? 1u : 0u;
+    mp.s_pay = ppoolS.as<uint32_t>();
+    mp.out   = c.q.kind == JOIN_GROUP ? nullptr : (uint2*) c.q.out;  // (k_join_group has its own)
+    mp.cap   = c.q.cap;
+    mp.count = (unsigned long long*) c.result();
+    return mp;
+}
+
+int Engine::join_pairs(const JoinCtx& c, const JobInputs& ji) {
+    if (const int rc = clear_job_surv(c)) return rc;
+    launch_join_mat(mat_params(c, ji), c.s.NJ, c.in.stream);
+    return 0;
+}
+
+int Engine::join_semi(const JoinCtx& c, const JobInputs& ji) {
+    const JoinReq& q      = c.q;
+    hipStream_t    stream = c.in.stream;
+    const bool     marks  = semi_marks(c.g, q);
+    uint2*         out    = (uint2*) q.out;
+    if (const int rc = clear_job_surv(c)) return rc;
+    if (marks) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, c.s.LS * 4, stream));
+    SemiJoinParams sj{};
+    sj.j     = ji;
+    sj.bm    = pay_bitmap(c.g) ? 1u : 0u;
+    sj.anti  = q.anti ? 1u : 0u;
+    sj.basic = c.g.mode == MODE_SLICE_BASIC ? 1u : 0u;
+    sj.s_pay = ppoolS.as<uint32_t>();
+    sj.mark  = marks ? smark.as<uint32_t>() : nullptr;
+    sj.tabs  = d_tabs_;
+    sj.out   = out;
+    sj.cap   = q.cap;
+    sj.count = (unsigned long long*) c.result();
+    launch_join_semi(sj, c.s.NJ, stream);
+    if (!q.anti) return 0;
+    // every unmarked S tuple: the filter's rejects and the unmatched survivors
+    SemiEmitParams se{};
+    se.pool       = S_.pool.as<uint32_t>();
+    se.ppool      = ppoolS.as<uint32_t>();
+    se.list       = S_.list.as<uint32_t>();
+    se.list_start = S_.lstart.as<uint32_t>();
+    se.mark       = smark.as<uint32_t>();
+    se.g          = c.g;
+    se.tabs       = d_tabs_;
+    se.out        = out;
+    se.cap        = q.cap;
+    se.count      = sj.count;
+    launch_semi_emit(se, (uint32_t) cus_ * 2, stream);
+    if (c.vS)  // a NULL key has no partner: {the stored key, row}
+        launch_null_rows(NullRowsParams{c.vS, (const uint32_t*) c.in.dS, c.in.nS, NULL_ROWS_ANTI, 0u, out, q.cap,
+                                        sj.count, nullptr},
+                         (uint32_t) cus_ * 2, stream);
+    return 0;
+}
+
+int Engine::join_outer(const JoinCtx& c, const JobInputs& ji) {
+    const JoinReq& q      = c.q;
+    hipStream_t    stream = c.in.stream;
+    uint2*         out    = (uint2*) q.out;
+    if (const int rc = clear_job_surv(c)) return rc;
+    if (q.keep_s) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, c.s.LS * 4, stream));
+    // the class counters: u64 words 6 (R-only) and 7 (S-only) of the slot (last_slot_); inner = rows - both
+    unsigned long long* rows = (unsigned long long*) c.result();
+    unsigned long long* cls  = rows + 6;
+    OuterJoinParams     op{};
+    op.m        = mat_params(c, ji);
+    op.keep_s   = q.keep_s ? 1u : 0u;
+    op.keep_r   = q.keep_r ? 1u : 0u;
+    op.null_pay = q.null_pay;
+    op.mark     = q.keep_s ? smark.as<uint32_t>() : nullptr;
+    op.n_r_only = cls;
+    launch_join_outer(op, c.s.NJ, stream);
+    if (q.keep_s) {  // every unmarked S tuple: the filter's rejects and the unmatched survivors
+        OuterEmitParams oe{};
+        oe.ppool      = ppoolS.as<uint32_t>();
+        oe.list       = S_.list.as<uint32_t>();
+        oe.list_start = S_.lstart.as<uint32_t>();
+        oe.mark       = smark.as<uint32_t>();
+        oe.log2F      = c.g.log2F;
+        oe.null_pay   = q.null_pay;
+        oe.out        = out;
+        oe.cap        = q.cap;
+        oe.count      = rows;
+        oe.n_s_only   = cls + 1;
+        launch_outer_emit(oe, (uint32_t) cus_ * 2, stream);
     }
-    if (mat) {
-        // (k_join_split, which leaves job_surv zero for the next join, does not run here)
-        HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));
-        if (outer && outer->keep_s) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
-        MatJoinParams mp{};
-        mp.j               = ji;
-        mp.r_pay           = rpay.as<uint32_t>();
-        mp.bm              = (g.sub_shift > 0 && 32 - g.hash_shift <= 17) ? 1u : 0u;
-        mp.s_pay           = ppoolS.as<uint32_t>();
-        mp.out             = mat->out;
-        mp.cap             = mat->cap;
-        mp.count           = (unsigned long long*) d_result;
-        if (outer) {
-            // the class counters: u64 words 6 (R-only) and 7 (S-only) of the slot, zeroed with the
-            // counts by the R scatter and not read by ring_collect; inner = rows - both
-            unsigned long long* cls = (unsigned long long*) sm + 6;
-            outer_cls_ = (const uint64_t*) cls;
-            OuterJoinParams op{};
-            op.m        = mp;
-            op.keep_s   = outer->keep_s ? 1u : 0u;
-            op.keep_r   = outer->keep_r ? 1u : 0u;
-            op.null_pay = outer->null_pay;
-            op.mark     = outer->keep_s ? smark.as<uint32_t>() : nullptr;
-            op.n_r_only = cls;
-            launch_join_outer(op, NJ, stream);
-            if (outer->keep_s) {  // every unmarked S tuple: the filter's rejects and the unmatched survivors
-                OuterEmitParams oe{};
-                oe.ppool      = ppoolS.as<uint32_t>();
-                oe.list       = S_.list.as<uint32_t>();
-                oe.list_start = S_.lstart.as<uint32_t>();
-                oe.mark       = smark.as<uint32_t>();
-                oe.log2F      = g.log2F;
-                oe.null_pay   = outer->null_pay;
-                oe.out        = outer->out;
-                oe.cap        = outer->cap;
-                oe.count      = (unsigned long long*) d_result;
-                oe.n_s_only   = cls + 1;
-                launch_outer_emit(oe, (uint32_t) cus_ * 2, stream);
-            }
-            // NULL keys: S-only and R-only rows of the sides that are kept
-            if (outer->keep_s && vS)
-                launch_null_rows(NullRowsParams{vS, nullptr, nS, NULL_ROWS_S, outer->null_pay, outer->out, outer->cap,
-                                                (unsigned long long*) d_result, cls + 1},
-                                 (uint32_t) cus_ * 2, stream);
-            if (outer->keep_r && vR)
-                launch_null_rows(NullRowsParams{vR, nullptr, nR, NULL_ROWS_R, outer->null_pay, outer->out, outer->cap,
-                                                (unsigned long long*) d_result, cls},
-                                 (uint32_t) cus_ * 2, stream);
-        } else if (group) {
-            // the pair counter: u64 word 6 of the slot (as the outer join's class counters)
-            unsigned long long* pairs = (unsigned long long*) sm + 6;
-            group_pairs_ = (const uint64_t*) pairs;
-            GroupJoinParams gp{};
-            gp.m       = mp;
-            gp.all     = group->all ? 1u : 0u;
-            gp.agg     = group->agg;
-            gp.out     = group->out;
-            gp.n_pairs = pairs;
-            launch_join_group(gp, NJ, stream);
-            // NULL keys of R are in no partition, so no job saw them: under ALL their identity rows
-            // come from here, through the same row counter
-            if (group->all && vR)
-                launch_null_group_rows(NullGroupRowsParams{vR, nR, group->agg, group->out, group->cap,
-                                                           (unsigned long long*) d_result},
-                                       (uint32_t) cus_ * 2, stream);
-        } else {
-            launch_join_mat(mp, NJ, stream);
-        }
-    } else if (semi) {
-        HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + NJ, 0, (size_t) NJ * 4, stream));  // (as above)
-        if (semi_mark) HWBRJ_CHECK(hipMemsetAsync(smark.p, 0, LS * 4, stream));
-        SemiJoinParams sj{};
-        sj.j               = ji;
-        sj.bm              = semi_bm ? 1u : 0u;
-        sj.anti            = semi->anti ? 1u : 0u;
-        sj.basic           = g.mode == MODE_SLICE_BASIC ? 1u : 0u;
-        sj.s_pay           = ppoolS.as<uint32_t>();
-        sj.mark            = semi_mark ? smark.as<uint32_t>() : nullptr;
-        sj.tabs            = d_tabs_;
-        sj.out             = semi->out;
-        sj.cap             = semi->cap;
-        sj.count           = (unsigned long long*) d_result;
-        launch_join_semi(sj, NJ, stream);
-        if (semi->anti) {  // every unmarked S tuple: the filter's rejects and the unmatched survivors
-            SemiEmitParams se{};
-            se.pool       = S_.pool.as<uint32_t>();
-            se.ppool      = ppoolS.as<uint32_t>();
-            se.list       = S_.list.as<uint32_t>();
-            se.list_start = S_.lstart.as<uint32_t>();
-            se.mark       = smark.as<uint32_t>();
-            se.g          = g;
-            se.tabs       = d_tabs_;
-            se.out        = semi->out;
-            se.cap        = semi->cap;
-            se.count      = (unsigned long long*) d_result;
-            launch_semi_emit(se, (uint32_t) cus_ * 2, stream);
-            if (vS)  // a NULL key has no partner: {the stored key, row}
-                launch_null_rows(NullRowsParams{vS, (const uint32_t*) dS, nS, NULL_ROWS_ANTI, 0u, semi->out, semi->cap,
-                                                (unsigned long long*) d_result, nullptr},
-                                 (uint32_t) cus_ * 2, stream);
-        }
-    } else {
-        launch_join(jp, NJ, jparts.as<uint32_t>() + NJ, stream);
-    }
-    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
-    HWBRJ_CHECK(hipGetLastError());
-    pending_      = true;
-    pending_rc_   = 0;
-    pending_args_ = args != nullptr;
-    pending_nS_   = nS;
-    pending_ev_   = phase_ev_;
-    pending_sfirst_ = s_first;
-    pending_fmt_    = pp.fmt_cnt != nullptr;
-    pending_slots_  = !pl;
-    pending_stream_ = stream;
-    have_filter_  = args != nullptr;
-    last_g_       = g;
-    {  // the shape of this join's tables (tables_info / tables_read)
-        tab_.state = semi || outer || group ? kTabOther : kTabJoin;  // (the existence / outer / group join's tables: not read back)
-        tab_.sync  = phase_ev_;
-        tab_.mat   = mat != nullptr;
-        tab_.g     = g;
-        tab_.G     = G;
-        tab_.nseg  = nseg;
-        tab_.CH    = CH;
-        tab_.BSW   = (uint32_t) BSW;
-        tab_.SLOT  = (uint32_t) SLOT;
-        (void) probe_lds_bytes(g, &tab_.stage_cap, pl);
-        tab_.jkind  = (uint32_t) jkind;
-        tab_.kbits  = kbits;
-        tab_.bitmap = mat ? ((g.sub_shift > 0 && 32 - g.hash_shift <= 17) ? 1u : 0u) : jp.bitmap;
-        tab_.split  = jp.split_surv;
-        tab_.NJ     = NJ;
-        tab_.sweeps_max = sweeps_max;
-        tab_.seg_stride = LS * 32;
-    }
-    {
-        JoinRec r;
-        r.slot  = rslot;
-        r.args  = args != nullptr;
-        r.fmt   = pending_fmt_;
-        r.kbits = kbits;
-        r.slots = !pl;
-        r.timed = rtimed;
-        r.nS    = nS;
-        r.g     = g;
-        r.s_masked = vS != nullptr || vV != nullptr;
-        ring_push(r);
-    }
+    // NULL keys: S-only and R-only rows of the sides that are kept
+    if (q.keep_s && c.vS)
+        launch_null_rows(NullRowsParams{c.vS, nullptr, c.in.nS, NULL_ROWS_S, q.null_pay, out, q.cap, rows, cls + 1},
+                         (uint32_t) cus_ * 2, stream);
+    if (q.keep_r && c.vR)
+        launch_null_rows(NullRowsParams{c.vR, nullptr, c.in.nR, NULL_ROWS_R, q.null_pay, out, q.cap, rows, cls},
+                         (uint32_t) cus_ * 2, stream);
+    return 0;
+}
+
+int Engine::join_group(const JoinCtx& c, const JobInputs& ji) {
+    const JoinReq& q = c.q;
+    if (const int rc = clear_job_surv(c)) return rc;
+    GroupJoinParams gp{};
+    gp.m       = mat_params(c, ji);
+    gp.all     = q.all ? 1u : 0u;
+    gp.agg     = q.agg;
+    gp.out     = (uint4*) q.out;
+    gp.n_pairs = (unsigned long long*) c.result() + 6;  // the pair counter: u64 word 6 of the slot (last_slot_)
+    launch_join_group(gp, c.s.NJ, c.in.stream);
+    // NULL keys of R are in no partition, so no job saw them: under ALL their identity rows come
+    // from here, through the same row counter
+    if (q.all && c.vR)
+        launch_null_group_rows(NullGroupRowsParams{c.vR, c.in.nR, q.agg, gp.out, q.cap, gp.m.count},
+                               (uint32_t) cus_ * 2, c.in.stream);
     return 0;
 }
 
@@ -922,43 +980,38 @@ int Engine::enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
 // the last pass are re-partitioned by code (MODE_CODE_OF_KEY), the join's layout, so the join
 // takes its bitmap path like the blocked filter's: R is partitioned by code for the join, and the
 // slices are built from R's partitioned bit positions (k_bitpos, k_slice_fill).
-int Engine::enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                             const Geometry& g, hipStream_t stream, int jkind, int layout) {
-    Geometry    gj;  // the join layout: R and the survivors partitioned by code
-    std::string err;
+int Engine::enqueue_basic_kk(const JoinIn& in, const Geometry& g, const JoinReq& req) {
+    const void *   dR = in.dR, *dS = in.dS;
+    const uint64_t nR = in.nR, nS = in.nS;
+    hipStream_t    stream = in.stream;
+    const int      layout = req.layout;
+    Geometry       gj;  // the join layout: R and the survivors partitioned by code
+    std::string    err;
     if (!plan_geometry(nullptr, nR, &gj, &err)) {
         set_last_error(err);
         return 2;
     }
     const uint32_t F = 1u << g.log2F, Fj = 1u << gj.log2F, Fm = std::max(F, Fj);
-    const uint32_t NSUB = 1u << gj.log2NSUB, NJ = Fj * NSUB;
-    const uint32_t nseg = g.nseg, CH = probe_chunks_per_item();
+    const uint32_t NSUB = 1u << gj.log2NSUB, nseg = g.nseg, CH = probe_chunks_per_item();
     // one workgroup per CU for every scatter and bit pass: pass j's workgroup w writes region w
     // (rw words) and pass j + 1's scatter workgroup w partitions it
     const uint32_t G    = (uint32_t) cus_;
     const uint64_t nRk  = (uint64_t) g.k * nR;
     const uint64_t Ib   = ((nS / 32 + (uint64_t) G * (Fm + 1)) / CH + Fm + 1) * nseg;  // items of a pass
     const uint64_t rw   = ((Ib + G - 1) / G) * CH * 32;  // words a pass workgroup may append
-    const uint64_t capR = region_cap(nR, G, Fm);
-    const uint64_t capS = std::max(region_cap(std::max(nS, nRk), G, Fm), rw / 32 + Fm + 1);
-    const uint64_t LR = (uint64_t) G * capR, LS = (uint64_t) G * capS;
-    const uint64_t items_max = (LS / CH + Fm + 1) * nseg;
-    if (!part_fits(G, capR, capS)) {
-        set_last_error("relation too large for 27-bit chunk ids (|S| or |R| > ~4.2e9 tuples per GPU)");
+    // the buffers hold the larger of the filter's and the join's partition counts; the jobs are the join's
+    const JoinShape s = JoinShape::make(Fm, NSUB, Fj * NSUB, nseg, G, region_cap(nR, G, Fm),
+                                        std::max(region_cap(std::max(nS, nRk), G, Fm), rw / 32 + Fm + 1), true);
+    const uint64_t capR = s.capR, capS = s.capS, BSW = s.BSW;
+    if (const char* why = shape_limits(s, req)) {
+        set_last_error(why);
         return 3;
     }
-    bool ok = R_.ensure(LR, G, Fm) && S_.ensure(LS, G, Fm);
-    const uint64_t BSW = build_chunks_per_sweep(), SLOT = build_sweep_slot();
-    const uint64_t sweeps_max = LR / BSW + Fm + 1;
-    ok &= rjoin.ensure(sweeps_max * SLOT * 4) && rrun.ensure(2 * sweeps_max * NSUB * 4);
-    ok &= surv.ensure(LS * 128) && survcnt.ensure(items_max * NSUB * 4) && survoff.ensure(items_max * NSUB * 4);
-    ok &= jring_.ensure(kJoinRing * ring_slot_bytes());
-    const bool jnew = jparts.bytes < (size_t) (2 * NJ + 1) * 4 || NJ != last_nj_;
-    last_nj_ = NJ;
-    ok &= jtask.ensure((size_t) join_extra_tasks() * 8) && jparts.ensure((size_t) (2 * NJ + 1) * 4);
-    ok &= slices.ensure((uint64_t) F * nseg * g.seg_words * 4) && (g.k <= G || bpos.ensure(nRk * 4));
+    bool jnew = false;
+    bool ok   = ensure_common(s, 1, &jnew);
+    ok = ok && slices.ensure((uint64_t) F * nseg * g.seg_words * 4) && (g.k <= G || bpos.ensure(nRk * 4));
     const uint32_t NC = (g.k + 64) & ~63u;  // pass counters [0, k - 1) + the dummy [NC - 1]
-    ok &= dense.ensure(G * rw * 4) && dense2.ensure(G * rw * 4) && kkcnt.ensure(NC * 8 + 2 * G * 4);
+    ok = ok && dense.ensure(G * rw * 4) && dense2.ensure(G * rw * 4) && kkcnt.ensure(NC * 8 + 2 * G * 4);
     if (!ok) {
         set_last_error("hipMalloc failed (device memory)");
         return 4;
@@ -973,50 +1026,30 @@ int Engine::enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64
     HWBRJ_CHECK(hipMemsetAsync(sm, 0, 64, stream));
     HWBRJ_CHECK(hipMemsetAsync(kkcnt.p, 0, kkcnt.bytes, stream));
     if (jnew) HWBRJ_CHECK(hipMemsetAsync(jparts.p, 0, jparts.bytes, stream));
-    HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + 2 * NJ, 0, 4, stream));
-
-    auto side = [&](const PartSide& s, uint64_t cap) {
-        ScatterParams sp{};
-        sp.tabs = d_tabs_;
-        s.bind(&sp, cap);
-        return sp;
-    };
+    HWBRJ_CHECK(hipMemsetAsync(jparts.as<uint32_t>() + 2 * s.NJ, 0, 4, stream));
 
     HWBRJ_CHECK(mark(0, stream));
     // ---------------------------------------------------------------- R: the join layout
-    ScatterParams sp = side(R_, capR);
-    sp.g   = gj;
+    ScatterParams sp = scatter_params(gj, R_, capR);
     sp.src = dR;
     sp.n   = nR;
     launch_scatter(sp, layout, SIDE_R, G, stream);
     HWBRJ_CHECK(mark(1, stream));
     index_side(R_, capR, gj.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
-    BuildParams bp{};
-    bp.g           = gj;
-    bp.tabs        = d_tabs_;
-    bp.pool        = R_.pool.as<uint32_t>();
-    bp.list        = R_.list.as<uint32_t>();
-    bp.list_start  = R_.lstart.as<uint32_t>();
-    bp.elem_start  = R_.estart.as<uint64_t>();
-    bp.sweep_start = R_.istart.as<uint32_t>();
-    bp.out_codes   = rjoin.as<uint32_t>();
-    bp.run_cnt     = rrun.as<uint32_t>();
-    bp.run_off     = rrun.as<uint32_t>() + sweeps_max * NSUB;
-    launch_build(bp, Fj, stream);
+    launch_build(build_params(gj, s), Fj, stream);
     // ---------------------------------------------------------------- the filter slices
-    sp = side(S_, capS);
     if (g.k <= G) {  // R's k bit positions partitioned by slice straight from the tuples
         Geometry gp = g;
         gp.mode     = MODE_BASIC_POS;
-        sp.g        = gp;
+        sp          = scatter_params(gp, S_, capS);
         sp.src      = dR;
         sp.n        = nRk;
         sp.vn       = nR;
         launch_scatter(sp, layout, SIDE_R, G, stream);
     } else {
         launch_bitpos(dR, layout, nR, g, bpos.as<uint32_t>(), stream);
-        sp.g   = g;
+        sp     = scatter_params(g, S_, capS);
         sp.src = bpos.p;
         sp.n   = nRk;
         launch_scatter(sp, SRC_CODES, SIDE_R, G, stream);
@@ -1026,8 +1059,7 @@ int Engine::enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64
                       slices.as<uint32_t>(), stream);
     HWBRJ_CHECK(mark(3, stream));
     // ---------------------------------------------------------------- S: by the slice of bit 0
-    sp     = side(S_, capS);
-    sp.g   = g;
+    sp     = scatter_params(g, S_, capS);
     sp.src = dS;
     sp.n   = nS;
     launch_scatter(sp, layout, SIDE_S, G, stream);
@@ -1035,21 +1067,15 @@ int Engine::enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64
     index_side(S_, capS, g.log2F, CH, nseg, G, stream);
     HWBRJ_CHECK(mark(5, stream));
     // ---------------------------------------------------------------- one bit per pass
-    const uint32_t PG = G;
-    ProbeParams    pb{};
-    pb.pool       = S_.pool.as<uint32_t>();
-    pb.list       = S_.list.as<uint32_t>();
-    pb.list_start = S_.lstart.as<uint32_t>();
-    pb.item_start = S_.istart.as<uint32_t>();
-    pb.slices     = slices.as<uint32_t>();
+    ProbeParams pb = probe_params(g, s);  // (k_probe_bitj reads the lists, the slices and what a pass sets)
+    pb.slices      = slices.as<uint32_t>();
     uint32_t* dz[2] = {dense.as<uint32_t>(), dense2.as<uint32_t>()};
     for (uint32_t j = 0; j < g.k; j++) {
         Geometry gb = g;
         gb.bitj     = j;
         if (j > 0) {  // the candidates of pass j - 1, by the slice of bit j
             gb.mode       = MODE_BASIC_BITJ;
-            sp            = side(S_, capS);
-            sp.g          = gb;
+            sp            = scatter_params(gb, S_, capS);
             sp.src        = dz[(j - 1) & 1];
             sp.seg_cnt    = wgc[(j - 1) & 1];
             sp.seg_stride = rw;
@@ -1061,114 +1087,65 @@ int Engine::enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64
         pb.surv_seg_stride = rw;
         pb.wg_cnt          = wgc[j & 1];
         pb.filtered        = j + 1 < g.k ? cnt + j : d_filtered;
-        launch_probe_bitj(pb, PG, stream);
+        launch_probe_bitj(pb, G, stream);
     }
     HWBRJ_CHECK(mark(6, stream));
     // ---------------------------------------------------------------- survivors: the join layout
     {
         Geometry gc = gj;
         gc.mode     = MODE_CODE_OF_KEY;
-        sp          = side(S_, capS);
-        sp.g        = gc;
+        sp            = scatter_params(gc, S_, capS);
         sp.src        = dz[(g.k - 1) & 1];
         sp.seg_cnt    = wgc[(g.k - 1) & 1];
         sp.seg_stride = rw;
         launch_scatter(sp, SRC_CODES, SIDE_S, G, stream);
         index_side(S_, capS, gj.log2F, CH, 1, G, stream);
     }
-    ProbeParams pp{};
-    pp.g               = gj;
-    pp.tabs            = d_tabs_;
-    pp.pool            = S_.pool.as<uint32_t>();
-    pp.list            = S_.list.as<uint32_t>();
-    pp.list_start      = S_.lstart.as<uint32_t>();
-    pp.item_start      = S_.istart.as<uint32_t>();
-    pp.surv            = surv.as<uint32_t>();
-    pp.surv_seg_stride = LS * 32;
-    pp.surv_cnt        = survcnt.as<uint32_t>();
-    pp.surv_off        = survoff.as<uint32_t>();
-    pp.filtered        = cnt + NC - 1;  // (counted by the last bit pass)
-    pp.job_surv        = jparts.as<uint32_t>() + NJ;
-    const size_t   pl_lds = probe_lds_bytes(gj, nullptr);
-    launch_probe(pp, (uint32_t) cus_ * wg_per_cu(pl_lds), stream);
+    ProbeParams pp = probe_params(gj, s);
+    pp.filtered    = cnt + NC - 1;  // (counted by the last bit pass)
+    launch_probe(pp, (uint32_t) cus_ * wg_per_cu(probe_lds_bytes(gj, nullptr)), stream);
     HWBRJ_CHECK(mark(7, stream));
     surv_fused_ = false;
     // -------------------------------------------------------------------------- join
-    JoinParams jp{};
-    jp.r_codes         = rjoin.as<uint32_t>();
-    jp.r_sweep_start   = R_.istart.as<uint32_t>();
-    jp.r_cnt           = rrun.as<uint32_t>();
-    jp.r_off           = rrun.as<uint32_t>() + sweeps_max * NSUB;
-    jp.slot            = (uint32_t) SLOT;
-    jp.surv            = surv.as<uint32_t>();
-    jp.surv_cnt        = survcnt.as<uint32_t>();
-    jp.surv_off        = survoff.as<uint32_t>();
-    jp.item_start      = S_.istart.as<uint32_t>();
-    jp.list_start      = S_.lstart.as<uint32_t>();
-    jp.surv_seg_stride = LS * 32;
-    jp.nseg            = 1;
-    jp.CH              = CH;
-    jp.log2NSUB        = gj.log2NSUB;
-    jp.hash_shift      = gj.hash_shift;
-    jp.bitmap          = join_uses_bitmap(gj) ? 1u : 0u;
-    jp.jsum            = (uint64_t*) (sm + 128);
-    jp.nparts          = jparts.as<uint32_t>();
-    jp.extra           = jtask.as<uint2>();
-    jp.nextra          = jparts.as<uint32_t>() + 2 * NJ;
-    jp.jkind           = (uint32_t) jkind;
-    jp.split_surv      = test_hooks().join_split;
-    jp.timing          = phase_ev_ ? 1u : 0u;
-    launch_join(jp, NJ, jparts.as<uint32_t>() + NJ, stream);
-    HWBRJ_CHECK(hipEventRecord(ev_[8], stream));
-    HWBRJ_CHECK(hipGetLastError());
-    pending_      = true;
-    pending_rc_   = 0;
-    pending_args_ = true;
-    pending_nS_   = nS;
-    pending_ev_   = phase_ev_;
-    pending_sfirst_ = false;
-    pending_fmt_    = false;
-    pending_slots_  = true;
-    pending_stream_ = stream;
-    have_filter_  = true;
-    last_g_       = g;
-    tab_.state    = kTabOther;  // (the repartitioning passes' tables: not read back)
-    tab_.sync     = phase_ev_;
-    {
-        JoinRec r;
-        r.slot  = rslot;
-        r.args  = true;
-        r.slots = true;
-        r.nS    = nS;
-        r.g     = g;
-        ring_push(r);
+    JoinParams jp = join_params(gj, s, sm, req.jkind);
+    jp.nseg       = 1;  // (the survivors were re-partitioned without segments)
+    launch_join(jp, s.NJ, jparts.as<uint32_t>() + s.NJ, stream);
+    TabRec t;
+    t.state = kTabOther;  // (the repartitioning passes' tables: not read back)
+    JoinRec r;
+    r.slot  = rslot;
+    r.slots = true;
+    return finish(in, g, false, t, r);
+}
+
+// h = the six result words of a slot b; with slots, k_join's partial sums behind them added
+static void slot_counts(const uint64_t* b, bool slots, uint64_t h[6]) {
+    const size_t S = join_sum_slots(), W = join_sum_stride();
+    for (int i = 0; i < 6; i++) h[i] = b[i];
+    for (size_t j = 0; slots && j < S; j++) {
+        h[0] += b[16 + j * W];
+        h[3] += b[16 + j * W + 1];
+        h[4] += b[16 + j * W + 2];
     }
-    return 0;
 }
 
 int read_join_counts(const void* small, bool slots, hipStream_t stream, uint64_t h[6]) {
-    const size_t          S = join_sum_slots(), W = join_sum_stride();
-    std::vector<uint64_t> buf(16 + (slots ? S * W : 0));  // 128 bytes of result words, then the slots
+    std::vector<uint64_t> buf(16 + (slots ? join_sum_slots() * join_sum_stride() : 0));  // 128 bytes of result words, then the slots
     if (hipMemcpyAsync(buf.data(), small, buf.size() * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess) {
         set_last_error("reading the join's counts failed");
         return 1;
     }
-    for (int i = 0; i < 6; i++) h[i] = buf[i];
-    if (slots)
-        for (size_t j = 0; j < S; j++) {
-            h[0] += buf[16 + j * W];
-            h[3] += buf[16 + j * W + 1];
-            h[4] += buf[16 + j * W + 2];
-        }
+    slot_counts(buf.data(), slots, h);
     return 0;
 }
 
 void* Engine::ring_take(uint32_t* slot) {
     if (jr_.size() >= (size_t) kJoinRing && ring_collect()) return nullptr;
-    *slot    = jr_next_;
-    jr_next_ = (jr_next_ + 1) % kJoinRing;
-    return (char*) jring_.p + (size_t) *slot * ring_slot_bytes();
+    *slot      = jr_next_;
+    jr_next_   = (jr_next_ + 1) % kJoinRing;
+    last_slot_ = (const uint64_t*) ((char*) jring_.p + (size_t) *slot * ring_slot_bytes());
+    return (void*) last_slot_;
 }
 
 // The counts of every join in jr_ (all completed once ev_[8] has: they share the device's scratch,
@@ -1182,17 +1159,9 @@ int Engine::ring_collect() {
     const uint32_t a = jr_.front().slot, z = jr_.back().slot;
     const size_t   off = a <= z ? (size_t) a * SB : 0, len = a <= z ? (size_t) (z - a + 1) * SB : kJoinRing * SB;
     HWBRJ_CHECK(hipMemcpy((char*) buf.data() + off, (char*) jring_.p + off, len, hipMemcpyDeviceToHost));
-    const size_t S = join_sum_slots(), W = join_sum_stride();
     for (const JoinRec& r : jr_) {
-        const uint64_t* b = buf.data() + (size_t) r.slot * (SB / 8);
-        uint64_t        h[6];
-        for (int i = 0; i < 6; i++) h[i] = b[i];
-        if (r.slots)
-            for (size_t j = 0; j < S; j++) {
-                h[0] += b[16 + j * W];
-                h[3] += b[16 + j * W + 1];
-                h[4] += b[16 + j * W + 2];
-            }
+        uint64_t h[6];
+        slot_counts(buf.data() + (size_t) r.slot * (SB / 8), r.slots, h);
         if (r.fmt) pack3_hint_ = (uint32_t) h[5] == 0;  // (k_probe's count, ProbeParams::fmt_cnt)
         const Geometry& g = r.g;
         hwbrj_stats_t   st;
@@ -1253,9 +1222,9 @@ static int wait_common(hwbrj_stats_t* last, bool phases, const hipEvent_t* ev, b
     return 0;
 }
 
-int Engine::wait_all(hwbrj_stats_t* st, int cap, int* n) {
-    HWBRJ_CHECK(hipSetDevice(device_));
-    if (n) *n = 0;
+// What wait and wait_all start with: the last join has completed and every join since the last wait
+// is collected (jdone_), or why not.
+int Engine::wait_pending() {
     if (!pending_) {
         ring_drop();
         set_last_error("no join has been enqueued");
@@ -1267,7 +1236,13 @@ int Engine::wait_all(hwbrj_stats_t* st, int cap, int* n) {
         set_last_error(pending_err_);
         return pending_rc_;
     }
-    if (const int rc = ring_collect()) return rc;
+    return ring_collect();
+}
+
+int Engine::wait_all(hwbrj_stats_t* st, int cap, int* n) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (n) *n = 0;
+    if (const int rc = wait_pending()) return rc;
     for (size_t i = 0; i < jdone_.size(); i++) {  // ticks -> ms (only the last has phase times)
         if (i + 1 == jdone_.size()) {
             if (const int rc = wait_common(&jdone_[i], pending_ev_, ev_, pending_sfirst_, surv_fused_)) return rc;
@@ -1290,18 +1265,7 @@ int Engine::wait_all(hwbrj_stats_t* st, int cap, int* n) {
 
 int Engine::wait(hwbrj_stats_t* st) {
     HWBRJ_CHECK(hipSetDevice(device_));
-    if (!pending_) {
-        ring_drop();
-        set_last_error("no join has been enqueued");
-        return 6;
-    }
-    HWBRJ_CHECK(hipEventSynchronize(ev_[8]));
-    if (pending_rc_) {  // the last join stopped after some of its kernels (a failed broadcast)
-        ring_drop();
-        set_last_error(pending_err_);
-        return pending_rc_;
-    }
-    if (const int rc = ring_collect()) return rc;
+    if (const int rc = wait_pending()) return rc;
     if (!jdone_.empty()) {  // (else: the last join was collected before; its stats again)
         last_st_ = jdone_.back();
         jdone_.clear();
@@ -1376,18 +1340,18 @@ int Engine::tables_info(uint64_t* out, int n) {
     out[HWBRJ_TI_NSUB]        = 1u << t.g.log2NSUB;
     out[HWBRJ_TI_SUB_SHIFT]   = t.g.sub_shift;
     out[HWBRJ_TI_HASH_SHIFT]  = t.g.hash_shift;
-    out[HWBRJ_TI_NSEG]        = t.nseg;
+    out[HWBRJ_TI_NSEG]        = t.s.nseg;
     out[HWBRJ_TI_BITMAP]      = t.bitmap;
     out[HWBRJ_TI_JKIND]       = t.jkind;
     out[HWBRJ_TI_KEY_BITS]    = t.kbits ? t.kbits : 32u;
-    out[HWBRJ_TI_GRID]        = t.G;
-    out[HWBRJ_TI_CH]          = t.CH;
-    out[HWBRJ_TI_BSW]         = t.BSW;
-    out[HWBRJ_TI_SLOT]        = t.SLOT;
+    out[HWBRJ_TI_GRID]        = t.s.G;
+    out[HWBRJ_TI_CH]          = t.s.CH;
+    out[HWBRJ_TI_BSW]         = t.s.BSW;
+    out[HWBRJ_TI_SLOT]        = t.s.SLOT;
     out[HWBRJ_TI_STAGE_CAP]   = t.stage_cap;
     out[HWBRJ_TI_SWEEPS]      = sweeps;
     out[HWBRJ_TI_ITEMS]       = items;
-    out[HWBRJ_TI_JOBS]        = t.NJ;
+    out[HWBRJ_TI_JOBS]        = t.s.NJ;
     out[HWBRJ_TI_MAT]         = t.mat ? 1u : 0u;
     out[HWBRJ_TI_SPLIT]       = t.split ? t.split : c.join_task_surv;
     out[HWBRJ_TI_SC_ROUND]    = c.sc_round;
@@ -1436,10 +1400,10 @@ int Engine::tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t*
         HWBRJ_CHECK(hipMemcpy(is.data(), S_.istart.p, (F + 1) * 4, hipMemcpyDeviceToHost));
         HWBRJ_CHECK(hipMemcpy(ls.data(), S_.lstart.p, (F + 1) * 4, hipMemcpyDeviceToHost));
         const uint32_t q = (uint32_t) (std::upper_bound(is.begin(), is.end(), it) - is.begin()) - 1;
-        const uint32_t npc = (is[q + 1] - is[q]) / t.nseg, local = it - is[q];
+        const uint32_t npc = (is[q + 1] - is[q]) / t.s.nseg, local = it - is[q];
         const uint32_t seg = local / npc, piece = local - seg * npc;
-        const uint32_t nch = std::min(t.CH, ls[q + 1] - ls[q] - piece * t.CH);
-        src  = surv.as<uint32_t>() + (uint64_t) seg * t.seg_stride + (uint64_t) (ls[q] + piece * t.CH) * 32;
+        const uint32_t nch = std::min(t.s.CH, ls[q + 1] - ls[q] - piece * t.s.CH);
+        src  = surv.as<uint32_t>() + (uint64_t) seg * t.s.seg_stride() + (uint64_t) (ls[q] + piece * t.s.CH) * 32;
         need = (uint64_t) nch * 128;
     } else {
         switch (which) {
@@ -1448,9 +1412,9 @@ int Engine::tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t*
             case HWBRJ_TAB_R_SWEEP_START: src = R_.istart.p, need = (uint64_t) (F + 1) * 4; break;
             case HWBRJ_TAB_R_RUN_CNT: src = rrun.p, need = (uint64_t) sweeps * NSUB * 4; break;
             case HWBRJ_TAB_R_RUN_OFF:
-                src = rrun.as<uint32_t>() + t.sweeps_max * NSUB, need = (uint64_t) sweeps * NSUB * 4;
+                src = rrun.as<uint32_t>() + t.s.sweeps_max * NSUB, need = (uint64_t) sweeps * NSUB * 4;
                 break;
-            case HWBRJ_TAB_R_KEYS: src = rjoin.p, need = (uint64_t) sweeps * t.SLOT * 4; break;
+            case HWBRJ_TAB_R_KEYS: src = rjoin.p, need = (uint64_t) sweeps * t.s.SLOT * 4; break;
             case HWBRJ_TAB_S_LIST_START: src = S_.lstart.p, need = (uint64_t) (F + 1) * 4; break;
             case HWBRJ_TAB_S_ITEM_START: src = S_.istart.p, need = (uint64_t) (F + 1) * 4; break;
             case HWBRJ_TAB_SURV_CNT: src = survcnt.p, need = (uint64_t) items * NSUB * 4; break;
@@ -1461,14 +1425,14 @@ int Engine::tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t*
                     return 13;
                 }
                 // nparts [NJ], then the extra-part count (jparts: nparts | job_surv | nextra)
-                need = (uint64_t) (t.NJ + 1) * 4;
+                need = (uint64_t) (t.s.NJ + 1) * 4;
                 if (bytes) *bytes = need;
                 if (cap_bytes < need || !host_out) {
                     set_last_error("cap_bytes too small (*bytes holds the need)");
                     return 7;
                 }
-                HWBRJ_CHECK(hipMemcpy(host_out, jparts.p, (size_t) t.NJ * 4, hipMemcpyDeviceToHost));
-                HWBRJ_CHECK(hipMemcpy((uint32_t*) host_out + t.NJ, jparts.as<uint32_t>() + 2 * t.NJ, 4,
+                HWBRJ_CHECK(hipMemcpy(host_out, jparts.p, (size_t) t.s.NJ * 4, hipMemcpyDeviceToHost));
+                HWBRJ_CHECK(hipMemcpy((uint32_t*) host_out + t.s.NJ, jparts.as<uint32_t>() + 2 * t.s.NJ, 4,
                                       hipMemcpyDeviceToHost));
                 return 0;
             default: set_last_error("unknown table"); return 2;
@@ -1527,42 +1491,52 @@ int Engine::side_pass(const void* dR, uint64_t nR, int layout, hipStream_t strea
     return 0;
 }
 
-int Engine::materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
-                        uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout) {
-    return side_pass(dR, nR, layout, stream, "materialization table", {}, n, 1, ms,
+int Engine::side(const JoinIn& in, const JoinReq& req, uint64_t* n, JoinExtras* x, double* ms) {
+    JoinExtras own;
+    if (!x) x = &own;
+    switch (req.kind) {
+        case JOIN_PAIRS: return pairs_side(in, req, n, ms);
+        case JOIN_SEMI: return semi_side(in, req, n, ms);
+        case JOIN_OUTER: return outer_side(in, req, n, x->cls, ms);
+        case JOIN_GROUP: return group_side(in, req, n, &x->pairs, ms);
+        default: set_last_error("a counting join has no side pass"); return 2;
+    }
+}
+
+// (R.payload, S.payload) of every match into out[0, cap)
+int Engine::pairs_side(const JoinIn& in, const JoinReq& q, uint64_t* n, double* ms) {
+    return side_pass(in.dR, in.nR, q.layout, in.stream, "materialization table", {}, n, 1, ms,
                      [&](const SideTable& t, hipStream_t s) {
-                         if (nR && nS)
-                             launch_pair_probe(dS, layout, nS, dR, t, 0u, 0u, nullptr, out, cap,
+                         if (in.nR && in.nS)
+                             launch_pair_probe(in.dS, q.layout, in.nS, in.dR, t, 0u, 0u, nullptr, (uint2*) q.out, q.cap,
                                                mcount.as<unsigned long long>(), s);
                      });
 }
 
-int Engine::semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
-                      uint64_t* n, hipStream_t stream, double* ms, int layout) {
-    return side_pass(dR, nR, layout, stream, "existence table", {}, n, 1, ms,
+int Engine::semi_side(const JoinIn& in, const JoinReq& q, uint64_t* n, double* ms) {
+    return side_pass(in.dR, in.nR, q.layout, in.stream, "existence table", {}, n, 1, ms,
                      [&](const SideTable& t, hipStream_t s) {
-                         if (nS)
-                             launch_semi_probe(dS, layout, nS, t, semi.anti ? 1u : 0u, semi.out, semi.cap,
+                         if (in.nS)
+                             launch_semi_probe(in.dS, q.layout, in.nS, t, q.anti ? 1u : 0u, (uint2*) q.out, q.cap,
                                                mcount.as<unsigned long long>(), s);
                      });
 }
 
-int Engine::outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
-                       uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout) {
+int Engine::outer_side(const JoinIn& in, const JoinReq& q, uint64_t* n, uint64_t cls[3], double* ms) {
     tab_.state = kTabOther;  // (an outer join's tables are not read back, in this mode either)
-    const size_t fbytes = (size_t) std::max<uint64_t>(side_slots(nR) / 8, 4);  // one bit per table slot
+    const size_t fbytes = (size_t) std::max<uint64_t>(side_slots(in.nR) / 8, 4);  // one bit per table slot
     std::vector<SideBuf> own;
-    if (outer.keep_r) own.push_back({&smark, fbytes, 0u});
+    if (q.keep_r) own.push_back({&smark, fbytes, 0u});
     uint64_t  c[3];
     const int rc = side_pass(
-        dR, nR, layout, stream, "outer join table", own, c, 3, ms, [&](const SideTable& t, hipStream_t s) {
-            uint32_t*           rflag = outer.keep_r ? smark.as<uint32_t>() : nullptr;
+        in.dR, in.nR, q.layout, in.stream, "outer join table", own, c, 3, ms, [&](const SideTable& t, hipStream_t s) {
+            uint32_t*           rflag = q.keep_r ? smark.as<uint32_t>() : nullptr;
             unsigned long long* cnt   = mcount.as<unsigned long long>();
-            if (nS)
-                launch_pair_probe(dS, layout, nS, dR, t, outer.keep_s ? 1u : 0u, outer.null_pay, rflag, outer.out,
-                                  outer.cap, cnt, s);
-            if (outer.keep_r && nR)
-                launch_outer_rtab(dR, layout, t.tab, t.mask + 1, rflag, outer.null_pay, outer.out, outer.cap, cnt, s);
+            if (in.nS)
+                launch_pair_probe(in.dS, q.layout, in.nS, in.dR, t, q.keep_s ? 1u : 0u, q.null_pay, rflag,
+                                  (uint2*) q.out, q.cap, cnt, s);
+            if (q.keep_r && in.nR)
+                launch_outer_rtab(in.dR, q.layout, t.tab, t.mask + 1, rflag, q.null_pay, (uint2*) q.out, q.cap, cnt, s);
         });
     if (rc) return rc;
     *n     = c[0];
@@ -1572,25 +1546,24 @@ int Engine::outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
     return 0;
 }
 
-int Engine::group_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const GroupReq& group,
-                       uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms, int layout) {
-    if (layout == SRC_KEYS && nS && !group.s_val) {
+int Engine::group_side(const JoinIn& in, const JoinReq& q, uint64_t* n, uint64_t* pairs, double* ms) {
+    if (q.layout == SRC_KEYS && in.nS && !q.s_val) {
         set_last_error("key columns: a group join needs S's value column");
         return 2;
     }
     tab_.state = kTabOther;  // (a group join's tables are not read back, in this mode either)
-    const size_t rows = (size_t) std::max<uint64_t>(nR, 1);  // one count and one sum (or min and max) per R row
-    const bool   minmax = group.agg == GRP_COUNT_MINMAX;
+    const size_t rows = (size_t) std::max<uint64_t>(in.nR, 1);  // one count and one sum (or min and max) per R row
+    const bool   minmax = q.agg == GRP_COUNT_MINMAX;
     std::vector<SideBuf> own{{&gcnt, rows * 4, 0u}};
     if (minmax) own.insert(own.end(), {{&gmin, rows * 4, (uint32_t) INT32_MAX}, {&gmax, rows * 4, (uint32_t) INT32_MIN}});
     else own.push_back({&gsum, rows * 8, 0u});
     uint64_t  c[2];
-    const int rc = side_pass(dR, nR, layout, stream, "group join table", own, c, 2, ms,
+    const int rc = side_pass(in.dR, in.nR, q.layout, in.stream, "group join table", own, c, 2, ms,
                                 [&](const SideTable& t, hipStream_t s) {
         const GroupAcc a{gcnt.as<uint32_t>(), gsum.as<unsigned long long>(), gmin.as<int32_t>(), gmax.as<int32_t>()};
-        if (nR && nS) launch_group_probe(dS, group.s_val, layout, nS, t, a, group.agg, s);
-        if (nR)
-            launch_group_rows(dR, layout, nR, a, group.agg, group.all ? 1u : 0u, group.out, group.cap,
+        if (in.nR && in.nS) launch_group_probe(in.dS, q.s_val, q.layout, in.nS, t, a, q.agg, s);
+        if (in.nR)
+            launch_group_rows(in.dR, q.layout, in.nR, a, q.agg, q.all ? 1u : 0u, (uint4*) q.out, q.cap,
                               mcount.as<unsigned long long>(), s);
     });
     if (rc) return rc;

@@ -22,51 +22,86 @@ namespace hwbrj {
 bool plan_geometry(const bloom_filter_args_t* args, uint64_t nR, Geometry* g, std::string* err,
                    bool mat = false);
 
-// A materializing join's output: {R.payload, S.payload} pairs into out[0, cap).
-struct MatReq {
-    uint2*   out;
-    uint64_t cap;
-};
-constexpr int kRcMatGlobal = 11;  // run_mat / run_semi: global-bitmap mode, use the side pass
-// An existence join's output: whole S tuples {key, payload} into out[0, cap). anti: the S tuples
-// without a partner in R (else those with one).
-struct SemiReq {
-    uint2*   out;
-    uint64_t cap;
-    bool     anti;
-};
-// An outer join's output: rows {R.payload | null, S.payload | null} into out[0, cap). keep_s: the S
-// rows without a partner in R are rows too; keep_r: the R rows without a partner in S.
-struct OuterReq {
-    uint2*   out;
-    uint64_t cap;
-    bool     keep_s, keep_r;
-    uint32_t null_pay;
-};
-// A group join's output: rows {R.payload, count, sum} (hwbrj_group_row_t, 16 bytes) into
-// out[0, cap). all: every R row is a row; otherwise those with count > 0. agg (GroupAgg):
-// GRP_COUNT_MINMAX gives rows {R.payload, count, min, max} (hwbrj_group_minmax_row_t) instead.
-// s_val: with key columns (layout SRC_KEYS), S's value column, |S| uint32 beside its key column: the
-// S payloads that are aggregated (R.payload is then the R row index); tuples: not read.
-struct GroupReq {
-    uint4*      out;
-    uint64_t    cap;
-    bool        all;
-    uint32_t    agg   = GRP_COUNT_SUM;
-    const void* s_val = nullptr;
-};
+constexpr int kRcMatGlobal = 11;  // a payload join in the global-bitmap mode: use the side pass (Engine::side)
 
 // The validity bitmaps of two key columns (layout SRC_KEYS; include/hwbrj.h "validity bitmaps"): row
 // i of a column is bit i & 7 of byte i >> 3, set = valid; nullptr: that column has no NULL keys and
 // runs the kernels it runs without a KeyMasks. A NULL key joins nothing. Partition-slice modes and no
 // filter only (9 otherwise).
-// sv: the group joins on key columns only (GroupReq::s_val), the bitmap of S's value column in the
+// sv: the group joins on key columns only (JoinReq::s_val), the bitmap of S's value column in the
 // same layout: an S row takes part iff its key bit and its value bit are set, so count is COUNT(S.val)
 // and sum / min / max are over the same rows. Under GROUP_ALL a NULL R row still gets its identity row.
 struct KeyMasks {
     const uint8_t* r  = nullptr;
     const uint8_t* s  = nullptr;
     const uint8_t* sv = nullptr;
+};
+
+// One join of device-resident relations: what it produces (kind), where, and how its inputs are read.
+//  COUNT: matches only. PAIRS: {R.payload, S.payload} of every match. SEMI: whole S tuples {key,
+//  payload}, those with a partner in R or (anti) those without. OUTER: rows {R.payload | null_pay,
+//  S.payload | null_pay}; keep_s: the S rows without a partner are rows too, keep_r: the R rows.
+//  GROUP: rows {R.payload, count, sum} (hwbrj_group_row_t, 16 bytes) or, agg = GRP_COUNT_MINMAX,
+//  {R.payload, count, min, max} (hwbrj_group_minmax_row_t); all: every R row, else those with count > 0.
+// Rows go to out[0, cap) (uint2, GROUP: uint4); the counts also count the rows beyond cap.
+// Every kind but COUNT runs the payload-carrying pipeline (the materializing geometry, S payloads
+// beside the partition words); SEMI's R side is the counting join's (32-bit codes, no payloads), the
+// others carry R's payloads too and differ from the join kernel on.
+// jkind: the per-partition join of COUNT (JoinParams::jkind: 0 PRO, 1 PRH, 2 PRHO).
+// layout: what dR and dS both point to: SRC_TUPLES (uint2 {key, payload}) or SRC_KEYS (one uint32 key
+// per element, 16-byte aligned; every payload is the row index, |R|, |S| < 2^31). Only the kernels
+// that read the relations differ; the partition words and payloads, and so everything from the pools
+// on, do not depend on it. s_val: GROUP on key columns, S's value column (|S| uint32 beside its keys):
+// the payloads that are aggregated, read by the S payload scatter as SRC_KEYS_VAL.
+// masks: validity bitmaps (KeyMasks, SRC_KEYS only). A side with a bitmap runs the SRC_KEYS_MASK
+// scatter (GROUP's S side SRC_KEYS_VAL_MASK, with one bitmap or two), the other side the kernel it
+// runs without; nothing after the scatters knows: a NULL key is in no partition. The rows NULL keys
+// contribute themselves (anti, outer, GROUP all) come from k_null_rows / k_null_group_rows after the
+// kind's own emit kernels, through the same row counter.
+enum JoinKind : int { JOIN_COUNT = 0, JOIN_PAIRS, JOIN_SEMI, JOIN_OUTER, JOIN_GROUP };
+struct JoinReq {
+    JoinKind    kind = JOIN_COUNT;
+    void*       out  = nullptr;
+    uint64_t    cap  = 0;
+    bool        anti = false;                      // SEMI
+    bool        keep_s = false, keep_r = false;    // OUTER
+    uint32_t    null_pay = 0;
+    bool        all   = false;                     // GROUP
+    uint32_t    agg   = GRP_COUNT_SUM;
+    const void* s_val = nullptr;
+    int         jkind = 0, layout = SRC_TUPLES;
+    KeyMasks    masks;
+    bool carries_s_payloads() const { return kind != JOIN_COUNT; }
+    bool carries_r_payloads() const { return kind == JOIN_PAIRS || kind == JOIN_OUTER || kind == JOIN_GROUP; }
+};
+// The relations of a join, its filter (nullptr: none) and its stream (nullptr: the Engine's own)
+struct JoinIn {
+    const void*                dR;
+    uint64_t                   nR;
+    const void*                dS;
+    uint64_t                   nS;
+    const bloom_filter_args_t* args;
+    hipStream_t                stream;
+};
+// What a kind counts beside its rows: OUTER cls = {inner, S-only, R-only} rows; GROUP pairs = the sum
+// of the rows' counts
+struct JoinExtras {
+    uint64_t cls[3] = {0, 0, 0};
+    uint64_t pairs  = 0;
+};
+
+// The derived sizes of one join, computed in one place (JoinShape::make) for both enqueue paths and
+// kept for the table readback: F partitions of NSUB subs (NJ join jobs), nseg slice segments, CH
+// chunks per probe item; G scatter workgroups whose regions hold capR / capS chunks (LR / LS in all);
+// build sweeps of BSW chunks into slots of SLOT words.
+struct JoinShape {
+    uint32_t F = 0, NSUB = 0, NJ = 0, nseg = 1, CH = 0, G = 0;
+    uint64_t capR = 0, capS = 0, LR = 0, LS = 0, items_max = 0;
+    uint64_t BSW = 0, SLOT = 0, sweeps_max = 0;
+    bool     slice_mode = false;
+    uint64_t seg_stride() const { return LS * 32; }  // survivor words of one slice segment
+    static JoinShape make(uint32_t F, uint32_t NSUB, uint32_t NJ, uint32_t nseg, uint32_t G, uint64_t capR,
+                          uint64_t capS, bool slice_mode);
 };
 
 // The modes whose pass-1 scatters are the only readers of the raw relations (Engine::enqueue): a
@@ -121,17 +156,12 @@ class Engine {
   public:
     explicit Engine(int device);
     ~Engine();
-    // Synchronous join of device-resident relations. Returns 0 on success.
-    // jkind: the per-partition join (JoinParams::jkind: 0 PRO, 1 PRH, 2 PRHO).
-    // layout: what dR and dS both point to: SRC_TUPLES (uint2 {key, payload}) or SRC_KEYS (one
-    // uint32 key per element, 16-byte aligned). Only the kernels that read the relations differ.
-    int  run(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-             const bloom_filter_args_t* args, hipStream_t stream, hwbrj_stats_t* st, int jkind = 0,
-             int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
-    // Enqueue only (wait = false in run): wait() then waits for the last enqueued join.
-    int  run_async(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                   const bloom_filter_args_t* args, hipStream_t stream, int jkind = 0,
-                   int layout = SRC_TUPLES);
+    // One synchronous join (JoinReq): enqueue, wait, then the kind's extra counts (*x, or nullptr).
+    // Returns 0 on success. st->matches = matches (COUNT) or rows (all of them, also beyond cap).
+    // kRcMatGlobal: a payload join in the global-bitmap mode (run COUNT, then side()).
+    int  run(const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, JoinExtras* x = nullptr);
+    // Enqueue only, a counting join without masks: wait() then waits for the last enqueued join.
+    int  run_async(const JoinIn& in, int jkind = 0, int layout = SRC_TUPLES);
     int  wait(hwbrj_stats_t* st);
     // Every join enqueued since the last wait / wait_all, oldest first, each with its own counts
     // (they stay on the device in a ring of kJoinRing result slots, one per join; an enqueue that
@@ -152,44 +182,10 @@ class Engine {
     // hipMemcpy only: no kernel, no device write.
     int  tables_info(uint64_t* out, int n);
     int  tables_read(int which, void* host_out, uint64_t cap_bytes, uint64_t* bytes);
-    // The materializing join (the partitioned pipeline carrying payloads): st->matches = pairs
-    // (all of them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
-    // layout (here, run_semi, run_outer and their side passes): SRC_TUPLES, or SRC_KEYS: key columns
-    // as in run(), every element's payload its row index (|R|, |S| < 2^31).
-    int  run_mat(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                 const bloom_filter_args_t* args, hipStream_t stream, const MatReq& mat,
-                 hwbrj_stats_t* st, int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
-    // The existence join (semi / anti) on the materializing pipeline's geometry: S carries its
-    // payloads, R does not (k_join_semi, and k_semi_emit for anti). st->matches = rows (all of
-    // them, also beyond cap). kRcMatGlobal: not for the global-bitmap mode.
-    int  run_semi(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                  const bloom_filter_args_t* args, hipStream_t stream, const SemiReq& semi,
-                  hwbrj_stats_t* st, int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
-    // The outer join on the materializing pipeline (both payloads; k_join_outer, and k_outer_emit
-    // when S is preserved). st->matches = rows (all of them, also beyond cap); cls = {inner, S-only,
-    // R-only} rows. kRcMatGlobal: not for the global-bitmap mode.
-    int  run_outer(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                   const bloom_filter_args_t* args, hipStream_t stream, const OuterReq& outer,
-                   hwbrj_stats_t* st, uint64_t cls[3], int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
-    // The group join on the materializing pipeline up to the join, then k_join_group. st->matches =
-    // rows (all of them, also beyond cap); *pairs = the sum of their counts. kRcMatGlobal: not for the
-    // global-bitmap mode. layout SRC_KEYS: R's payload is its row index (|R| < 2^31) and S's payloads
-    // are group.s_val (GroupReq), the only payloads of S that are read. masks: SRC_KEYS only (KeyMasks,
-    // sv included).
-    int  run_group(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                   const bloom_filter_args_t* args, hipStream_t stream, const GroupReq& group,
-                   hwbrj_stats_t* st, uint64_t* pairs, int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
-    // The side passes after a counting join (global-bitmap mode; one skeleton: side_pass). *n = rows
-    // (all of them, also beyond the capacity); *pairs, cls as above; materialize: (R.payload, S.payload)
-    // of every match into out[0, cap). *ms = the side pass's device time.
-    int  group_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const GroupReq& group,
-                    uint64_t* n, uint64_t* pairs, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
-    int  outer_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const OuterReq& outer,
-                    uint64_t* n, uint64_t cls[3], hipStream_t stream, double* ms, int layout = SRC_TUPLES);
-    int  semi_side(const void* dR, uint64_t nR, const void* dS, uint64_t nS, const SemiReq& semi,
-                   uint64_t* n, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
-    int  materialize(const void* dR, uint64_t nR, const void* dS, uint64_t nS, uint2* out,
-                     uint64_t cap, uint64_t* n, hipStream_t stream, double* ms, int layout = SRC_TUPLES);
+    // The side pass of a payload join after a counting join (global-bitmap mode; one skeleton:
+    // side_pass), selected by req.kind. *n = rows (all of them, also beyond the capacity); *x as in
+    // run(); *ms = the side pass's device time.
+    int  side(const JoinIn& in, const JoinReq& req, uint64_t* n, JoinExtras* x, double* ms);
     int  generate(uint2* d_out, uint64_t n, uint64_t offset, uint64_t count, uint32_t nthreads,
                   uint64_t maxid, uint64_t threshold, double selectivity, uint64_t seed,
                   hipStream_t stream);
@@ -299,6 +295,10 @@ class Engine {
     template <class Launch>
     int side_pass(const void* dR, uint64_t nR, int layout, hipStream_t stream, const char* what,
                   const std::vector<SideBuf>& own, uint64_t* c, uint32_t nc, double* ms, Launch&& launch);
+    int pairs_side(const JoinIn& in, const JoinReq& q, uint64_t* n, double* ms);
+    int semi_side(const JoinIn& in, const JoinReq& q, uint64_t* n, double* ms);
+    int outer_side(const JoinIn& in, const JoinReq& q, uint64_t* n, uint64_t cls[3], double* ms);
+    int group_side(const JoinIn& in, const JoinReq& q, uint64_t* n, uint64_t* pairs, double* ms);
     void*        comm_       = nullptr;  // ncclComm_t of this device's rank (hwbrj_comm_init)
     int          comm_world_ = 1, comm_rank_ = 0;
     bool         bcast_      = false;
@@ -314,8 +314,6 @@ class Engine {
     Geometry     last_g_{};
     // the last enqueued join (collected by wait)
     bool         pending_      = false;
-    bool         pending_args_ = false;
-    uint64_t     pending_nS_   = 0;
     uint32_t     last_nj_      = 0;  // join jobs of the last enqueue (job_surv layout)
     // phase events: recorded by synchronous joins only (run_async clears phase_ev_); surv_fused_:
     // the pending join's survivor phase is fused into its probe (no ev_[7] of its own)
@@ -326,8 +324,6 @@ class Engine {
     // joins enqueued on it (a destroyed stream's handle can be reused by a new one).
     hipStream_t  pending_stream_ = nullptr;
     bool         pending_sfirst_ = false;  // the pending join ran its S pass first (phase boundaries)
-    bool         pending_fmt_    = false;  // the pending join counted its unstaged probe items
-    bool         pending_slots_  = false;  // the pending join's matches are in k_join's partial sums
     bool         pack3_hint_     = true;   // the last waited join had none: packed join keys pay
     int          pending_rc_     = 0;   // nonzero: the pending join failed after enqueuing kernels
     std::string  pending_err_;
@@ -351,30 +347,68 @@ class Engine {
     bool                       async_timing_ = false;      // hwbrj_set_async_timing
     hipEvent_t                 tev_[kJoinRing][2] = {};    // per slot: the async S scatter's start, end
     void*        ring_take(uint32_t* slot);            // the next slot's bytes (jring_ grown first)
-    void         ring_push(const JoinRec& r) { jr_.push_back(r); }
+    // the last taken slot. Its u64 words 6 and 7 belong to the join's kind (zeroed with the counts
+    // by the R scatter, not read by ring_collect): OUTER's {R-only, S-only} rows, GROUP's pairs in
+    // word 6; run() reads them after the join (the slot is taken again by the next enqueue only)
+    const uint64_t* last_slot_ = nullptr;
     int          ring_collect();                       // jr_ (completed) -> jdone_
+    int          wait_pending();
     void         ring_drop() { jr_.clear(); jdone_.clear(); }
     hipError_t   mark(int i, hipStream_t stream);  // ev_[i] when phase_ev_
     bool         alloc_only_   = false;  // reserve(): enqueue returns after its allocations
-    int          enqueue(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                         const bloom_filter_args_t* args, hipStream_t stream, int jkind,
-                         const MatReq* mat = nullptr, const SemiReq* semi = nullptr,
-                         const OuterReq* outer = nullptr, const GroupReq* group = nullptr,
-                         int layout = SRC_TUPLES, const KeyMasks* masks = nullptr);
-    // basic k >= 2 without materialization: the repartitioning pipeline (hwbrj_engine.cpp)
-    int          enqueue_basic_kk(const void* dR, uint64_t nR, const void* dS, uint64_t nS,
-                                  const Geometry& g, hipStream_t stream, int jkind, int layout);
+    // One enqueue's state, stage to stage (hwbrj_engine.cpp "Engine::enqueue")
+    struct JoinCtx {
+        JoinIn         in;  // (stream: never nullptr after validate)
+        const JoinReq& q;
+        Geometry       g{};
+        JoinShape      s{};
+        // the bitmap of each non-empty side, or nullptr (an empty column has no NULL rows); vV: S's
+        // value column (the group joins)
+        const uint8_t *vR = nullptr, *vS = nullptr, *vV = nullptr;
+        bool      basic_kk = false;       // basic k >= 2 on the payload pipeline: slices from bit positions
+        uint64_t  nRk      = 0;           // its k * |R| bit positions
+        bool      bcast    = false;       // the slices arrive by RCCL broadcast: a collective
+        bool      jnew     = false;       // the job table is cleared first
+        char*     sm       = nullptr;     // the ring slot, number rslot
+        uint32_t  rslot = 0, kbits = 0;   // kbits: packed join-key bits of build / probe / join
+        bool      rtimed = false, s_first = false;
+        uint64_t* result() const { return (uint64_t*) sm; }  // [0] matches / rows, [1] dense count, [2] filtered
+    };
     // what tables_info / tables_read need of the last enqueued join: which pipeline left its tables
     // in the buffers below, and the shape they are indexed with
     enum { kTabNone = 0, kTabJoin = 1, kTabOther = 2 };  // kTabOther: a pipeline with other tables
     struct TabRec {
-        int      state = kTabNone;
-        bool     sync = false, mat = false;
-        Geometry g{};
-        uint32_t G = 0, nseg = 1, CH = 0, BSW = 0, SLOT = 0, stage_cap = 0, jkind = 0, kbits = 0;
-        uint32_t bitmap = 0, split = 0, NJ = 0;
-        uint64_t sweeps_max = 0, seg_stride = 0;
+        int       state = kTabNone;
+        bool      sync = false, mat = false;
+        Geometry  g{};
+        JoinShape s{};
+        uint32_t  stage_cap = 0, jkind = 0, kbits = 0, bitmap = 0, split = 0;
     };
+    // the stages of enqueue, in order (hwbrj_engine.cpp)
+    int          validate(JoinCtx* c);
+    void         plan(JoinCtx* c);
+    bool         ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew);
+    bool         ensure_buffers(JoinCtx* c);
+    int          s_pass(const JoinCtx& c, hipStream_t st, bool marks, hipEvent_t* tev);
+    int          r_side(const JoinCtx& c);
+    int          passes(JoinCtx* c);
+    int          probe(const JoinCtx& c, ProbeParams* pp);
+    int          join_count(const JoinCtx& c, const JoinParams& jp);
+    int          join_pairs(const JoinCtx& c, const JobInputs& ji);
+    int          join_semi(const JoinCtx& c, const JobInputs& ji);
+    int          join_outer(const JoinCtx& c, const JobInputs& ji);
+    int          join_group(const JoinCtx& c, const JobInputs& ji);
+    int          clear_job_surv(const JoinCtx& c);
+    MatJoinParams mat_params(const JoinCtx& c, const JobInputs& ji) const;
+    int          finish(const JoinIn& in, const Geometry& g, bool s_first, const TabRec& tab, JoinRec rec);
+    // the parameter blocks both enqueue paths share; each path overrides what differs
+    ScatterParams scatter_params(const Geometry& g, const PartSide& side, uint64_t cap) const;
+    BuildParams  build_params(const Geometry& g, const JoinShape& s) const;
+    ProbeParams  probe_params(const Geometry& g, const JoinShape& s) const;
+    JoinParams   join_params(const Geometry& g, const JoinShape& s, char* slot, int jkind) const;
+    int          enqueue(const JoinIn& in, const JoinReq& req);
+    // basic k >= 2 without payloads: the repartitioning pipeline (hwbrj_engine.cpp)
+    int          enqueue_basic_kk(const JoinIn& in, const Geometry& g, const JoinReq& req);
     TabRec       tab_;
     int          tables_ready();  // 0, or why the tables cannot be read (the codes of hwbrj.h)
     CrcTables*   d_tabs_ = nullptr;
@@ -388,8 +422,6 @@ class Engine {
     DevBuf ppoolR, ppoolS, rpay, survpos;
     DevBuf smark;  // existence / outer join: one bit per S chunk position (matched survivors); the
                    // outer side pass: one bit per slot of its table of R (outer_side)
-    const uint64_t* outer_cls_ = nullptr;  // the last outer join's {R-only, S-only} counters (its ring slot)
-    const uint64_t* group_pairs_ = nullptr;  // the last group join's pair counter (its ring slot)
     DevBuf gcnt, gsum;  // the group join's side pass: count and sum per R row (group_side)
     DevBuf gmin, gmax;  // its min/max form: min and max per R row
     DevBuf dense2, kkcnt;  // basic k >= 2: the second dense candidate buffer, per-pass counts
