@@ -22,6 +22,9 @@ __all__ = [
     "pack_validity", "generate_host", "nonunique_threshold", "create_relation_nonunique",
     "create_relation_nonunique_from_pk", "create_relation_fk_from_pk", "create_relation_zipf",
     "rand_stream", "reference_relations", "create_relation_zipf_device",
+    "Build", "build_keys_device", "BUILD_COUNT", "BUILD_ROWS", "PROBE_MARK_INNER", "PROBE_MARK_S",
+    "probe_keys_device", "probe_keys_pairs_device", "semi_probe_keys_device", "outer_probe_keys_device",
+    "group_probe_keys_device", "group_minmax_probe_keys_device",
     "export_filter", "tables_info", "tables_read", "hash_crc", "hash_crapwow", "lib", "LIB_PATH", "shard_range", "write_relation",
 ]
 
@@ -173,6 +176,27 @@ def lib() -> ctypes.CDLL:
         for nm in ("hwbrj_join_keys_group_nulls_device", "hwbrj_join_keys_group_minmax_nulls_device"):
             getattr(L, nm).restype = ctypes.c_int
             getattr(L, nm).argtypes = [g[0], ctypes.c_void_p, g[1], g[2], ctypes.c_void_p, g[3], ctypes.c_void_p] + list(g[4:])
+        # prepared builds: the build's handle first, then the counterpart's S-side arguments
+        vp, u64, pu64 = ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
+        pst, pdb = ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)
+        for nm, at in (
+                ("hwbrj_build_keys_device", [vp, vp, u64, ctypes.POINTER(_BloomArgs), ctypes.c_int, vp,
+                                             ctypes.POINTER(vp), pdb]),
+                ("hwbrj_build_free", [vp]),
+                ("hwbrj_build_info", [vp, pu64, ctypes.c_int]),
+                ("hwbrj_build_export_filter", [vp, vp, u64]),
+                ("hwbrj_build_unmatched_device", [vp, vp, u64, pu64, vp, pdb]),
+                ("hwbrj_build_reset_marks", [vp]),
+                ("hwbrj_probe_keys_device", [vp, vp, vp, u64, ctypes.c_int, vp, pst]),
+                ("hwbrj_probe_keys_pairs_device", [vp, vp, vp, u64, vp, u64, pu64, vp, pst, pdb]),
+                ("hwbrj_probe_keys_semi_device", [vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, vp, pst, pdb]),
+                ("hwbrj_probe_keys_outer_device", [vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64, vp, pst, pdb]),
+                ("hwbrj_probe_keys_group_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64, vp,
+                                                   pst, pdb]),
+                ("hwbrj_probe_keys_group_minmax_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64,
+                                                          vp, pst, pdb])):
+            getattr(L, nm).restype = ctypes.c_int
+            getattr(L, nm).argtypes = at
         L.hwbrj_set_materialize.restype = None
         L.hwbrj_set_materialize.argtypes = [ctypes.c_int]
         L.hwbrj_set_gpus.restype = ctypes.c_int
@@ -1097,6 +1121,232 @@ def group_minmax_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = 
     import torch
     stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_minmax_device", True, Rk, Sk, Sv, args, kind, stream,
                                         capacity, r_valid, s_valid, sv_valid)
+    rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
+    return stats, rows, pairs, ms
+
+
+# ---- prepared builds (include/hwbrj.h "Prepared builds"): build R once, probe it with S batches ----
+BUILD_COUNT, BUILD_ROWS = 0, 1          # include/hwbrj.h HWBRJ_BUILD_COUNT / _ROWS
+PROBE_MARK_INNER, PROBE_MARK_S = 3, 4   # HWBRJ_PROBE_MARK_INNER / _S (outer_probe_keys_device)
+_BI_NAMES = ("nR", "purpose", "mode", "F", "NSUB", "join_key_bits", "device", "bytes", "masked")
+
+
+class Build:
+    """A prepared build (hwbrj_build_t): the R side of the joins on key columns, made once by
+    build_keys_device and probed by the *_probe_keys_device functions. Owns its device buffers and
+    keeps no reference to the column it was made from. A context manager; freed by free(), on exit
+    and on garbage collection."""
+
+    def __init__(self, handle: int, device, ms: float = 0.0):
+        self._h = handle
+        self.device = device
+        self.ms = ms  # the build's device time
+
+    def _handle(self) -> int:
+        if not self._h:
+            raise ValueError("the build has been freed")
+        _err(lib().hwbrj_set_device(self.device.index or 0), "hwbrj_set_device")
+        return self._h
+
+    def free(self) -> None:
+        if self._h:
+            h, self._h = self._h, 0
+            _err(lib().hwbrj_set_device(self.device.index or 0), "hwbrj_set_device")
+            _err(lib().hwbrj_build_free(h), "hwbrj_build_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # (interpreter shutdown: the library may be gone)
+            pass
+
+    def info(self) -> dict:
+        """hwbrj_build_info: nR, purpose, mode, F, NSUB, join_key_bits, device, bytes (the device
+        memory the build holds), masked (R had a validity bitmap)."""
+        out = (ctypes.c_uint64 * len(_BI_NAMES))()
+        _err(lib().hwbrj_build_info(self._handle(), out, len(_BI_NAMES)), "hwbrj_build_info")
+        return {n: int(out[i]) for i, n in enumerate(_BI_NAMES)}
+
+    def export_filter(self, m_bits: int) -> np.ndarray:
+        """The build's filter in the reference layout (hwbrj_build_export_filter), as export_filter
+        returns the one-shot join's."""
+        out = np.zeros(m_bits // 8, dtype=np.uint8)
+        _err(lib().hwbrj_build_export_filter(self._handle(), out.ctypes.data, out.nbytes), "hwbrj_build_export_filter")
+        return out
+
+    def unmatched_rows(self, capacity: Optional[int] = None, stream=None):
+        """(rows, ms): {R row, -1} of every R row no marking probe (PROBE_MARK_INNER / PROBE_MARK_S)
+        has matched since the build or the last reset_marks(), NULL R rows included, unordered
+        (hwbrj_build_unmatched_device). capacity None: one count-only call first."""
+        h = self._handle()
+        sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+        n, ms = ctypes.c_uint64(), ctypes.c_double()
+
+        def call(out, cap):
+            return lib().hwbrj_build_unmatched_device(h, out, cap, ctypes.byref(n), sp, ctypes.byref(ms))
+
+        if capacity is None:
+            rc = call(None, 0)
+            if rc not in (0, 7):
+                _err(rc, "hwbrj_build_unmatched_device")
+            capacity = n.value
+        return _rows_out(call, "hwbrj_build_unmatched_device", capacity, n, self.device), ms.value
+
+    def reset_marks(self) -> None:
+        _err(lib().hwbrj_build_reset_marks(self._handle()), "hwbrj_build_reset_marks")
+
+
+def build_keys_device(Rk, args: Optional[BloomFilterArgs] = None, purpose: int = BUILD_ROWS, r_valid=None,
+                      stream=None) -> Build:
+    """The R side of the joins on key columns, run once (hwbrj_build_keys_device): Rk and r_valid are
+    join_keys_device's. purpose BUILD_COUNT serves probe_keys_device, BUILD_ROWS the probes that
+    return rows. Partition-slice filters and no filter only. Synchronous; Rk and r_valid are not
+    read again afterwards and the Build keeps no reference to them."""
+    import torch
+    vr = _check_valid("r_valid", r_valid, Rk)
+    _check_keys(Rk, torch.empty(0, dtype=torch.int32, device=Rk.device) if isinstance(Rk, torch.Tensor) else Rk, stream)
+    a = args._c() if args is not None else None
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    h, ms = ctypes.c_void_p(), ctypes.c_double()
+    rc = lib().hwbrj_build_keys_device(_ptr(Rk), _vptr(vr), Rk.shape[0], ctypes.byref(a) if a is not None else None,
+                                       int(purpose), sp, ctypes.byref(h), ctypes.byref(ms))
+    _err(rc, "hwbrj_build_keys_device")
+    return Build(h.value, Rk.device, ms.value)
+
+
+def _check_probe(build, Sk, stream, Sv=None):
+    """A probe's arguments: a live Build and S's columns on its device (_check_keys' rules)."""
+    import torch
+    if not isinstance(build, Build):
+        raise ValueError("build must be a Build (build_keys_device)")
+    h = build._handle()
+    if isinstance(Sk, torch.Tensor) and Sk.device != build.device:
+        raise ValueError(f"Sk is on {Sk.device} but the build is on {build.device}")
+    _check_keys(Sk, Sk, stream, Sv)
+    return h
+
+
+def _stats(st) -> Stats:
+    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+
+
+def probe_keys_device(build: Build, Sk, stream=None, algorithm: int = ALGO_PRO, *, s_valid=None) -> Stats:
+    """join_keys_device of the build's R and this S batch (hwbrj_probe_keys_device; a BUILD_COUNT
+    build): the same Stats, the R phases 0."""
+    vs = _check_valid("s_valid", s_valid, Sk)
+    h = _check_probe(build, Sk, stream)
+    st = _Stats()
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    _err(lib().hwbrj_probe_keys_device(h, _ptr(Sk), _vptr(vs), Sk.shape[0], int(algorithm), sp, ctypes.byref(st)),
+         "hwbrj_probe_keys_device")
+    return _stats(st)
+
+
+def _probe_rows(entry: str, build, Sk, s_valid, stream, capacity, kind=None, n_class=None, count_first=True):
+    """(Stats, rows, ms) of a probe that returns (n, 2) rows, with the one-shot wrappers' capacity
+    behaviour (None: one count-only call first; too small: run again at the exact size)."""
+    vs = _check_valid("s_valid", s_valid, Sk)
+    h = _check_probe(build, Sk, stream)
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n, st, ms = ctypes.c_uint64(), _Stats(), ctypes.c_double()
+    fn = getattr(lib(), entry)
+
+    def call(out, cap):
+        a = [h, _ptr(Sk), _vptr(vs), Sk.shape[0]] + ([int(kind)] if kind is not None else []) + [out, cap, ctypes.byref(n)]
+        return fn(*(a + ([n_class] if n_class is not None else []) + [sp, ctypes.byref(st), ctypes.byref(ms)]))
+
+    if capacity is None:
+        rc = call(None, 0)  # count only
+        if rc not in (0, 7):
+            _err(rc, entry)
+        capacity = n.value
+    out = _rows_out(call, entry, capacity, n, build.device)
+    return _stats(st), out, ms.value
+
+
+def probe_keys_pairs_device(build: Build, Sk, stream=None, capacity: Optional[int] = None, *, s_valid=None):
+    """(Stats, pairs, ms): join_keys_pairs_device of the build's R and this S batch
+    (hwbrj_probe_keys_pairs_device; a BUILD_ROWS build). S rows are positions in this batch."""
+    return _probe_rows("hwbrj_probe_keys_pairs_device", build, Sk, s_valid, stream, capacity)
+
+
+def semi_probe_keys_device(build: Build, Sk, anti: bool = False, stream=None, capacity: Optional[int] = None, *,
+                           s_valid=None):
+    """(Stats, rows, ms): semi_join_keys_device of the build's R and this S batch
+    (hwbrj_probe_keys_semi_device; a BUILD_ROWS build)."""
+    return _probe_rows("hwbrj_probe_keys_semi_device", build, Sk, s_valid, stream, capacity,
+                       kind=JOIN_ANTI if anti else JOIN_SEMI)
+
+
+def outer_probe_keys_device(build: Build, Sk, kind: int = OUTER_S, stream=None, capacity: Optional[int] = None, *,
+                            s_valid=None):
+    """(Stats, rows, (n_inner, n_s_only, n_r_only), ms): outer_join_keys_device of the build's R and
+    this S batch (hwbrj_probe_keys_outer_device; a BUILD_ROWS build). kind also takes
+    PROBE_MARK_INNER (the batch's inner pairs) and PROBE_MARK_S (plus its S-only rows): both mark the
+    R rows matched, for Build.unmatched_rows() after the last batch, and write no R-only row."""
+    cls = (ctypes.c_uint64 * 3)()
+    stats, out, ms = _probe_rows("hwbrj_probe_keys_outer_device", build, Sk, s_valid, stream, capacity, kind=kind,
+                                 n_class=cls)
+    return stats, out, (int(cls[0]), int(cls[1]), int(cls[2])), ms
+
+
+def _group_probe(entry: str, minmax: bool, build, Sk, Sv, kind, stream, capacity, s_valid, sv_valid):
+    """_group_keys for a probe: (Stats, raw rows, n_pairs, ms)."""
+    import torch
+    vs, vv = _check_valid("s_valid", s_valid, Sk), _check_valid("sv_valid", sv_valid, Sk)
+    h = _check_probe(build, Sk, stream, Sv)
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n, pairs, st, ms = ctypes.c_uint64(), ctypes.c_uint64(), _Stats(), ctypes.c_double()
+    fn = getattr(lib(), entry)
+
+    def call(out, cap):
+        return fn(h, _ptr(Sk), _vptr(vs), _ptr(Sv), _vptr(vv), Sk.shape[0], int(kind), out, cap, ctypes.byref(n),
+                  ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
+
+    if capacity is None:
+        if int(kind) == GROUP_ALL:
+            capacity = build.info()["nR"]
+        else:
+            rc = call(None, 0)  # count only
+            if rc not in (0, 7):
+                _err(rc, entry)
+            capacity = n.value
+    for _ in range(2):
+        out = (torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=build.device) if minmax else
+               torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=build.device))
+        rc = call(_ptr(out), int(capacity))
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, entry)
+    return _stats(st), out[: n.value], int(pairs.value), ms.value
+
+
+def group_probe_keys_device(build: Build, Sk, Sv, kind: int = GROUP_MATCHED, stream=None,
+                            capacity: Optional[int] = None, *, s_valid=None, sv_valid=None):
+    """(Stats, GroupRows, n_pairs, ms): group_join_keys_device of the build's R and this S batch
+    (hwbrj_probe_keys_group_device; a BUILD_ROWS build). The rows are this batch's partial
+    aggregates: the caller combines the batches' rows per R row."""
+    import torch
+    stats, raw, pairs, ms = _group_probe("hwbrj_probe_keys_group_device", False, build, Sk, Sv, kind, stream, capacity,
+                                         s_valid, sv_valid)
+    rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
+    return stats, rows, pairs, ms
+
+
+def group_minmax_probe_keys_device(build: Build, Sk, Sv, kind: int = GROUP_MATCHED, stream=None,
+                                   capacity: Optional[int] = None, *, s_valid=None, sv_valid=None):
+    """(Stats, GroupMinMaxRows, n_pairs, ms): group_minmax_join_keys_device of the build's R and this
+    S batch (hwbrj_probe_keys_group_minmax_device; a BUILD_ROWS build)."""
+    import torch
+    stats, raw, pairs, ms = _group_probe("hwbrj_probe_keys_group_minmax_device", True, build, Sk, Sv, kind, stream,
+                                         capacity, s_valid, sv_valid)
     rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
     return stats, rows, pairs, ms
 

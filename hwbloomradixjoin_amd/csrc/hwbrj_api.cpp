@@ -24,6 +24,9 @@ void set_last_error(const std::string& s) { g_last_error = s; }
 
 using namespace hwbrj;
 
+// include/hwbrj.h's opaque build: Engine's Build behind a tag that tells a build from any other pointer
+struct hwbrj_build_t : hwbrj::Build {};
+
 extern "C" {
 
 const char* hwbrj_last_error(void) { return g_last_error.c_str(); }
@@ -270,9 +273,10 @@ int hwbrj_join_wait_all(hwbrj_stats_t* stats, int capacity, int* n_joins) {
 // Pairs in the global-bitmap mode: the side pass writes the first cap pairs whatever the count
 // (k_pair_probe's row stage holds every store to out[0, cap)); only the count-only form, cap = 0,
 // stays a count.
+// b: a probe of a prepared build (always the partitioned pipeline: a build has no global-bitmap mode).
 static int pipeline_or_side_pass(Engine* e, const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, uint64_t* n,
-                                 JoinExtras* x, double* ms) {
-    int rc = e->run(in, req, st, x);
+                                 JoinExtras* x, double* ms, const Build* b = nullptr) {
+    int rc = e->run(in, req, st, x, b);
     if (rc == 0) {
         *n = (uint64_t) st->matches;
         if (ms) *ms = st->ms_total;
@@ -301,14 +305,23 @@ static int pipeline_or_side_pass(Engine* e, const JoinIn& in, const JoinReq& req
 // The shared tail of the payload joins' entries, after their argument checks: the join, the kind's
 // extra counts (n_class: the outer join's three; n_pairs: the group join's), then the caller's outputs
 // and the capacity rule (what: "match" or "row"). *ms = the device time of the rows' production.
+// The build of a probe belongs to the current device (after the entry's argument checks)
+static int build_device_ok(const Build* b, Engine* e) {
+    if (!b || b->device == e->device()) return 0;
+    set_last_error("the build belongs to another device than the current one");
+    return 2;
+}
+
 static int payload_join(const JoinIn& in, const JoinReq& req, const char* what, uint64_t* n_out, hwbrj_stats_t* stats,
-                        double* ms, uint64_t* n_class = nullptr, uint64_t* n_pairs = nullptr) {
+                        double* ms, uint64_t* n_class = nullptr, uint64_t* n_pairs = nullptr,
+                        const Build* b = nullptr) {
     Engine* e = engine_for_current_device();
     if (!e) return 10;  // (last error set by engine_for_current_device)
+    if (const int rc = build_device_ok(b, e)) return rc;
     hwbrj_stats_t st;
     uint64_t      n = 0;
     JoinExtras    x;
-    if (const int rc = pipeline_or_side_pass(e, in, req, &st, &n, &x, ms)) return rc;
+    if (const int rc = pipeline_or_side_pass(e, in, req, &st, &n, &x, ms, b)) return rc;
     if (n_class)
         for (int i = 0; i < 3; i++) n_class[i] = x.cls[i];
     if (n_pairs) *n_pairs = x.pairs;
@@ -335,9 +348,10 @@ static JoinReq payload_req(JoinKind kind, void* d_out, uint64_t capacity, int la
 static int join_pairs(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, tuple_t* d_out, uint64_t capacity, uint64_t* n_out,
                       void* stream, hwbrj_stats_t* stats, double* ms_materialize, int layout,
-                      const KeyMasks& masks = KeyMasks{}) {
+                      const KeyMasks& masks = KeyMasks{}, const Build* b = nullptr) {
     return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream},
-                        payload_req(JOIN_PAIRS, d_out, capacity, layout, masks), "match", n_out, stats, ms_materialize);
+                        payload_req(JOIN_PAIRS, d_out, capacity, layout, masks), "match", n_out, stats, ms_materialize,
+                        nullptr, nullptr, b);
 }
 
 int hwbrj_join_materialize_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -376,7 +390,7 @@ int hwbrj_join_keys_pairs_device(const int32_t* d_Rkeys, uint64_t nR, const int3
 static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                      const bloom_filter_args_t* args, int kind, tuple_t* d_out, uint64_t capacity,
                      uint64_t* n_out, void* stream, hwbrj_stats_t* stats, double* ms, int layout,
-                     const KeyMasks& masks = KeyMasks{}) {
+                     const KeyMasks& masks = KeyMasks{}, const Build* b = nullptr) {
     if (kind != HWBRJ_JOIN_SEMI && kind != HWBRJ_JOIN_ANTI) {  // (before any device call)
         set_last_error("unknown existence join kind (HWBRJ_JOIN_SEMI, HWBRJ_JOIN_ANTI)");
         return 2;
@@ -387,7 +401,8 @@ static int join_semi(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
     }
     JoinReq req = payload_req(JOIN_SEMI, d_out, capacity, layout, masks);
     req.anti    = kind == HWBRJ_JOIN_ANTI;
-    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms);
+    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms, nullptr,
+                        nullptr, b);
 }
 
 int hwbrj_join_semi_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -409,9 +424,13 @@ int hwbrj_join_keys_semi_device(const int32_t* d_Rkeys, uint64_t nR, const int32
 static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, int32_t null_payload, tuple_t* d_out,
                       uint64_t capacity, uint64_t* n_out, uint64_t* n_class, void* stream,
-                      hwbrj_stats_t* stats, double* ms, int layout, const KeyMasks& masks = KeyMasks{}) {
-    if (kind != HWBRJ_OUTER_S && kind != HWBRJ_OUTER_R && kind != HWBRJ_OUTER_FULL) {  // (before any device call)
-        set_last_error("unknown outer join kind (HWBRJ_OUTER_S, HWBRJ_OUTER_R, HWBRJ_OUTER_FULL)");
+                      hwbrj_stats_t* stats, double* ms, int layout, const KeyMasks& masks = KeyMasks{},
+                      Build* b = nullptr) {
+    // (the marking kinds belong to the probes of a prepared build: its marks outlive the call)
+    const bool marking = b && (kind == HWBRJ_PROBE_MARK_INNER || kind == HWBRJ_PROBE_MARK_S);
+    if (kind != HWBRJ_OUTER_S && kind != HWBRJ_OUTER_R && kind != HWBRJ_OUTER_FULL && !marking) {  // (before any device call)
+        set_last_error(b ? "unknown outer probe kind (HWBRJ_OUTER_S, _R, _FULL, HWBRJ_PROBE_MARK_INNER, _S)"
+                         : "unknown outer join kind (HWBRJ_OUTER_S, HWBRJ_OUTER_R, HWBRJ_OUTER_FULL)");
         return 2;
     }
     if (capacity > 0 && !d_out) {
@@ -419,10 +438,12 @@ static int join_outer(const void* d_R, uint64_t nR, const void* d_S, uint64_t nS
         return 2;
     }
     JoinReq req  = payload_req(JOIN_OUTER, d_out, capacity, layout, masks);
-    req.keep_s   = kind != HWBRJ_OUTER_R;
-    req.keep_r   = kind != HWBRJ_OUTER_S;
+    req.keep_s   = marking ? kind == HWBRJ_PROBE_MARK_S : kind != HWBRJ_OUTER_R;
+    req.keep_r   = !marking && kind != HWBRJ_OUTER_S;
+    req.rmark    = marking ? b->marks.as<uint32_t>() : nullptr;
     req.null_pay = (uint32_t) null_payload;
-    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms, n_class);
+    return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms, n_class,
+                        nullptr, b);
 }
 
 int hwbrj_join_outer_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -527,7 +548,7 @@ int hwbrj_join_keys_outer_nulls_device(const int32_t* d_Rkeys, const uint8_t* d_
 static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void* d_Svals, uint64_t nS,
                       const bloom_filter_args_t* args, int kind, uint32_t agg, void* d_out, uint64_t capacity,
                       uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms,
-                      int layout, const KeyMasks& masks = KeyMasks{}) {
+                      int layout, const KeyMasks& masks = KeyMasks{}, const Build* b = nullptr) {
     static_assert(sizeof(hwbrj_group_row_t) == 16 && sizeof(hwbrj_group_minmax_row_t) == 16,
                   "a row is one 16-byte store");
     if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {  // (before any device call)
@@ -551,7 +572,7 @@ static int join_group(const void* d_R, uint64_t nR, const void* d_S, const void*
     req.agg     = agg;
     req.s_val   = d_Svals;
     return payload_join(JoinIn{d_R, nR, d_S, nS, args, (hipStream_t) stream}, req, "row", n_out, stats, ms, nullptr,
-                        n_pairs);
+                        n_pairs, b);
 }
 
 int hwbrj_join_group_device(const tuple_t* d_R, uint64_t nR, const tuple_t* d_S, uint64_t nS,
@@ -642,6 +663,228 @@ int hwbrj_join_keys_group_minmax_nulls_device(const int32_t* d_Rkeys, const uint
                                               uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms) {
     return join_keys_group_nulls(d_Rkeys, d_Rvalid, nR, d_Skeys, d_Svalid, d_Svals, d_Svals_valid, nS, args, kind,
                                  GRP_COUNT_MINMAX, d_out, capacity, n_out, n_pairs, stream, stats, ms);
+}
+
+// ---- prepared builds (include/hwbrj.h "Prepared builds") ----
+int hwbrj_build_keys_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uint64_t nR,
+                            const bloom_filter_args_t* args, int purpose, void* stream, hwbrj_build_t** build,
+                            double* ms) {
+    // (all of these before any device call; *build is written on success only)
+    if (purpose != HWBRJ_BUILD_COUNT && purpose != HWBRJ_BUILD_ROWS) {
+        set_last_error("unknown build purpose (HWBRJ_BUILD_COUNT, HWBRJ_BUILD_ROWS)");
+        return 2;
+    }
+    if (!build) {
+        set_last_error("build must point to where the build's handle goes");
+        return 2;
+    }
+    const bool rows = purpose == HWBRJ_BUILD_ROWS;
+    if (!keys_aligned(d_Rkeys, nR, nullptr, 0)) return 2;
+    if (d_Rvalid && nR && ((uintptr_t) d_Rvalid & 3u)) {
+        set_last_error("validity bitmap of R is not 4-byte aligned (shard a masked column at multiples of 32 rows)");
+        return 2;
+    }
+    if (rows && nR >= (1ull << 31)) {
+        set_last_error("key column R has 2^31 rows or more (row indices are int32)");
+        return 3;
+    }
+    Geometry    g;
+    std::string err;
+    if (!plan_geometry(args, nR, &g, &err, rows)) {
+        set_last_error(err);
+        return 2;
+    }
+    if (!masks_supported(g)) {
+        set_last_error("a prepared build needs partition slices (blocked/sectorized, basic k = 1, or no filter)");
+        return kRcMaskFilter;
+    }
+    Engine* e = engine_for_current_device();
+    if (!e) return 10;
+    hwbrj_build_t* b = new hwbrj_build_t();
+    b->rows          = rows;
+    const int rc     = e->build(d_Rkeys, d_Rvalid, nR, args, (hipStream_t) stream, b, ms);
+    if (rc) {
+        b->r.release();
+        b->marks.release();
+        b->cnt.release();
+        delete b;
+        return rc;
+    }
+    *build = b;
+    return 0;
+}
+
+// The current device's Engine when it is the build's, else why not
+static Engine* build_engine(const Build* b, int* rc) {
+    Engine* e = engine_for_current_device();
+    *rc       = !e ? 10 : build_device_ok(b, e);
+    return *rc ? nullptr : e;
+}
+
+int hwbrj_build_free(hwbrj_build_t* b) {
+    if (!b) return 0;
+    int rc = 0;
+    if (!build_engine(b, &rc)) return rc;
+    b->r.release();
+    b->marks.release();
+    b->cnt.release();
+    delete b;
+    return 0;
+}
+
+int hwbrj_build_info(const hwbrj_build_t* b, uint64_t* out, int n) {
+    if (!b) {
+        set_last_error("build is NULL");
+        return 2;
+    }
+    if (!out || n < HWBRJ_BI_COUNT) {
+        set_last_error("out must hold HWBRJ_BI_COUNT words");
+        return 7;
+    }
+    for (int i = 0; i < n; i++) out[i] = 0;
+    out[HWBRJ_BI_NR]       = b->r.nR;
+    out[HWBRJ_BI_PURPOSE]  = b->rows ? HWBRJ_BUILD_ROWS : HWBRJ_BUILD_COUNT;
+    out[HWBRJ_BI_MODE]     = (uint64_t) b->r.g.mode;
+    out[HWBRJ_BI_F]        = b->r.s.F;
+    out[HWBRJ_BI_NSUB]     = b->r.s.NSUB;
+    out[HWBRJ_BI_KEY_BITS] = b->r.kbits ? b->r.kbits : 32u;
+    out[HWBRJ_BI_DEVICE]   = (uint64_t) b->device;
+    out[HWBRJ_BI_BYTES]    = b->bytes();
+    out[HWBRJ_BI_MASKED]   = b->r.r_masked ? 1u : 0u;
+    return 0;
+}
+
+int hwbrj_build_export_filter(const hwbrj_build_t* b, uint8_t* host_out, uint64_t nbytes) {
+    if (!b) {
+        set_last_error("build is NULL");
+        return 2;
+    }
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    return e ? e->export_build_filter(*b, host_out, nbytes) : rc;
+}
+
+// What every probe checks first, before any device call: the build and its purpose
+static int probe_build_ok(const hwbrj_build_t* b, bool rows) {
+    if (!b) {
+        set_last_error("build is NULL");
+        return 2;
+    }
+    if (b->rows != rows) {
+        set_last_error(rows ? "this probe needs a HWBRJ_BUILD_ROWS build" : "the counting probe needs a HWBRJ_BUILD_COUNT build");
+        return 2;
+    }
+    return 0;
+}
+// the build's filter, and the bitmaps of a probe: R's is the build's own copy
+static const bloom_filter_args_t* build_args(const Build* b) { return b->has_args ? &b->args : nullptr; }
+static KeyMasks probe_masks(const Build* b, const uint8_t* d_Svalid, const uint8_t* d_Svv = nullptr) {
+    return KeyMasks{b->r.rvalid.as<uint8_t>(), d_Svalid, d_Svv};
+}
+
+int hwbrj_probe_keys_device(const hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                            int algorithm, void* stream, hwbrj_stats_t* stats) {
+    if (const int rc = probe_build_ok(b, false)) return rc;
+    if (!keys_aligned(nullptr, 0, d_Skeys, nS)) return 2;
+    if (const int rc = masks_ok(nullptr, b->r.nR, d_Svalid, nS, build_args(b), false)) return rc;
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    if (!e) return rc;
+    // (a counting build keeps no copy of R's bitmap: nothing after the R scatter reads it)
+    return e->run(JoinIn{nullptr, b->r.nR, d_Skeys, nS, build_args(b), (hipStream_t) stream},
+                  count_req(algorithm, SRC_KEYS, KeyMasks{nullptr, d_Svalid}), stats, nullptr, b);
+}
+
+int hwbrj_probe_keys_pairs_device(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                  tuple_t* d_out, uint64_t capacity, uint64_t* n_out, void* stream,
+                                  hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = keys_rows_ok(nullptr, b->r.nR, d_Skeys, nS)) return rc;
+    if (const int rc = masks_ok(nullptr, b->r.nR, d_Svalid, nS, build_args(b), true)) return rc;
+    if (capacity > 0 && !d_out) {
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    return join_pairs(nullptr, b->r.nR, d_Skeys, nS, build_args(b), d_out, capacity, n_out, stream, stats, ms, SRC_KEYS,
+                      probe_masks(b, d_Svalid), b);
+}
+
+int hwbrj_probe_keys_semi_device(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                 int kind, tuple_t* d_out, uint64_t capacity, uint64_t* n_out, void* stream,
+                                 hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = keys_rows_ok(nullptr, b->r.nR, d_Skeys, nS)) return rc;
+    if (const int rc = masks_ok(nullptr, b->r.nR, d_Svalid, nS, build_args(b), true)) return rc;
+    return join_semi(nullptr, b->r.nR, d_Skeys, nS, build_args(b), kind, d_out, capacity, n_out, stream, stats, ms,
+                     SRC_KEYS, probe_masks(b, d_Svalid), b);
+}
+
+int hwbrj_probe_keys_outer_device(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                  int kind, tuple_t* d_out, uint64_t capacity, uint64_t* n_out, uint64_t* n_class,
+                                  void* stream, hwbrj_stats_t* stats, double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = keys_rows_ok(nullptr, b->r.nR, d_Skeys, nS)) return rc;
+    if (const int rc = masks_ok(nullptr, b->r.nR, d_Svalid, nS, build_args(b), true)) return rc;
+    return join_outer(nullptr, b->r.nR, d_Skeys, nS, build_args(b), kind, -1, d_out, capacity, n_out, n_class, stream,
+                      stats, ms, SRC_KEYS, probe_masks(b, d_Svalid), b);
+}
+
+static int probe_keys_group(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid, const int32_t* d_Svals,
+                            const uint8_t* d_Svals_valid, uint64_t nS, int kind, uint32_t agg, void* d_out,
+                            uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats,
+                            double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = keys_group_ok(nullptr, b->r.nR, d_Skeys, d_Svals, nS)) return rc;
+    if (const int rc = masks_ok(nullptr, b->r.nR, d_Svalid, nS, build_args(b), true, d_Svals_valid)) return rc;
+    return join_group(nullptr, b->r.nR, d_Skeys, d_Svals, nS, build_args(b), kind, agg, d_out, capacity, n_out, n_pairs,
+                      stream, stats, ms, SRC_KEYS, probe_masks(b, d_Svalid, d_Svals_valid), b);
+}
+
+int hwbrj_probe_keys_group_device(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid,
+                                  const int32_t* d_Svals, const uint8_t* d_Svals_valid, uint64_t nS, int kind,
+                                  hwbrj_group_row_t* d_out, uint64_t capacity, uint64_t* n_out, uint64_t* n_pairs,
+                                  void* stream, hwbrj_stats_t* stats, double* ms) {
+    return probe_keys_group(b, d_Skeys, d_Svalid, d_Svals, d_Svals_valid, nS, kind, GRP_COUNT_SUM, d_out, capacity, n_out,
+                            n_pairs, stream, stats, ms);
+}
+
+int hwbrj_probe_keys_group_minmax_device(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid,
+                                         const int32_t* d_Svals, const uint8_t* d_Svals_valid, uint64_t nS, int kind,
+                                         hwbrj_group_minmax_row_t* d_out, uint64_t capacity, uint64_t* n_out,
+                                         uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats, double* ms) {
+    return probe_keys_group(b, d_Skeys, d_Svalid, d_Svals, d_Svals_valid, nS, kind, GRP_COUNT_MINMAX, d_out, capacity,
+                            n_out, n_pairs, stream, stats, ms);
+}
+
+int hwbrj_build_unmatched_device(hwbrj_build_t* b, tuple_t* d_out, uint64_t capacity, uint64_t* n_out, void* stream,
+                                 double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (capacity > 0 && !d_out) {
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    if (!e) return rc;
+    uint64_t n = 0;
+    if ((rc = e->unmatched(b, (uint2*) d_out, capacity, &n, (hipStream_t) stream, ms))) return rc;
+    if (n_out) *n_out = n;
+    if (n > capacity) {
+        set_last_error("output capacity below the row count (*n_out holds the count)");
+        return 7;
+    }
+    return 0;
+}
+
+int hwbrj_build_reset_marks(hwbrj_build_t* b) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    int rc = 0;
+    if (!build_engine(b, &rc)) return rc;
+    if (hipMemset(b->marks.p, 0, b->marks.bytes) != hipSuccess) {
+        set_last_error("clearing the marks failed");
+        return 1;
+    }
+    return 0;
 }
 
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE

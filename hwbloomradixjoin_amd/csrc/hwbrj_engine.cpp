@@ -247,6 +247,19 @@ void PartSide::release() {
     for (DevBuf* b : {&pool, &meta, &used, &wgqc, &wgqe, &wgqo, &lstart, &estart, &istart, &list, &col}) b->release();
 }
 
+void RSide::release() {
+    R.release();
+    for (DevBuf* b : {&slices, &rjoin, &rrun, &rpay, &ppoolR, &rvalid}) b->release();
+}
+
+size_t RSide::bytes() const {
+    size_t n = 0;
+    for (const DevBuf* b : {&R.pool, &R.meta, &R.used, &R.wgqc, &R.wgqe, &R.wgqo, &R.lstart, &R.estart, &R.istart,
+                            &R.list, &R.col, &slices, &rjoin, &rrun, &rpay, &ppoolR, &rvalid})
+        n += b->bytes;
+    return n;
+}
+
 void PartSide::bind(ScatterParams* sp, uint64_t cap) const {
     sp->pool       = pool.as<uint32_t>();
     sp->meta       = meta.as<uint32_t>();
@@ -320,8 +333,8 @@ uint64_t region_cap(uint64_t n, uint32_t G, uint32_t F) {
     return (per + 31) / 32 + F + 1;
 }
 
-int Engine::run(const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, JoinExtras* x) {
-    int rc = enqueue(in, req);
+int Engine::run(const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, JoinExtras* x, const Build* b) {
+    int rc = enqueue(in, req, b);
     if (rc == 0) rc = wait(st);
     if (rc || !x) return rc;
     // (the join has completed; its ring slot is taken again by the next enqueue only)
@@ -410,11 +423,14 @@ static const char* shape_limits(const JoinShape& s, const JoinReq& q) {
 // (job_surv is left zero by k_join_split for the NJ jobs it saw: a join with another NJ clears the
 // whole buffer, *jnew, so no stale count of an earlier job layout is read; last_nj_ moves whether or
 // not an allocation fails)
-bool Engine::ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew) {
+// r_side off (a probe of a prepared build): no buffer of R's is grown, the build has its own.
+bool Engine::ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew, bool r_side) {
     *jnew    = jparts.bytes < (size_t) (2 * s.NJ + 1) * 4 || s.NJ != last_nj_;
     last_nj_ = s.NJ;
-    return R_.ensure(s.LR, s.G, s.F) && S_.ensure(s.LS, s.G, s.F) && rjoin.ensure(s.sweeps_max * s.SLOT * 4) &&
-           rrun.ensure(2 * s.sweeps_max * s.NSUB * 4) && surv.ensure(surv_segs * s.LS * 128) &&
+    if (r_side && !(R_.ensure(s.LR, s.G, s.F) && rjoin.ensure(s.sweeps_max * s.SLOT * 4) &&
+                    rrun.ensure(2 * s.sweeps_max * s.NSUB * 4)))
+        return false;
+    return S_.ensure(s.LS, s.G, s.F) && surv.ensure(surv_segs * s.LS * 128) &&
            survcnt.ensure(s.items_max * s.NSUB * 4) && survoff.ensure(s.items_max * s.NSUB * 4) &&
            jring_.ensure(kJoinRing * ring_slot_bytes()) && jtask.ensure((size_t) join_extra_tasks() * 8) &&
            jparts.ensure((size_t) (2 * s.NJ + 1) * 4);
@@ -423,12 +439,12 @@ bool Engine::ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew) {
 bool Engine::ensure_buffers(JoinCtx* c) {
     const JoinShape& s = c->s;
     const Geometry&  g = c->g;
-    bool ok = ensure_common(s, s.nseg, &c->jnew);
-    if (s.slice_mode) ok = ok && slices.ensure((uint64_t) s.F * s.nseg * g.seg_words * 4);
+    bool ok = ensure_common(s, s.nseg, &c->jnew, !c->b);
+    if (s.slice_mode && !c->b) ok = ok && slices.ensure((uint64_t) s.F * s.nseg * g.seg_words * 4);
     if (g.mode == MODE_GLOBAL) ok = ok && bitmap.ensure(((g.m + 31) / 32) * 4) && dense.ensure(c->in.nS * 4);
     if (c->basic_kk) ok = ok && bpos.ensure(c->nRk * 4);
     if (c->q.carries_s_payloads()) ok = ok && ppoolS.ensure(s.LS * 128) && survpos.ensure(s.nseg * s.LS * 128);
-    if (c->q.carries_r_payloads()) ok = ok && ppoolR.ensure(s.LR * 128) && rpay.ensure(s.sweeps_max * s.SLOT * 4);
+    if (c->q.carries_r_payloads() && !c->b) ok = ok && ppoolR.ensure(s.LR * 128) && rpay.ensure(s.sweeps_max * s.SLOT * 4);
     if (uses_smark(g, c->q)) ok = ok && smark.ensure(s.LS * 4);
     return ok;
 }
@@ -443,18 +459,18 @@ ScatterParams Engine::scatter_params(const Geometry& g, const PartSide& side, ui
 }
 
 // k_build over R's lists (R items = build sweeps); no slices, no payloads, 32-bit codes
-BuildParams Engine::build_params(const Geometry& g, const JoinShape& s) const {
+BuildParams Engine::build_params(const RSide& r, const Geometry& g, const JoinShape& s) const {
     BuildParams bp{};
     bp.g           = g;
     bp.tabs        = d_tabs_;
-    bp.pool        = R_.pool.as<uint32_t>();
-    bp.list        = R_.list.as<uint32_t>();
-    bp.list_start  = R_.lstart.as<uint32_t>();
-    bp.elem_start  = R_.estart.as<uint64_t>();
-    bp.sweep_start = R_.istart.as<uint32_t>();
-    bp.out_codes   = rjoin.as<uint32_t>();
-    bp.run_cnt     = rrun.as<uint32_t>();
-    bp.run_off     = rrun.as<uint32_t>() + s.sweeps_max * s.NSUB;
+    bp.pool        = r.R.pool.as<uint32_t>();
+    bp.list        = r.R.list.as<uint32_t>();
+    bp.list_start  = r.R.lstart.as<uint32_t>();
+    bp.elem_start  = r.R.estart.as<uint64_t>();
+    bp.sweep_start = r.R.istart.as<uint32_t>();
+    bp.out_codes   = r.rjoin.as<uint32_t>();
+    bp.run_cnt     = r.rrun.as<uint32_t>();
+    bp.run_off     = r.rrun.as<uint32_t>() + s.sweeps_max * s.NSUB;
     return bp;
 }
 
@@ -476,12 +492,12 @@ ProbeParams Engine::probe_params(const Geometry& g, const JoinShape& s) const {
 }
 
 // k_join over the build's and the probe's runs, its partial sums in the ring slot; 32-bit codes
-JoinParams Engine::join_params(const Geometry& g, const JoinShape& s, char* slot, int jkind) const {
+JoinParams Engine::join_params(const RSide& r, const Geometry& g, const JoinShape& s, char* slot, int jkind) const {
     JoinParams jp{};
-    jp.r_codes         = rjoin.as<uint32_t>();
-    jp.r_sweep_start   = R_.istart.as<uint32_t>();
-    jp.r_cnt           = rrun.as<uint32_t>();
-    jp.r_off           = rrun.as<uint32_t>() + s.sweeps_max * s.NSUB;
+    jp.r_codes         = r.rjoin.as<uint32_t>();
+    jp.r_sweep_start   = r.R.istart.as<uint32_t>();
+    jp.r_cnt           = r.rrun.as<uint32_t>();
+    jp.r_off           = r.rrun.as<uint32_t>() + s.sweeps_max * s.NSUB;
     jp.slot            = (uint32_t) s.SLOT;
     jp.surv            = surv.as<uint32_t>();
     jp.surv_cnt        = survcnt.as<uint32_t>();
@@ -557,7 +573,9 @@ int Engine::validate(JoinCtx* c) {
         return 2;
     }
     std::string err;
-    if (!plan_geometry(in.args, in.nR, &c->g, &err, q.carries_s_payloads())) {
+    if (c->b) {  // (a probe: the build's geometry, planned and found supported when it was made)
+        c->g = c->b->r.g;
+    } else if (!plan_geometry(in.args, in.nR, &c->g, &err, q.carries_s_payloads())) {
         set_last_error(err);
         return 2;
     }
@@ -585,22 +603,32 @@ void Engine::plan(JoinCtx* c) {
     c->nRk      = c->basic_kk ? (uint64_t) g.k * c->in.nR : 0;
     c->s = JoinShape::make(F, NSUB, F * NSUB, slice_mode ? g.nseg : 1, G, region_cap(c->in.nR, G, F),
                            region_cap(std::max(c->in.nS, c->nRk), G, F), slice_mode);
+    // a probe: capR, and with it the sweeps' layout of rrun, are the build's; capS from this batch
+    if (c->b) {
+        const JoinShape& r = c->b->r.s;
+        c->s = JoinShape::make(r.F, r.NSUB, r.NJ, r.nseg, r.G, r.capR, region_cap(c->in.nS, r.G, r.F), r.slice_mode);
+    }
     // the north_star's bitmap broadcast (opt-in, hwbrj_set_filter_broadcast) makes this join a
     // collective: from here on a failure of this rank alone must not leave its peers waiting in
     // ncclBroadcast, so every return before the first kernel goes through one status agreement
     // (enqueue's pre(); argument errors before it fail alike on every rank)
-    c->bcast = bcast_ && comm_ && slice_mode && !c->basic_kk;
+    c->bcast = bcast_ && comm_ && slice_mode && !c->basic_kk && !c->b;  // (a build's slices are always local)
 }
 
-int Engine::enqueue(const JoinIn& in, const JoinReq& req) {
+// b: a probe of a prepared build (Build). The same stages over the build's RSide instead of the
+// Engine's own, without the R side: the shape takes capR from the build, only the S side and the job
+// table are ensured, the S scatter carries the ring slot's zeroing, and the tables are not read back.
+int Engine::enqueue(const JoinIn& in, const JoinReq& req, const Build* b) {
     JoinCtx c{in, req};
+    c.b  = b;
+    c.rs = b ? &b->r : &rs_;
     if (const int rc = validate(&c)) return rc;
     // Every join on this device shares this Engine's scratch (pools, lists, slices, counters):
     // a join enqueued on another stream than a still-pending one must run after it (on the same
     // stream, stream order does it: no wait packet between back-to-back joins).
     if (!c.in.stream) c.in.stream = own_stream_;
     if (pending_ && c.in.stream != pending_stream_) HWBRJ_CHECK(hipStreamWaitEvent(c.in.stream, ev_[8], 0));
-    if (!req.carries_s_payloads() && c.g.mode == MODE_SLICE_BASIC && c.g.k > 1 &&
+    if (!b && !req.carries_s_payloads() && c.g.mode == MODE_SLICE_BASIC && c.g.k > 1 &&
         (uint64_t) c.g.k * in.nR <= (1ull << 31))
         return enqueue_basic_kk(c.in, c.g, req);
     plan(&c);
@@ -623,7 +651,7 @@ int Engine::enqueue(const JoinIn& in, const JoinReq& req) {
     if (const int rc = passes(&c)) return rc;
     ProbeParams pp;
     if (const int rc = probe(c, &pp)) return rc;
-    JoinParams jp = join_params(c.g, c.s, c.sm, req.jkind);
+    JoinParams jp = join_params(*c.rs, c.g, c.s, c.sm, req.jkind);
     jp.r_kbits    = c.kbits;
     jp.fmt_cnt    = pp.fmt_cnt;
     const JobInputs ji = job_inputs(jp, survpos.as<uint32_t>());
@@ -638,7 +666,8 @@ int Engine::enqueue(const JoinIn& in, const JoinReq& req) {
     if (rc) return rc;
     TabRec t;  // the shape of this join's tables (tables_info / tables_read)
     // (the existence / outer / group join's tables: not read back)
-    t.state = req.kind == JOIN_COUNT || req.kind == JOIN_PAIRS ? kTabJoin : kTabOther;
+    // nor a probe's: R's tables are the build's
+    t.state = !b && (req.kind == JOIN_COUNT || req.kind == JOIN_PAIRS) ? kTabJoin : kTabOther;
     t.mat   = req.carries_r_payloads();
     t.s     = c.s;
     (void) probe_lds_bytes(c.g, &t.stage_cap, req.carries_s_payloads());
@@ -653,20 +682,22 @@ int Engine::enqueue(const JoinIn& in, const JoinReq& req) {
     r.slots    = !req.carries_s_payloads();  // (the matches are in k_join's partial sums)
     r.timed    = c.rtimed;
     r.s_masked = c.vS != nullptr || c.vV != nullptr;
-    return finish(c.in, c.g, c.s_first, t, r);
+    return finish(c.in, c.g, c.s_first, t, r, b != nullptr);
 }
 
 // 8. The epilogue of both enqueue paths: the join's completion event, what wait() and the next
 // enqueue need of it, its tables' shape and its record in the ring.
-int Engine::finish(const JoinIn& in, const Geometry& g, bool s_first, const TabRec& tab, JoinRec rec) {
+// prepared: a probe's filter belongs to its build, so export_filter finds none.
+int Engine::finish(const JoinIn& in, const Geometry& g, bool s_first, const TabRec& tab, JoinRec rec, bool prepared) {
     HWBRJ_CHECK(hipEventRecord(ev_[8], in.stream));
     HWBRJ_CHECK(hipGetLastError());
     pending_        = true;
     pending_rc_     = 0;
     pending_ev_     = phase_ev_;
     pending_sfirst_ = s_first;
+    pending_prepared_ = prepared;
     pending_stream_ = in.stream;
-    have_filter_    = in.args != nullptr;
+    have_filter_    = in.args != nullptr && !prepared;
     last_g_         = g;
     tab_            = tab;
     tab_.sync       = phase_ev_;
@@ -704,6 +735,10 @@ int Engine::s_pass(const JoinCtx& c, hipStream_t st, bool marks, hipEvent_t* tev
         else if (c.vS) ss.valid = c.vS;                          // (the same slot: never both)
     }
     ss.ppool = c.q.carries_s_payloads() ? ppoolS.as<uint32_t>() : nullptr;
+    if (c.b) {  // a probe has no R scatter: this one's workgroup 0 zeroes the slot's counts and the extra-task count
+        ss.zero_small = (uint32_t*) c.sm;
+        ss.zero_word  = jparts.as<uint32_t>() + 2 * c.s.NJ;
+    }
     if (tev) HWBRJ_CHECK(hipEventRecord(tev[0], st));
     launch_scatter(ss, g.mode == MODE_GLOBAL ? SRC_CODES : val_masked ? SRC_KEYS_VAL_MASK : c.vS ? SRC_KEYS_MASK : layout_s,
                    SIDE_S, c.s.G, st);
@@ -716,7 +751,9 @@ int Engine::s_pass(const JoinCtx& c, hipStream_t st, bool marks, hipEvent_t* tev
 
 // R: pass-1 (+ filter), its lists, the build sweeps; then the slices' broadcast, or their build from
 // bit positions (basic k >= 2).
-int Engine::r_side(const JoinCtx& c) {
+// r: where it is left (the Engine's own RSide, or a build's); zero_small / zero_word: the join's
+// zeroing the R scatter carries (a build: none, it is part of no join).
+int Engine::r_side(const JoinCtx& c, RSide* r, uint32_t* zero_small, uint32_t* zero_word) {
     const Geometry&  g = c.g;
     const JoinShape& s = c.s;
     const JoinIn&    in = c.in;
@@ -726,21 +763,21 @@ int Engine::r_side(const JoinCtx& c) {
         launch_build_global(in.dR, c.q.layout, in.nR, g, d_tabs_, bitmap.as<uint32_t>(), stream);
     // zeroing (the reference callocs before its timer, :1583, :1601): the counts and the join's
     // extra-task count are zeroed by this scatter's workgroup 0 (two memset dispatches less per join)
-    ScatterParams sp = scatter_params(g, R_, s.capR);
+    ScatterParams sp = scatter_params(g, r->R, s.capR);
     sp.src        = in.dR;
     sp.n          = in.nR;
-    sp.ppool      = rpay_on ? ppoolR.as<uint32_t>() : nullptr;
-    sp.zero_small = (uint32_t*) c.sm;
-    sp.zero_word  = jparts.as<uint32_t>() + 2 * s.NJ;
+    sp.ppool      = rpay_on ? r->ppoolR.as<uint32_t>() : nullptr;
+    sp.zero_small = zero_small;
+    sp.zero_word  = zero_word;
     if (c.vR) sp.valid = c.vR;
     launch_scatter(sp, c.vR ? SRC_KEYS_MASK : c.q.layout, SIDE_R, s.G, stream);
     HWBRJ_CHECK(mark(1, stream));
-    index_side(R_, s.capR, g.log2F, (uint32_t) s.BSW, 1, s.G, stream);
+    index_side(r->R, s.capR, g.log2F, (uint32_t) s.BSW, 1, s.G, stream);
     HWBRJ_CHECK(mark(2, stream));
-    BuildParams bp = build_params(g, s);
-    bp.slices  = s.slice_mode ? slices.as<uint32_t>() : nullptr;
-    bp.ppool   = rpay_on ? ppoolR.as<uint32_t>() : nullptr;
-    bp.out_pay = rpay_on ? rpay.as<uint32_t>() : nullptr;
+    BuildParams bp = build_params(*r, g, s);
+    bp.slices  = s.slice_mode ? r->slices.as<uint32_t>() : nullptr;
+    bp.ppool   = rpay_on ? r->ppoolR.as<uint32_t>() : nullptr;
+    bp.out_pay = rpay_on ? r->rpay.as<uint32_t>() : nullptr;
     bp.kbits   = c.kbits;
     // the broadcast: rank 0 builds the slices, the other ranks only sub-partition R for the join
     // and receive them over RCCL (HWBRJ_HOOK_BCAST_NONROOT: this rank takes the non-root side, for
@@ -788,7 +825,12 @@ int Engine::passes(JoinCtx* c) {
     // probe items too large for the stage (their 32-bit survivor runs make the join read two formats,
     // k_join_mixed): a performance hint only, both paths give the same counts
     c->kbits = !pl && join_pack3(g) && pack3_hint_ ? join_key_bits(g) : 0u;  // 18 at the north star
+    if (c->b) c->kbits = c->b->r.kbits;  // (a build's packing was decided when it was made)
     HWBRJ_CHECK(mark(0, stream));
+    if (c->b) {  // a probe: the S pass alone (wait_common gives the R phases 0)
+        c->s_first = true;
+        return s_pass(*c, stream, true, nullptr);
+    }
     const bool ovl = HWBRJ_OVL_ASYNC && !phase_ev_ && g.mode != MODE_GLOBAL && !c->basic_kk && !pl && !c->bcast;
     if (ovl) {  // S pass on the side stream (with phase events, its phases would show inside the R side's)
         if (!ovl_stream_) {
@@ -818,7 +860,7 @@ int Engine::passes(JoinCtx* c) {
     c->s_first = !ovl && g.mode != MODE_GLOBAL && !c->basic_kk;
     if (c->s_first)
         if (const int rc = s_pass(*c, stream, true, nullptr)) return rc;
-    if (const int rc = r_side(*c)) return rc;
+    if (const int rc = r_side(*c, &rs_, (uint32_t*) c->sm, jparts.as<uint32_t>() + 2 * c->s.NJ)) return rc;
     if (ovl) {
         HWBRJ_CHECK(hipStreamWaitEvent(stream, ovl_ev_[1], 0));
         HWBRJ_CHECK(mark(4, stream));
@@ -833,7 +875,7 @@ int Engine::passes(JoinCtx* c) {
 int Engine::probe(const JoinCtx& c, ProbeParams* pp) {
     const bool pl = c.q.carries_s_payloads();
     *pp           = probe_params(c.g, c.s);
-    pp->slices    = c.s.slice_mode ? slices.as<uint32_t>() : nullptr;
+    pp->slices    = c.s.slice_mode ? c.rs->slices.as<uint32_t>() : nullptr;
     pp->filtered  = c.result() + 2;
     pp->surv_pos  = pl ? survpos.as<uint32_t>() : nullptr;
     pp->kbits     = c.kbits;
@@ -860,7 +902,7 @@ int Engine::clear_job_surv(const JoinCtx& c) {
 MatJoinParams Engine::mat_params(const JoinCtx& c, const JobInputs& ji) const {
     MatJoinParams mp{};
     mp.j     = ji;
-    mp.r_pay = rpay.as<uint32_t>();
+    mp.r_pay = c.rs->rpay.as<uint32_t>();
     mp.bm    = pay_bitmap(c.g) ? 1u : 0u;
     mp.s_pay = ppoolS.as<uint32_t>();
     mp.out   = c.q.kind == JOIN_GROUP ? nullptr : (uint2*) c.q.out;  // (k_join_group has its own)
@@ -931,7 +973,8 @@ int Engine::join_outer(const JoinCtx& c, const JobInputs& ji) {
     op.null_pay = q.null_pay;
     op.mark     = q.keep_s ? smark.as<uint32_t>() : nullptr;
     op.n_r_only = cls;
-    launch_join_outer(op, c.s.NJ, stream);
+    if (q.rmark) launch_join_outer_mark(OuterMarkParams{op, q.rmark}, c.s.NJ, stream);
+    else launch_join_outer(op, c.s.NJ, stream);
     if (q.keep_s) {  // every unmarked S tuple: the filter's rejects and the unmatched survivors
         OuterEmitParams oe{};
         oe.ppool      = ppoolS.as<uint32_t>();
@@ -1037,7 +1080,7 @@ int Engine::enqueue_basic_kk(const JoinIn& in, const Geometry& g, const JoinReq&
     HWBRJ_CHECK(mark(1, stream));
     index_side(R_, capR, gj.log2F, (uint32_t) BSW, 1, G, stream);
     HWBRJ_CHECK(mark(2, stream));
-    launch_build(build_params(gj, s), Fj, stream);
+    launch_build(build_params(rs_, gj, s), Fj, stream);
     // ---------------------------------------------------------------- the filter slices
     if (g.k <= G) {  // R's k bit positions partitioned by slice straight from the tuples
         Geometry gp = g;
@@ -1107,7 +1150,7 @@ int Engine::enqueue_basic_kk(const JoinIn& in, const Geometry& g, const JoinReq&
     HWBRJ_CHECK(mark(7, stream));
     surv_fused_ = false;
     // -------------------------------------------------------------------------- join
-    JoinParams jp = join_params(gj, s, sm, req.jkind);
+    JoinParams jp = join_params(rs_, gj, s, sm, req.jkind);
     jp.nseg       = 1;  // (the survivors were re-partitioned without segments)
     launch_join(jp, s.NJ, jparts.as<uint32_t>() + s.NJ, stream);
     TabRec t;
@@ -1194,12 +1237,16 @@ int Engine::ring_collect() {
 
 // Waits for the last join and collects every join since the last wait; the last one's phase times
 // (synchronous joins) are read from its events.
-static int wait_common(hwbrj_stats_t* last, bool phases, const hipEvent_t* ev, bool sfirst, bool surv_fused) {
+// prepared: the join probed a prepared build (S pass first, no R side): its R boundaries ev[1..3]
+// were not recorded, and stand at the end of the S lists, so the R phases are 0.
+static int wait_common(hwbrj_stats_t* last, bool phases, const hipEvent_t* ev, bool sfirst, bool surv_fused,
+                       bool prepared) {
     float ms[9] = {0, 0, 0, 0, (float) last->ms_s_scatter, 0, 0, 0, 0};  // (async: the timed S scatter only)
     if (phases) {  // (async joins: counts only)
         hipEvent_t e[9];
         for (int i = 0; i <= 8; i++) e[i] = ev[i];
         if (surv_fused) e[7] = ev[6];
+        if (prepared) e[1] = e[2] = e[3] = ev[5];
         // phase i ends at boundary i and starts at boundary from[i] (S pass first: it starts the
         // join, the R scatter starts after the S lists, the probe after the build)
         static const int kFrom[2][9] = {{0, 0, 1, 2, 3, 4, 5, 6, 7}, {0, 5, 1, 2, 0, 4, 3, 6, 7}};
@@ -1245,7 +1292,7 @@ int Engine::wait_all(hwbrj_stats_t* st, int cap, int* n) {
     if (const int rc = wait_pending()) return rc;
     for (size_t i = 0; i < jdone_.size(); i++) {  // ticks -> ms (only the last has phase times)
         if (i + 1 == jdone_.size()) {
-            if (const int rc = wait_common(&jdone_[i], pending_ev_, ev_, pending_sfirst_, surv_fused_)) return rc;
+            if (const int rc = wait_common(&jdone_[i], pending_ev_, ev_, pending_sfirst_, surv_fused_, pending_prepared_)) return rc;
         } else {
             jdone_[i].ms_join_probe = jdone_[i].ms_join = 0;  // (the ticks: not phase times)
         }
@@ -1269,7 +1316,7 @@ int Engine::wait(hwbrj_stats_t* st) {
     if (!jdone_.empty()) {  // (else: the last join was collected before; its stats again)
         last_st_ = jdone_.back();
         jdone_.clear();
-        if (const int rc = wait_common(&last_st_, pending_ev_, ev_, pending_sfirst_, surv_fused_)) return rc;
+        if (const int rc = wait_common(&last_st_, pending_ev_, ev_, pending_sfirst_, surv_fused_, pending_prepared_)) return rc;
     }
     if (st) *st = last_st_;
     return 0;
@@ -1290,17 +1337,152 @@ int Engine::export_filter(uint8_t* host_out, uint64_t nbytes) {
         HWBRJ_CHECK(hipMemcpy(host_out, bitmap.p, nbytes, hipMemcpyDeviceToHost));
         return 0;
     }
+    return export_slices(slices, g, host_out, nbytes);
+}
+
+// the filter of slices sl (geometry g) in the reference layout, m / 8 bytes
+int Engine::export_slices(const DevBuf& sl, const Geometry& g, uint8_t* host_out, uint64_t nbytes) {
     const uint64_t nwords = (g.m + 31) / 32;
     DevBuf tmp;
     if (!tmp.ensure(nwords * 4)) {
         set_last_error("hipMalloc failed");
         return 4;
     }
-    launch_export(slices.as<uint32_t>(), g, tmp.as<uint32_t>(), nwords, own_stream_);
+    launch_export(sl.as<uint32_t>(), g, tmp.as<uint32_t>(), nwords, own_stream_);
     HWBRJ_CHECK(hipStreamSynchronize(own_stream_));
     HWBRJ_CHECK(hipMemcpy(host_out, tmp.p, nbytes, hipMemcpyDeviceToHost));
     tmp.release();
     return 0;
+}
+
+// ------------------------------------------------------------------- prepared builds
+// The R side of the one-shot join of (dR, vR, nR, args) into b's own buffers: the same plan, the same
+// kernels (r_side), no ring slot and no zeroing, since it is part of no join. What the stages after
+// the R side do not read (R's pool, metas, queues and lists but the sweeps' starts, and the R payload
+// pool) is freed once k_build has run. The caller (hwbrj_api.cpp) has refused what a build does not
+// offer; the geometry's refusals are repeated here for a caller that has not.
+int Engine::build(const void* dR, const uint8_t* vR, uint64_t nR, const bloom_filter_args_t* args, hipStream_t stream,
+                  Build* b, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    JoinReq q;
+    q.kind    = b->rows ? JOIN_PAIRS : JOIN_COUNT;
+    q.layout  = SRC_KEYS;
+    q.masks.r = vR;
+    JoinCtx c{JoinIn{dR, nR, nullptr, 0, args, stream}, q};
+    c.vR = nR ? vR : nullptr;
+    std::string err;
+    if (!plan_geometry(args, nR, &c.g, &err, b->rows)) {
+        set_last_error(err);
+        return 2;
+    }
+    if (!masks_supported(c.g)) {
+        set_last_error("a prepared build needs partition slices (blocked/sectorized, basic k = 1, or no filter)");
+        return kRcMaskFilter;
+    }
+    plan(&c);
+    c.bcast = false;  // (hwbrj_set_filter_broadcast does not apply: a build's slices are built here)
+    if (const char* why = shape_limits(c.s, q)) {
+        set_last_error(why);
+        return 3;
+    }
+    RSide&           r = b->r;
+    const JoinShape& s = c.s;
+    bool ok = r.R.ensure(s.LR, s.G, s.F) && r.rjoin.ensure(s.sweeps_max * s.SLOT * 4) &&
+              r.rrun.ensure(2 * s.sweeps_max * s.NSUB * 4);
+    if (s.slice_mode) ok = ok && r.slices.ensure((uint64_t) s.F * s.nseg * c.g.seg_words * 4);
+    if (b->rows)
+        ok = ok && r.ppoolR.ensure(s.LR * 128) && r.rpay.ensure(s.sweeps_max * s.SLOT * 4) &&
+             b->marks.ensure(((nR + 31) / 32) * 4) && b->cnt.ensure(16);
+    if (b->rows && c.vR) ok = ok && r.rvalid.ensure((((nR + 7) / 8) + 3) & ~3ull);
+    if (!ok) {
+        set_last_error("hipMalloc failed (device memory)");
+        return 4;
+    }
+    // the packing of the join keys, decided once as passes() decides it for a one-shot join
+    c.kbits = !b->rows && join_pack3(c.g) && pack3_hint_ ? join_key_bits(c.g) : 0u;
+    hipEvent_t e[2] = {nullptr, nullptr};
+    HWBRJ_CHECK(hipEventCreate(&e[0]));
+    HWBRJ_CHECK(hipEventCreate(&e[1]));
+    auto run = [&]() -> int {
+        HWBRJ_CHECK(hipEventRecord(e[0], stream));
+        phase_ev_    = false;  // (the phase events belong to the joins)
+        const int rc = r_side(c, &r, nullptr, nullptr);
+        phase_ev_    = true;
+        if (rc) return rc;
+        if (b->rows) HWBRJ_CHECK(hipMemsetAsync(b->marks.p, 0, b->marks.bytes, stream));
+        if (r.rvalid.p)  // (the dword tail past ceil(nR / 8) bytes is never read: k_null_rows)
+            HWBRJ_CHECK(hipMemcpyAsync(r.rvalid.p, vR, (nR + 7) / 8, hipMemcpyDeviceToDevice, stream));
+        HWBRJ_CHECK(hipEventRecord(e[1], stream));
+        HWBRJ_CHECK(hipGetLastError());
+        HWBRJ_CHECK(hipStreamSynchronize(stream));
+        if (ms) {
+            float f = 0;
+            HWBRJ_CHECK(hipEventElapsedTime(&f, e[0], e[1]));
+            *ms = f;
+        }
+        return 0;
+    };
+    const int rc = run();
+    (void) hipEventDestroy(e[0]);
+    (void) hipEventDestroy(e[1]);
+    if (rc) return rc;
+    for (DevBuf* d : {&r.R.pool, &r.R.meta, &r.R.used, &r.R.wgqc, &r.R.wgqe, &r.R.wgqo, &r.R.lstart, &r.R.estart,
+                      &r.R.list, &r.R.col, &r.ppoolR})
+        d->release();
+    r.g        = c.g;
+    r.s        = s;
+    r.kbits    = c.kbits;
+    r.nR       = nR;
+    r.r_masked = c.vR != nullptr;
+    b->device  = device_;
+    b->has_args = args != nullptr;
+    if (args) b->args = *args;
+    return 0;
+}
+
+// The R rows no marking probe has matched: k_null_rows' pass over the marks, which have the layout of
+// a validity bitmap (a clear bit is a row to emit, the tail past nR is masked off).
+int Engine::unmatched(Build* b, uint2* out, uint64_t cap, uint64_t* n, hipStream_t stream, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    hipEvent_t e[2] = {nullptr, nullptr};
+    HWBRJ_CHECK(hipEventCreate(&e[0]));
+    HWBRJ_CHECK(hipEventCreate(&e[1]));
+    auto run = [&]() -> int {
+        HWBRJ_CHECK(hipMemsetAsync(b->cnt.p, 0, 8, stream));
+        HWBRJ_CHECK(hipEventRecord(e[0], stream));
+        launch_null_rows(NullRowsParams{b->marks.as<uint8_t>(), nullptr, b->r.nR, NULL_ROWS_R, 0xFFFFFFFFu, out, cap,
+                                        b->cnt.as<unsigned long long>(), nullptr},
+                         (uint32_t) cus_ * 2, stream);
+        HWBRJ_CHECK(hipEventRecord(e[1], stream));
+        HWBRJ_CHECK(hipGetLastError());
+        HWBRJ_CHECK(hipMemcpyAsync(n, b->cnt.p, 8, hipMemcpyDeviceToHost, stream));
+        HWBRJ_CHECK(hipStreamSynchronize(stream));
+        if (ms) {
+            float f = 0;
+            HWBRJ_CHECK(hipEventElapsedTime(&f, e[0], e[1]));
+            *ms = f;
+        }
+        return 0;
+    };
+    const int rc = run();
+    (void) hipEventDestroy(e[0]);
+    (void) hipEventDestroy(e[1]);
+    return rc;
+}
+
+int Engine::export_build_filter(const Build& b, uint8_t* host_out, uint64_t nbytes) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!b.has_args) {
+        set_last_error("no filter has been built");
+        return 5;
+    }
+    if (nbytes != b.r.g.m / 8) {
+        set_last_error("nbytes must equal m/8");
+        return 6;
+    }
+    return export_slices(b.r.slices, b.r.g, host_out, nbytes);
 }
 
 // ---- test-only table readback (include/hwbrj.h hwbrj_tables_info / hwbrj_tables_read) ----

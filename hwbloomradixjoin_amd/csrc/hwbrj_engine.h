@@ -58,6 +58,8 @@ struct KeyMasks {
 // runs without; nothing after the scatters knows: a NULL key is in no partition. The rows NULL keys
 // contribute themselves (anti, outer, GROUP all) come from k_null_rows / k_null_group_rows after the
 // kind's own emit kernels, through the same row counter.
+// rmark: the marking probes of a prepared build (OUTER, keep_r off): every R row with a partner sets
+// its bit there (k_join_outer_mark), and no R-only row is written.
 enum JoinKind : int { JOIN_COUNT = 0, JOIN_PAIRS, JOIN_SEMI, JOIN_OUTER, JOIN_GROUP };
 struct JoinReq {
     JoinKind    kind = JOIN_COUNT;
@@ -71,6 +73,7 @@ struct JoinReq {
     const void* s_val = nullptr;
     int         jkind = 0, layout = SRC_TUPLES;
     KeyMasks    masks;
+    uint32_t*   rmark = nullptr;  // OUTER on a prepared build: the build's marks (the marking probes)
     bool carries_s_payloads() const { return kind != JOIN_COUNT; }
     bool carries_r_payloads() const { return kind == JOIN_PAIRS || kind == JOIN_OUTER || kind == JOIN_GROUP; }
 };
@@ -152,6 +155,41 @@ inline bool join_uses_bitmap(const Geometry& g) {
     return g.sub_shift > 0 && 32 - g.hash_shift <= join_bitmap_log2();
 }
 
+// What the R side of a join (pass-1, lists, k_build, slices) leaves behind for the stages after it:
+// everything the probe and the join stages read of R. The Engine keeps one for the one-shot entries,
+// rewritten by every join; a prepared build (Build, include/hwbrj.h hwbrj_build_keys_device) owns
+// another, written once. R.istart (the sweeps' starts) is the only table of R's PartSide the later
+// stages read: a build frees the rest, and ppoolR, after its k_build (Engine::build).
+// g, s, kbits, nR: the geometry, the R half of the shape (JoinShape::make with capS = 0), the packed
+// join-key bits and |R| of the last R side run into it (a probe takes its shape from them).
+// rvalid: a build's own copy of R's validity bitmap (the NULL R rows of the outer and group probes),
+// or empty: R had none.
+struct RSide {
+    PartSide  R;
+    DevBuf    slices, rjoin, rrun, rpay, ppoolR, rvalid;
+    Geometry  g{};
+    JoinShape s{};
+    uint32_t  kbits = 0;
+    uint64_t  nR    = 0;
+    bool      r_masked = false;
+    void      release();
+    size_t    bytes() const;
+};
+
+// A prepared build (hwbrj_build_t): R's side, made once by Engine::build, probed by any number of
+// S batches (Engine::run with the build). rows: HWBRJ_BUILD_ROWS, the payload pipeline's R side with
+// R's row indices as payloads, and one mark bit per R row (marks; bit i & 31 of dword i >> 5) that
+// the marking probes OR into and Engine::unmatched reads; cnt: its row counter. args: the filter the
+// build was made with (has_args), kept for the probes' stats and export.
+struct Build {
+    RSide               r;
+    bool                rows = false, has_args = false;
+    int                 device = 0;
+    bloom_filter_args_t args{};
+    DevBuf              marks, cnt;
+    size_t              bytes() const { return r.bytes() + marks.bytes + cnt.bytes; }
+};
+
 class Engine {
   public:
     explicit Engine(int device);
@@ -159,7 +197,18 @@ class Engine {
     // One synchronous join (JoinReq): enqueue, wait, then the kind's extra counts (*x, or nullptr).
     // Returns 0 on success. st->matches = matches (COUNT) or rows (all of them, also beyond cap).
     // kRcMatGlobal: a payload join in the global-bitmap mode (run COUNT, then side()).
-    int  run(const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, JoinExtras* x = nullptr);
+    // b: a probe of a prepared build: in.dR is not read, in.nR and in.args are the build's, and the
+    // R side is skipped (enqueue).
+    int  run(const JoinIn& in, const JoinReq& req, hwbrj_stats_t* st, JoinExtras* x = nullptr,
+             const Build* b = nullptr);
+    // A prepared build: the R side of the one-shot join of (dR, vR, nR, args), into buffers b owns
+    // (rows: the payload pipeline's, else the counting join's with the packing the hint decides now).
+    // Synchronous; what only k_build reads is freed before it returns. *ms: its device time.
+    int  build(const void* dR, const uint8_t* vR, uint64_t nR, const bloom_filter_args_t* args, hipStream_t stream,
+               Build* b, double* ms);
+    // {R row, -1} of every R row whose mark is clear (k_null_rows over the marks); *n: all of them
+    int  unmatched(Build* b, uint2* out, uint64_t cap, uint64_t* n, hipStream_t stream, double* ms);
+    int  export_build_filter(const Build& b, uint8_t* host_out, uint64_t nbytes);
     // Enqueue only, a counting join without masks: wait() then waits for the last enqueued join.
     int  run_async(const JoinIn& in, int jkind = 0, int layout = SRC_TUPLES);
     int  wait(hwbrj_stats_t* st);
@@ -324,6 +373,7 @@ class Engine {
     // joins enqueued on it (a destroyed stream's handle can be reused by a new one).
     hipStream_t  pending_stream_ = nullptr;
     bool         pending_sfirst_ = false;  // the pending join ran its S pass first (phase boundaries)
+    bool         pending_prepared_ = false;  // the pending join probed a prepared build: no R phases
     bool         pack3_hint_     = true;   // the last waited join had none: packed join keys pay
     int          pending_rc_     = 0;   // nonzero: the pending join failed after enqueuing kernels
     std::string  pending_err_;
@@ -372,6 +422,8 @@ class Engine {
         char*     sm       = nullptr;     // the ring slot, number rslot
         uint32_t  rslot = 0, kbits = 0;   // kbits: packed join-key bits of build / probe / join
         bool      rtimed = false, s_first = false;
+        const Build* b  = nullptr;        // a probe of this prepared build: no R side
+        const RSide* rs = nullptr;        // what the stages after the R side read: b->r, or the Engine's own
         uint64_t* result() const { return (uint64_t*) sm; }  // [0] matches / rows, [1] dense count, [2] filtered
     };
     // what tables_info / tables_read need of the last enqueued join: which pipeline left its tables
@@ -387,10 +439,10 @@ class Engine {
     // the stages of enqueue, in order (hwbrj_engine.cpp)
     int          validate(JoinCtx* c);
     void         plan(JoinCtx* c);
-    bool         ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew);
+    bool         ensure_common(const JoinShape& s, uint32_t surv_segs, bool* jnew, bool r_side = true);
     bool         ensure_buffers(JoinCtx* c);
     int          s_pass(const JoinCtx& c, hipStream_t st, bool marks, hipEvent_t* tev);
-    int          r_side(const JoinCtx& c);
+    int          r_side(const JoinCtx& c, RSide* r, uint32_t* zero_small, uint32_t* zero_word);
     int          passes(JoinCtx* c);
     int          probe(const JoinCtx& c, ProbeParams* pp);
     int          join_count(const JoinCtx& c, const JoinParams& jp);
@@ -400,26 +452,32 @@ class Engine {
     int          join_group(const JoinCtx& c, const JobInputs& ji);
     int          clear_job_surv(const JoinCtx& c);
     MatJoinParams mat_params(const JoinCtx& c, const JobInputs& ji) const;
-    int          finish(const JoinIn& in, const Geometry& g, bool s_first, const TabRec& tab, JoinRec rec);
+    int          finish(const JoinIn& in, const Geometry& g, bool s_first, const TabRec& tab, JoinRec rec,
+                        bool prepared = false);
     // the parameter blocks both enqueue paths share; each path overrides what differs
     ScatterParams scatter_params(const Geometry& g, const PartSide& side, uint64_t cap) const;
-    BuildParams  build_params(const Geometry& g, const JoinShape& s) const;
+    BuildParams  build_params(const RSide& r, const Geometry& g, const JoinShape& s) const;
     ProbeParams  probe_params(const Geometry& g, const JoinShape& s) const;
-    JoinParams   join_params(const Geometry& g, const JoinShape& s, char* slot, int jkind) const;
-    int          enqueue(const JoinIn& in, const JoinReq& req);
+    JoinParams   join_params(const RSide& r, const Geometry& g, const JoinShape& s, char* slot, int jkind) const;
+    int          enqueue(const JoinIn& in, const JoinReq& req, const Build* b = nullptr);
+    int          export_slices(const DevBuf& sl, const Geometry& g, uint8_t* host_out, uint64_t nbytes);
     // basic k >= 2 without payloads: the repartitioning pipeline (hwbrj_engine.cpp)
     int          enqueue_basic_kk(const JoinIn& in, const Geometry& g, const JoinReq& req);
     TabRec       tab_;
     int          tables_ready();  // 0, or why the tables cannot be read (the codes of hwbrj.h)
     CrcTables*   d_tabs_ = nullptr;
     GenPlan*     d_plan_ = nullptr;
-    PartSide R_, S_;
-    DevBuf slices, bitmap, rjoin, rrun, surv, survcnt, survoff, dense, small;
+    // the one-shot entries' R side (RSide) under the names its buffers always had
+    RSide     rs_;
+    PartSide& R_ = rs_.R;
+    PartSide  S_;
+    DevBuf &  slices = rs_.slices, &rjoin = rs_.rjoin, &rrun = rs_.rrun, &rpay = rs_.rpay, &ppoolR = rs_.ppoolR;
+    DevBuf bitmap, surv, survcnt, survoff, dense, small;
     DevBuf bpos;        // basic k >= 2: R bit positions (k_bitpos)
     DevBuf mtab, mcount;  // the side passes: R table, counters
     // materializing pipeline: payload pools (chunk layout of R_.pool / S_.pool), R payloads of the
     // build sweeps, survivors' chunk positions
-    DevBuf ppoolR, ppoolS, rpay, survpos;
+    DevBuf ppoolS, survpos;
     DevBuf smark;  // existence / outer join: one bit per S chunk position (matched survivors); the
                    // outer side pass: one bit per slot of its table of R (outer_side)
     DevBuf gcnt, gsum;  // the group join's side pass: count and sum per R row (group_side)

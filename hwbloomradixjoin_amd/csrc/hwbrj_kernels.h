@@ -252,6 +252,16 @@ struct OuterJoinParams {
     unsigned long long* n_r_only;  // zero on entry
 };
 void   launch_join_outer(const OuterJoinParams& p, uint32_t jobs, hipStream_t st);
+// The marking probe of a prepared build (k_join_outer_mark): the outer join's pairs and S marks (o;
+// o.keep_r is not read), and every R tuple of a job with at least one partner ORs bit r_payload & 31
+// of dword r_payload >> 5 into rmark, the build's one bit per R row. No R-only row is written. The
+// pointer stands behind OuterJoinParams in a type of its own, the argument of that kernel alone
+// (as ScatterValParams): k_join_outer's argument block is what it was.
+struct OuterMarkParams {
+    OuterJoinParams o;
+    uint32_t*       rmark;  // [ceil(|R| / 32)]
+};
+void   launch_join_outer_mark(const OuterMarkParams& p, uint32_t jobs, hipStream_t st);
 // The outer join's S-only rows (k_outer_emit): {null_pay, payload} of every S tuple of the chunk
 // lists whose position is not marked, appended to out (up to cap; *count and *n_s_only += rows).
 // Reads the lists (for the chunks' counts), the payloads and the marks: not the words.

@@ -3391,17 +3391,24 @@ __device__ __forceinline__ void payload_job(const MatJoinParams& P, Pol& pol, ui
 //    the end of a piece: the unflagged tuples are then written as {R.payload, null} rows, a
 //    workgroup scan and one output atomic per piece. A job without probe items, or without
 //    survivors, therefore still loads its R and writes all of it.
+//  - MK (k_join_outer_mark, the marking probes of a prepared build; with KR): the flags as under KR,
+//    but at the end of a piece no row is written: every flagged tuple ORs the bit of its payload, R's
+//    row index, into the build's marks in global memory (rmark). One global atomic per matched R
+//    tuple and piece, so at most |R| per join whatever S's skew; a per-pair atomic in batch() is not
+//    bounded so. A job without survivors flags nothing, so it does not run (kAllR off).
 constexpr uint32_t kOutFlagWords = kMatT / 32;
 static_assert(kMatRCap <= kMatT && kMatT == kMatThreads * kMatUB, "one flag per rank / slot, kMatUB per thread");
 
-template <bool OUTER, bool KR>
+template <bool OUTER, bool KR, bool MK = false>
 struct PairPolicy {
-    static constexpr bool kAllR = KR, kStorePay = true;
+    static_assert(!MK || (OUTER && KR), "the marks are made of the R flags");
+    static constexpr bool kAllR = KR && !MK, kStorePay = true;
     const MatJoinParams&   P;
     const OuterJoinParams* O;      // OUTER
     uint32_t*              smem;
     JobLds&                L;
     uint32_t*              rflag;  // OUTER: [kOutFlagWords], cleared per piece; set under KR
+    uint32_t*              rmark = nullptr;  // MK: the build's marks, one bit per R row
 
     __device__ __forceinline__ void set_flag(uint32_t i) const { atomicOr(&rflag[i >> 5], 1u << (i & 31u)); }
 
@@ -3448,7 +3455,17 @@ struct PairPolicy {
     // barriers; the first one completes the flags.
     template <bool BM, int U, class Index>
     __device__ __forceinline__ void end(const uint32_t (&)[U], const uint32_t (&)[U], uint32_t nr, Index&&) const {
-        if constexpr (KR) {
+        if constexpr (MK) {
+            const uint32_t  n = BM ? nr : kMatT, tid = threadIdx.x;
+            const uint32_t* pay = BM ? bm_rest(smem) : smem + kMatT;
+            __syncthreads();  // the flags are complete
+#pragma unroll
+            for (int k = 0; k < kMatUB; k++) {
+                const uint32_t i = tid + k * kMatThreads;
+                if (i < n && (BM || smem[i] != kEmpty) && ((rflag[i >> 5] >> (i & 31u)) & 1u))
+                    atomicOr(&rmark[pay[i] >> 5], 1u << (pay[i] & 31u));
+            }
+        } else if constexpr (KR) {
             const uint32_t  n = BM ? nr : kMatT, tid = threadIdx.x;
             const uint32_t* pay = BM ? bm_rest(smem) : smem + kMatT;
             __syncthreads();
@@ -4693,6 +4710,21 @@ __global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(KR 
     __shared__ JobLds   L;
     PairPolicy<true, KR> pol{O.m, &O, smem, L, rflag};
     payload_job(O.m, pol, smem, L);
+}
+
+// The marking probe (OuterMarkParams): k_join_outer<true>'s job with the marks policy.
+__global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(6))) void k_join_outer_mark(OuterMarkParams M) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kPairWords];
+    __shared__ uint32_t rflag[kOutFlagWords];
+    __shared__ JobLds   L;
+    PairPolicy<true, true, true> pol{M.o.m, &M.o, smem, L, rflag, M.rmark};
+    payload_job(M.o.m, pol, smem, L);
+}
+
+void launch_join_outer_mark(const OuterMarkParams& p0, uint32_t jobs, hipStream_t st) {
+    OuterMarkParams p = p0;
+    p.o.m.j.xcd8      = job_xcd8(jobs, p.o.m.j.log2NSUB);
+    k_join_outer_mark<<<jobs, kMatThreads, 0, st>>>(p);
 }
 
 void launch_join_outer(const OuterJoinParams& p0, uint32_t jobs, hipStream_t st) {

@@ -498,6 +498,102 @@ int hwbrj_join_keys_group_minmax_nulls_device(const int32_t * d_Rkeys, const uin
                                               hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
                                               uint64_t * n_out, uint64_t * n_pairs /* optional */,
                                               void * stream, hwbrj_stats_t * stats, double * ms);
+/* ---- Prepared builds: build R once, probe it with many S batches (key columns) ----
+ * Every join entry above takes both relations and redoes the whole R side (R's scatter, its lists,
+ * the build sweeps, the filter slices, the R payloads of the row-index joins) in every call. A caller
+ * who streams S in batches builds R once instead: hwbrj_build_keys_device runs exactly the R side of
+ * the one-shot join of the same (d_Rkeys, d_Rvalid, args) and keeps what the later stages read in
+ * device buffers the build owns; the hwbrj_probe_keys_* entries then run the S pass, the probe and
+ * the join of their one-shot counterpart against it.
+ *  - purpose: HWBRJ_BUILD_COUNT is the counting join's R side (the packing of the join keys is
+ *    decided once, at build time, as a one-shot join decides it, and never changes afterwards);
+ *    HWBRJ_BUILD_ROWS is the R side of the joins that return rows, with R's row indices as payloads
+ *    and one mark bit per R row, clear after the build (the marking probes below).
+ *  - d_Rvalid: R's validity bitmap in the layout and under the alignment rule of the
+ *    hwbrj_join_keys_*_nulls_device entries, or NULL: no NULL keys.
+ *  - Filters: args == NULL, blocked / sectorized with B >= 8, basic k = 1. The global-bitmap and
+ *    basic k >= 2 configurations return 9 before any device call (their pipelines read R again).
+ *  - Refused before any device call, *build unwritten: an unknown purpose (2), build == NULL (2), a
+ *    non-empty key column that does not start at a 16-byte boundary or a non-NULL bitmap of a
+ *    non-empty column that does not start at a 4-byte boundary (2, "align" in hwbrj_last_error()),
+ *    nR >= 2^31 under HWBRJ_BUILD_ROWS (3). On any failure *build is left unwritten.
+ *  - Synchronous. R's column and bitmap are not read again after it returns: the caller may free or
+ *    overwrite them. *ms (optional): the build's device time.
+ *  - A build belongs to the caller and to the device that was current when it was made (another
+ *    current device: 2 from every entry that takes it). Any number may be alive. hwbrj_release, every
+ *    other join entry and the partitioned joins leave them intact; only hwbrj_build_free frees one
+ *    (NULL: 0, nothing done). hwbrj_set_filter_broadcast does not apply: slices are built locally.
+ * hwbrj_build_info writes the HWBRJ_BI_* words (n >= HWBRJ_BI_COUNT, else 7); BYTES is the device
+ * memory the build holds now: what only the build sweeps read (R's chunk pool, metas and lists) is
+ * freed before hwbrj_build_keys_device returns. hwbrj_build_export_filter is hwbrj_export_filter for
+ * the build's filter: the same bytes as after the one-shot join of the same R and args (5 for a build
+ * without a filter, 6 unless nbytes == m / 8).
+ * Not offered: tuple relations, async probes, the global-bitmap and basic k >= 2 configurations, the
+ * partitioned joins, group accumulators kept across batches (the caller combines the batches' rows). */
+typedef struct hwbrj_build_t hwbrj_build_t; /* opaque; owns its device buffers */
+enum { HWBRJ_BUILD_COUNT = 0, HWBRJ_BUILD_ROWS = 1 };
+enum {
+    HWBRJ_BI_NR = 0, HWBRJ_BI_PURPOSE, HWBRJ_BI_MODE, HWBRJ_BI_F, HWBRJ_BI_NSUB, HWBRJ_BI_KEY_BITS,
+    HWBRJ_BI_DEVICE, HWBRJ_BI_BYTES, HWBRJ_BI_MASKED /* R had a bitmap */, HWBRJ_BI_COUNT
+};
+int hwbrj_build_keys_device(const int32_t * d_Rkeys, const uint8_t * d_Rvalid, uint64_t nR,
+                            const bloom_filter_args_t * args, int purpose, void * stream,
+                            hwbrj_build_t ** build, double * ms /* optional */);
+int hwbrj_build_free(hwbrj_build_t * build);
+int hwbrj_build_info(const hwbrj_build_t * build, uint64_t * out, int n);
+int hwbrj_build_export_filter(const hwbrj_build_t * build, uint8_t * host_out, uint64_t nbytes);
+/* The probes: synchronous, key columns only. Each returns exactly what its one-shot counterpart
+ * (hwbrj_join_keys_nulls_device, _pairs_, _semi_, _outer_, _group_, _group_minmax_) returns on the R
+ * the build was made from and this S batch: the same rows as a multiset (R rows as positions in the
+ * caller's R column, S rows as positions in this batch), the same *n_out, n_class and n_pairs, the
+ * same capacity rule (7 above capacity, the count-only form), the same refusals in the same order,
+ * and the same stats->filtered, matches, mode, format, partitions, subparts, join_keys and
+ * join_key_bits. ms_r_scatter, ms_r_index and ms_build are 0 and ms_total covers the probe only.
+ *  - hwbrj_probe_keys_device needs a HWBRJ_BUILD_COUNT build, the five others a HWBRJ_BUILD_ROWS
+ *    build (the semi probe reads R's codes only); a NULL build or the wrong purpose: 2 before any
+ *    device call.
+ *  - After a probe hwbrj_tables_info / hwbrj_tables_read answer 13, and hwbrj_export_filter answers
+ *    as if no filter had been built: the filter belongs to the build.
+ *  - A probe collects pending async joins like every synchronous entry.
+ * hwbrj_probe_keys_outer_device takes two more kinds (the one-shot entries refuse them with 2), for
+ * right and full outer joins streamed over batches, where an R row unmatched in one batch may match
+ * in a later one: HWBRJ_PROBE_MARK_INNER, the inner pairs of this batch, and HWBRJ_PROBE_MARK_S, the
+ * inner pairs plus this batch's S-only rows (HWBRJ_OUTER_S's result, NULL S rows included). Both also
+ * set the build's mark bit of every R row with a partner in this batch; no R-only row is written per
+ * batch and n_class[2] is 0. hwbrj_build_unmatched_device then writes {R row, -1} of every R row
+ * whose mark is clear (NULL R rows included: they never match), in no particular order, under the
+ * usual capacity rule (*n_out the full count, 7 above capacity, capacity 0 with d_out NULL counts
+ * only), and leaves the marks as they are; hwbrj_build_reset_marks clears them. A streamed full outer
+ * join is one HWBRJ_PROBE_MARK_S probe per batch and one hwbrj_build_unmatched_device call; a
+ * streamed right outer join uses HWBRJ_PROBE_MARK_INNER; the streamed R-side anti join is the final
+ * call alone. Both need a HWBRJ_BUILD_ROWS build (2 otherwise). */
+enum { HWBRJ_PROBE_MARK_INNER = 3, HWBRJ_PROBE_MARK_S = 4 };
+int hwbrj_probe_keys_device(const hwbrj_build_t * build, const int32_t * d_Skeys, const uint8_t * d_Svalid,
+                            uint64_t nS, int algorithm, void * stream, hwbrj_stats_t * stats);
+int hwbrj_probe_keys_pairs_device(hwbrj_build_t * build, const int32_t * d_Skeys, const uint8_t * d_Svalid,
+                                  uint64_t nS, tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
+                                  void * stream, hwbrj_stats_t * stats, double * ms);
+int hwbrj_probe_keys_semi_device(hwbrj_build_t * build, const int32_t * d_Skeys, const uint8_t * d_Svalid,
+                                 uint64_t nS, int kind, tuple_t * d_out, uint64_t capacity,
+                                 uint64_t * n_out, void * stream, hwbrj_stats_t * stats, double * ms);
+int hwbrj_probe_keys_outer_device(hwbrj_build_t * build, const int32_t * d_Skeys, const uint8_t * d_Svalid,
+                                  uint64_t nS, int kind, tuple_t * d_out, uint64_t capacity,
+                                  uint64_t * n_out, uint64_t * n_class /* [3], optional */, void * stream,
+                                  hwbrj_stats_t * stats, double * ms);
+int hwbrj_probe_keys_group_device(hwbrj_build_t * build, const int32_t * d_Skeys, const uint8_t * d_Svalid,
+                                  const int32_t * d_Svals, const uint8_t * d_Svals_valid, uint64_t nS,
+                                  int kind, hwbrj_group_row_t * d_out, uint64_t capacity, uint64_t * n_out,
+                                  uint64_t * n_pairs /* optional */, void * stream, hwbrj_stats_t * stats,
+                                  double * ms);
+int hwbrj_probe_keys_group_minmax_device(hwbrj_build_t * build, const int32_t * d_Skeys,
+                                         const uint8_t * d_Svalid, const int32_t * d_Svals,
+                                         const uint8_t * d_Svals_valid, uint64_t nS, int kind,
+                                         hwbrj_group_minmax_row_t * d_out, uint64_t capacity,
+                                         uint64_t * n_out, uint64_t * n_pairs /* optional */, void * stream,
+                                         hwbrj_stats_t * stats, double * ms);
+int hwbrj_build_unmatched_device(hwbrj_build_t * build, tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
+                                 void * stream, double * ms /* optional */);
+int hwbrj_build_reset_marks(hwbrj_build_t * build);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
