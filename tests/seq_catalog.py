@@ -2,11 +2,12 @@
 configurations, join families, their host references and the two schedules that run every join entry
 after every other on one engine. Host only: numpy and the oracle, neither torch nor the library.
 
-A step is (family, config, set). Its reference is computed here once per (family, set) from
+A step is (family, config, set). Its reference is computed here once per (reference, set) from
 orc.join_pairs, np.isin and a sort plus reduceat, `filtered` once per (set, config) from orc.bpro:
-nothing is ever compared with the library's output of another call."""
+nothing is ever compared with the library's output of another call. A probe of a prepared build
+(layout p) has the reference of the one-shot join of the same R and S."""
 import random
-from collections import namedtuple
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
@@ -56,7 +57,10 @@ def plant(Rk, Sk, vR, vS, rng):
 class RelSet:
     """One relation set: key columns Rk, Sk (duplicates on both sides, negative keys, INT_MIN and INT_MAX
     on both), tuple payloads Rp, Sp (never INT_MIN), S's value column Sv (the whole int32 range) and the
-    validity arrays vR, vS (about a fifth NULL, planted keys underneath)."""
+    validity arrays vR, vS (about a fifth NULL, planted keys underneath). For the group joins with
+    validity bitmaps: vV, the validity of S's values (about a fifth NULL, not vS), and Svn, Sv with
+    INT_MIN / INT_MAX alternating under the NULL value bits (test_gpu_keys_group_nulls._poison). Both are
+    drawn from a generator of their own, so every other array is what it was without them."""
 
     def __init__(self, name):
         nR, nS, seed, share = SETS[name]
@@ -81,6 +85,13 @@ class RelSet:
         self.Ri, self.Si = rows2(Rk, np.arange(nR)), rows2(Sk, np.arange(nS))  # {key, row}: what a key-column entry sees
         rR, rS = np.nonzero(vR)[0], np.nonzero(vS)[0]
         self.Rm, self.Sm = self.Ri[rR], self.Si[rS]                        # the compacted valid rows, original indices
+        rng2 = np.random.default_rng(seed + 7)
+        self.vV = rng2.random(nS) >= 0.2
+        Svn = self.Sv.copy()
+        at = np.nonzero(~self.vV)[0]
+        Svn[at[::2]], Svn[at[1::2]] = INT_MIN, INT_MAX
+        self.Svn = Svn
+        self.Smv = self.Si[np.nonzero(vS & self.vV)[0]]                    # the S rows that take part in a masked group join
 
 
 _SETS = {}
@@ -123,8 +134,10 @@ def config_mode(name):
 
 
 # ---------------------------------------------------------------------------------- families
-# op: count | pairs | semi | outer | group | minmax | part; layout: t (tuples) | k (key columns);
-# kind: the entry's kind argument by name (or the HWBRJ_ALGO_* of a counting join); wait: async
+# op: count | pairs | semi | outer | group | minmax | part; layout: t (tuples) | k (key columns) | p (key
+# columns, a probe of a prepared build); kind: the entry's kind argument by name (or the HWBRJ_ALGO_* of
+# a counting join; PROBE_MARK_*: the outer join streamed over batches of S, then the unmatched R rows);
+# masked: with validity bitmaps (the group joins: S's value bitmap too); wait: async
 Family = namedtuple("Family", "name op layout masked kind wait")
 FAMILIES = (
     Family("count_t", "count", "t", False, "ALGO_PRO", False),
@@ -148,18 +161,54 @@ FAMILIES = (
     Family("gminmax_t", "minmax", "t", False, "GROUP_MATCHED", False),
     Family("gminmax_k", "minmax", "k", False, "GROUP_MATCHED", False),
     Family("part_t", "part", "t", False, None, False),
+    Family("gsum_km", "group", "k", True, "GROUP_ALL", False),
+    Family("gminmax_km", "minmax", "k", True, "GROUP_MATCHED", False),
+    Family("count_p", "count", "p", True, "ALGO_PRO", False),
+    Family("pairs_p", "pairs", "p", True, None, False),
+    Family("semi_p", "semi", "p", True, "JOIN_SEMI", False),
+    Family("anti_p", "semi", "p", True, "JOIN_ANTI", False),
+    Family("full_p", "outer", "p", True, "OUTER_FULL", False),
+    Family("full_pu", "outer", "p", False, "OUTER_FULL", False),
+    Family("stream_full_p", "outer", "p", True, "PROBE_MARK_S", False),
+    Family("stream_r_p", "outer", "p", True, "PROBE_MARK_INNER", False),
+    Family("gsum_p", "group", "p", True, "GROUP_ALL", False),
+    Family("gminmax_p", "minmax", "p", True, "GROUP_MATCHED", False),
 )
 FAMILY = {f.name: f for f in FAMILIES}
 FAMILY_NAMES = tuple(FAMILY)
 PAYLOAD = tuple(f.name for f in FAMILIES if f.op in ("pairs", "semi", "outer", "group", "minmax"))
 MASKED = tuple(f.name for f in FAMILIES if f.masked)
 ASYNC = tuple(f.name for f in FAMILIES if f.wait)
+PROBES = tuple(f.name for f in FAMILIES if f.layout == "p")
+STREAMED = tuple(f.name for f in FAMILIES if (f.kind or "").startswith("PROBE_MARK"))
+STREAMED_AS = {"PROBE_MARK_S": "OUTER_FULL", "PROBE_MARK_INNER": "OUTER_R"}  # the one-shot join a streamed one adds up to
 
 
 def is_step(family, config):
     """Whether the header puts (family, config) inside its contract (else: a refusal with code 9)."""
     f = FAMILY[family]
-    return not ((f.masked or f.op == "part") and config in UNSLICED)
+    return not ((f.masked or f.op == "part" or f.layout == "p") and config in UNSLICED)
+
+
+def mask_kind(family):
+    """Which rows a family's join sees: False (all), True (the valid keys: vR, vS) or "values" (a group
+    join with bitmaps: vR, and S rows whose key and value are both valid, vS & vV)."""
+    f = FAMILY[family]
+    return "values" if f.masked and f.op in ("group", "minmax") else f.masked
+
+
+def build_key(family, config, set_name):
+    """The prepared build a probe step uses: (set, config, purpose, masked)."""
+    f = FAMILY[family]
+    assert f.layout == "p"
+    return (set_name, config, "BUILD_COUNT" if f.op == "count" else "BUILD_ROWS", f.masked)
+
+
+def batches(nS):
+    """A streamed step's batches of S, [a, b): three that partition it, cut at multiples of 32 rows (a
+    bitmap's byte a / 8 is then a 4-byte boundary), and an empty one."""
+    c1, c2 = nS // 3 // 32 * 32, 2 * nS // 3 // 32 * 32
+    return ((0, c1), (c1, c2), (c2, nS), (c2, c2))
 
 
 STEPS = tuple((f, c, s) for f in FAMILY_NAMES for c in CONFIG_NAMES for s in SET_NAMES if is_step(f, c))
@@ -209,28 +258,60 @@ def _hits(s, masked):
     return _HITS[key]
 
 
-def _expect(orc, f, s, masked):
-    """The reference of family f on set s, with the masks honoured (masked) or ignored."""
-    keys = f.layout == "k"
-    p = pairs(orc, s.name, masked)
+Ref = namedtuple("Ref", "op keys kind nulls")  # what a reference depends on: several families share one
+
+
+def ref_of(family):
+    """The reference a family is held against: its op, whether rows are row indices (key columns, probes
+    included), the one-shot kind, and whether it is a group join that reads Svn."""
+    f = FAMILY[family]
+    keys = f.layout in ("k", "p")
     if f.op in ("count", "part"):
+        return Ref("count", False, None, False)
+    return Ref(f.op, keys, STREAMED_AS.get(f.kind, f.kind), f.masked and f.op in ("group", "minmax"))
+
+
+def _masked_group_rows(s, r, values):
+    """The group joins with validity bitmaps, on the valid rows alone: a valid R row keeps its position
+    as r_payload, an S row takes part iff its key and (values) its value are valid; under GROUP_ALL a
+    NULL R row gives its identity row."""
+    minmax = r.op == "minmax"
+    rR, v = np.nonzero(s.vR)[0], (s.vS & s.vV if values else s.vS)
+    rows, n_pairs = group_rows(s.Rk[rR], rR, s.Sk[v], s.Svn[v], minmax)
+    if r.kind == "GROUP_MATCHED":
+        return rows[rows[:, 1] != 0], n_pairs
+    nulls = np.nonzero(~s.vR)[0]
+    ident = (0, INT_MAX, INT_MIN) if minmax else (0, 0, 0)
+    null_rows = np.stack([_i32(nulls)] + [np.full(nulls.size, x, np.int32) for x in ident], 1)
+    return np.ascontiguousarray(np.concatenate([rows, null_rows])), n_pairs
+
+
+def _expect(orc, r, s, masked):
+    """Reference r on set s with the masks honoured (masked: True, or "values" with vV too) or ignored."""
+    keys = r.keys
+    p = pairs(orc, s.name, bool(masked))
+    if r.op == "count":
         return Expect(None, 0, p.shape[0], None, None)
     Rp, Sp, null = (np.arange(s.nR), np.arange(s.nS), NULL_K) if keys else (s.Rp, s.Sp, NULL_T)
     inner = rows2(np.asarray(Rp)[p[:, 0]], np.asarray(Sp)[p[:, 1]])
-    if f.op == "pairs":
+    if r.op == "pairs":
         return Expect(u64(inner), p.shape[0], p.shape[0], None, None)
-    if f.op in ("group", "minmax"):
-        rows, n_pairs = group_rows(s.Rk, Rp, s.Sk, s.Sv if keys else s.Sp, f.op == "minmax")
-        if f.kind == "GROUP_MATCHED":
-            rows = rows[rows[:, 1] != 0]
+    if r.op in ("group", "minmax"):
+        if masked:
+            rows, n_pairs = _masked_group_rows(s, r, masked == "values")
+        else:
+            Sv = (s.Svn if r.nulls else s.Sv) if keys else s.Sp
+            rows, n_pairs = group_rows(s.Rk, Rp, s.Sk, Sv, r.op == "minmax")
+            if r.kind == "GROUP_MATCHED":
+                rows = rows[rows[:, 1] != 0]
         return Expect(g64(rows), rows.shape[0], rows.shape[0], None, n_pairs)
     # existence and class rows: np.isin on the valid rows; a NULL row has no partner
     s_hit, r_hit = _hits(s, masked)
-    if f.op == "semi":
-        keep = ~s_hit if f.kind == "JOIN_ANTI" else s_hit
+    if r.op == "semi":
+        keep = ~s_hit if r.kind == "JOIN_ANTI" else s_hit
         rows = rows2(s.Sk[keep], np.asarray(Sp)[keep])
         return Expect(u64(rows), rows.shape[0], rows.shape[0], None, None)
-    keep_s, keep_r = f.kind != "OUTER_R", f.kind != "OUTER_S"
+    keep_s, keep_r = r.kind != "OUTER_R", r.kind != "OUTER_S"
     s_only = rows2(np.full(int((~s_hit).sum()), null), np.asarray(Sp)[~s_hit]) if keep_s else np.empty((0, 2), np.int32)
     r_only = rows2(np.asarray(Rp)[~r_hit], np.full(int((~r_hit).sum()), null)) if keep_r else np.empty((0, 2), np.int32)
     rows = np.concatenate([inner, s_only, r_only])
@@ -239,21 +320,24 @@ def _expect(orc, f, s, masked):
 
 def expect(orc, family, set_name, ignore_masks=False):
     """The reference of (family, set). ignore_masks: what a masked family would return without its
-    bitmaps (test_sequences.py shows that it differs)."""
-    f = FAMILY[family]
-    masked = f.masked and not ignore_masks
-    key = (family, set_name, masked)
+    bitmaps (True), or a masked group join without S's value bitmap alone ("vV"); test_sequences.py
+    shows that both differ."""
+    masked = mask_kind(family)
+    if ignore_masks:
+        masked = bool(masked) and ignore_masks == "vV"
+    key = (ref_of(family), set_name, masked)
     if key not in _EXPECT:
-        _EXPECT[key] = _expect(orc, f, relset(set_name), masked)
+        _EXPECT[key] = _expect(orc, key[0], relset(set_name), masked)
     return _EXPECT[key]
 
 
 def counts(orc, set_name, config, masked=False):
-    """(matches, filtered) of the counting join, from orc.bpro (masked: on the compacted valid rows)."""
+    """(matches, filtered) of the counting join, from orc.bpro (masked: on the compacted valid rows;
+    "values": R compacted by vR, S by vS & vV, what a group join with bitmaps filters)."""
     key = (set_name, config, masked)
     if key not in _FILTERED:
         s, c = relset(set_name), CONFIGS[config]
-        R, S = (s.Rm, s.Sm) if masked else (s.Ri, s.Si)
+        R, S = (s.Rm, s.Smv) if masked == "values" else (s.Rm, s.Sm) if masked else (s.Ri, s.Si)
         if c is None:
             res, filt, _ = orc.bpro(R, S, 8, 0, 0, 0, 0, use_bloom=False)
         else:
@@ -267,7 +351,39 @@ def filtered(orc, set_name, config, masked=False):
 
 
 # ------------------------------------------------------------------------------ the schedule
-CAP, CHUNK, SEED = 700, 25, 20251
+CAP, CHUNK, SEED = 1100, 25, 20251
+LIVE_BUILDS, ELDERS, ELDER_EVERY = 8, 2, 40
+
+
+class BuildCache:
+    """The prepared builds the probe steps share, by build_key. A build is made on first use and kept; at
+    most LIVE_BUILDS are alive, in two generations, each freed oldest first: every ELDER_EVERY-th build
+    made is one of the ELDERS, which live through some 2 * ELDER_EVERY other builds (probed again after
+    hundreds of other joins), the others are freed after LIVE_BUILDS - ELDERS later ones (and made again
+    when their key returns). make(key) and free(build) are the caller's."""
+
+    def __init__(self, make, free):
+        self.make, self.free, self.made = make, free, 0
+        self.young, self.elder = OrderedDict(), OrderedDict()
+
+    def get(self, key):
+        for q in (self.young, self.elder):
+            if key in q:
+                return q[key]
+        q, cap = (self.elder, ELDERS) if self.made % ELDER_EVERY == 0 else (self.young, LIVE_BUILDS - ELDERS)
+        self.made += 1
+        if len(q) == cap:
+            self.free(q.popitem(last=False)[1])
+        q[key] = self.make(key)
+        return q[key]
+
+    def live(self):
+        return list(self.elder.values()) + list(self.young.values())
+
+    def clear(self):
+        for q in (self.young, self.elder):
+            while q:
+                self.free(q.popitem(last=False)[1])
 
 
 def goals_of(prev, step):
@@ -332,24 +448,32 @@ def chunks(entries, size=CHUNK):
 def disturbers():
     d = [("code7", f, c) for c in ("blocked_packed", "global_b4") for f in PAYLOAD if is_step(f, c)]
     d += [("count_only", None, None)]
-    d += [("refused9", kind, c) for kind in ("masked", "part") for c in UNSLICED]
+    d += [("refused9", kind, c) for kind in ("masked", "part", "build") for c in UNSLICED]
     d += [("m_not_pow2", None, None), ("misaligned", None, None), ("unwaited", 1, None), ("unwaited", 3, None),
           ("release", None, None), ("export_filter", None, None), ("tables_read", None, None), ("join_split", None, None),
           ("caller_stream", None, None)]
+    # prepared builds: one made in front of the follower and probed behind it; one made, probed and freed;
+    # the unmatched rows above their capacity
+    d += [("build", "BUILD_COUNT", None), ("build", "BUILD_ROWS", None), ("build_free", None, None), ("unmatched7", None, None)]
     return d
+
+
+SLICED = tuple(c for c in CONFIG_NAMES if c not in UNSLICED)  # the configurations of a prepared build
+ON_B = ("join_split", "unmatched7")  # disturbers that need set B
 
 
 def disturber_schedule():
     """Every disturber followed once by every family: entries (disturber, its set, follower step, i). The
     follower's set alternates between A and B and the disturber runs on the other one (join_split: always
-    on B, the set with jobs above 700 survivors); the follower's config cycles over the ones valid for
+    on B, the set with jobs above 700 survivors; unmatched7: always on B, the set with more than 1,000
+    unmatched R rows); the follower's config cycles over the ones valid for
     its family; i (the entry's index) picks what a disturber cycles over."""
     out, i = [], 0
     for nd, d in enumerate(disturbers()):
         for nf, f in enumerate(FAMILY_NAMES):
             valid = [c for c in CONFIG_NAMES if is_step(f, c)]
             s = "AB"[(nd + nf) % 2]
-            dset = "B" if d[0] == "join_split" else "BA"[(nd + nf) % 2]
+            dset = "B" if d[0] in ON_B else "BA"[(nd + nf) % 2]
             out.append((d, dset, (f, valid[(nd + nf) % len(valid)], s), i))
             i += 1
     return out
