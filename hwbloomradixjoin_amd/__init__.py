@@ -25,6 +25,7 @@ __all__ = [
     "Build", "build_keys_device", "BUILD_COUNT", "BUILD_ROWS", "PROBE_MARK_INNER", "PROBE_MARK_S",
     "probe_keys_device", "probe_keys_pairs_device", "semi_probe_keys_device", "outer_probe_keys_device",
     "group_probe_keys_device", "group_minmax_probe_keys_device",
+    "AGG_SUM", "AGG_MINMAX", "group_accum_probe_keys_device",
     "export_filter", "tables_info", "tables_read", "hash_crc", "hash_crapwow", "lib", "LIB_PATH", "shard_range", "write_relation",
 ]
 
@@ -194,7 +195,11 @@ def lib() -> ctypes.CDLL:
                 ("hwbrj_probe_keys_group_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64, vp,
                                                    pst, pdb]),
                 ("hwbrj_probe_keys_group_minmax_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64,
-                                                          vp, pst, pdb])):
+                                                          vp, pst, pdb]),
+                ("hwbrj_probe_keys_group_accum_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, pu64, pu64, vp, pst,
+                                                         pdb]),
+                ("hwbrj_build_group_rows_device", [vp, ctypes.c_int, ctypes.c_int, vp, u64, pu64, pu64, vp, pdb]),
+                ("hwbrj_build_group_reset", [vp, ctypes.c_int])):
             getattr(L, nm).restype = ctypes.c_int
             getattr(L, nm).argtypes = at
         L.hwbrj_set_materialize.restype = None
@@ -1128,6 +1133,7 @@ def group_minmax_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = 
 # ---- prepared builds (include/hwbrj.h "Prepared builds"): build R once, probe it with S batches ----
 BUILD_COUNT, BUILD_ROWS = 0, 1          # include/hwbrj.h HWBRJ_BUILD_COUNT / _ROWS
 PROBE_MARK_INNER, PROBE_MARK_S = 3, 4   # HWBRJ_PROBE_MARK_INNER / _S (outer_probe_keys_device)
+AGG_SUM, AGG_MINMAX = 0, 1              # HWBRJ_AGG_SUM / _MINMAX (the group accumulators' two forms)
 _BI_NAMES = ("nR", "purpose", "mode", "F", "NSUB", "join_key_bits", "device", "bytes", "masked")
 
 
@@ -1200,6 +1206,50 @@ class Build:
 
     def reset_marks(self) -> None:
         _err(lib().hwbrj_build_reset_marks(self._handle()), "hwbrj_build_reset_marks")
+
+    def group_rows(self, agg: int = AGG_SUM, kind: int = GROUP_ALL, capacity: Optional[int] = None, stream=None):
+        """(GroupRows | GroupMinMaxRows, n_pairs, ms): the rows of everything the accumulating probes
+        (group_accum_probe_keys_device) of form agg have folded in since the build or the last
+        reset_group(agg), unordered (hwbrj_build_group_rows_device). GROUP_ALL: every R row, NULL R rows
+        and rows without a partner with the identities; GROUP_MATCHED: the rows with count > 0. The
+        accumulators stay as they are. capacity None: nR rows under GROUP_ALL, else one count-only call
+        first."""
+        import torch
+        h = self._handle()
+        sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+        n, pairs, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
+        minmax = int(agg) == AGG_MINMAX
+
+        def call(out, cap):
+            return lib().hwbrj_build_group_rows_device(h, int(agg), int(kind), out, cap, ctypes.byref(n),
+                                                       ctypes.byref(pairs), sp, ctypes.byref(ms))
+
+        if capacity is None:
+            if int(kind) == GROUP_ALL:
+                capacity = self.info()["nR"]
+            else:
+                rc = call(None, 0)  # count only
+                if rc not in (0, 7):
+                    _err(rc, "hwbrj_build_group_rows_device")
+                capacity = n.value
+        for _ in range(2):
+            raw = (torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=self.device) if minmax else
+                   torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=self.device))
+            rc = call(_ptr(raw), int(capacity))
+            if rc != 7:
+                break
+            capacity = n.value
+        _err(rc, "hwbrj_build_group_rows_device")
+        raw = raw[: n.value]
+        if minmax:
+            rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
+        else:
+            rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
+        return rows, int(pairs.value), ms.value
+
+    def reset_group(self, agg: int = AGG_SUM) -> None:
+        """The accumulators of form agg back to the identity rows (hwbrj_build_group_reset)."""
+        _err(lib().hwbrj_build_group_reset(self._handle(), int(agg)), "hwbrj_build_group_reset")
 
 
 def build_keys_device(Rk, args: Optional[BloomFilterArgs] = None, purpose: int = BUILD_ROWS, r_valid=None,
@@ -1349,6 +1399,24 @@ def group_minmax_probe_keys_device(build: Build, Sk, Sv, kind: int = GROUP_MATCH
                                          capacity, s_valid, sv_valid)
     rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
     return stats, rows, pairs, ms
+
+
+def group_accum_probe_keys_device(build: Build, Sk, Sv, agg: int = AGG_SUM, stream=None, *, s_valid=None,
+                                  sv_valid=None):
+    """(Stats, n_rows, n_pairs, ms): this S batch folded into the build's group accumulators of form
+    agg (hwbrj_probe_keys_group_accum_device; a BUILD_ROWS build). No row is returned: n_rows is the
+    number of R rows with a partner in this batch and n_pairs the batch's pairs, as the GROUP_MATCHED
+    probe of the same batch counts them. Build.group_rows(agg) returns the rows after the last batch.
+    The arguments are group_probe_keys_device's."""
+    vs, vv = _check_valid("s_valid", s_valid, Sk), _check_valid("sv_valid", sv_valid, Sk)
+    h = _check_probe(build, Sk, stream, Sv)
+    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+    n, pairs, st, ms = ctypes.c_uint64(), ctypes.c_uint64(), _Stats(), ctypes.c_double()
+    _err(lib().hwbrj_probe_keys_group_accum_device(h, _ptr(Sk), _vptr(vs), _ptr(Sv), _vptr(vv), Sk.shape[0], int(agg),
+                                                   ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st),
+                                                   ctypes.byref(ms)),
+         "hwbrj_probe_keys_group_accum_device")
+    return _stats(st), int(n.value), int(pairs.value), ms.value
 
 
 def copy_bandwidth(nbytes: int = 4 << 30, reps: int = 5) -> float:

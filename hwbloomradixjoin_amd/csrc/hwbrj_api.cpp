@@ -704,9 +704,7 @@ int hwbrj_build_keys_device(const int32_t* d_Rkeys, const uint8_t* d_Rvalid, uin
     b->rows          = rows;
     const int rc     = e->build(d_Rkeys, d_Rvalid, nR, args, (hipStream_t) stream, b, ms);
     if (rc) {
-        b->r.release();
-        b->marks.release();
-        b->cnt.release();
+        b->release();
         delete b;
         return rc;
     }
@@ -725,9 +723,7 @@ int hwbrj_build_free(hwbrj_build_t* b) {
     if (!b) return 0;
     int rc = 0;
     if (!build_engine(b, &rc)) return rc;
-    b->r.release();
-    b->marks.release();
-    b->cnt.release();
+    b->release();
     delete b;
     return 0;
 }
@@ -885,6 +881,94 @@ int hwbrj_build_reset_marks(hwbrj_build_t* b) {
         return 1;
     }
     return 0;
+}
+
+// ---- group accumulators kept across batches (include/hwbrj.h, "group accumulators") ----
+static_assert(HWBRJ_AGG_SUM == (int) GRP_COUNT_SUM && HWBRJ_AGG_MINMAX == (int) GRP_COUNT_MINMAX, "agg is GroupAgg");
+static int agg_ok(int agg) {
+    if (agg == HWBRJ_AGG_SUM || agg == HWBRJ_AGG_MINMAX) return 0;
+    set_last_error("unknown aggregate form (HWBRJ_AGG_SUM, HWBRJ_AGG_MINMAX)");
+    return 2;
+}
+
+// hwbrj_probe_keys_group_device's checks in its order, then the form's running total; the join is
+// that probe's under HWBRJ_GROUP_MATCHED with the build's accumulators in place of an output.
+int hwbrj_probe_keys_group_accum_device(hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid,
+                                        const int32_t* d_Svals, const uint8_t* d_Svals_valid, uint64_t nS, int agg,
+                                        uint64_t* n_rows, uint64_t* n_pairs, void* stream, hwbrj_stats_t* stats,
+                                        double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = keys_group_ok(nullptr, b->r.nR, d_Skeys, d_Svals, nS)) return rc;
+    if (const int rc = masks_ok(nullptr, b->r.nR, d_Svalid, nS, build_args(b), true, d_Svals_valid)) return rc;
+    if (const int rc = agg_ok(agg)) return rc;
+    if (nS >= (1ull << 32)) {
+        set_last_error("group join: |S| must be below 2^32 rows (32-bit counts)");
+        return 3;
+    }
+    if (b->gacc_ns[agg] + nS >= (1ull << 32)) {  // (all before any device call)
+        set_last_error("group accumulators: " + std::to_string(b->gacc_ns[agg]) + " S rows accumulated since the last reset, and " +
+                       std::to_string(nS) + " more would reach 2^32 (32-bit counts, exact 64-bit sums); read the rows and reset");
+        return 3;
+    }
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    if (!e) return rc;
+    if (!b->gacc[agg].p && (rc = e->group_acc_reset(b, (uint32_t) agg))) return rc;
+    JoinReq req = payload_req(JOIN_GROUP, nullptr, 0, SRC_KEYS, probe_masks(b, d_Svalid, d_Svals_valid));
+    req.agg     = (uint32_t) agg;
+    req.s_val   = d_Svals;
+    req.gacc    = b->gacc[agg].as<uint4>();
+    hwbrj_stats_t st;
+    uint64_t      n = 0;
+    JoinExtras    x;
+    if ((rc = pipeline_or_side_pass(e, JoinIn{nullptr, b->r.nR, d_Skeys, nS, build_args(b), (hipStream_t) stream}, req, &st,
+                                    &n, &x, ms, b)))
+        return rc;
+    b->gacc_ns[agg] += nS;
+    if (n_rows) *n_rows = n;
+    if (n_pairs) *n_pairs = x.pairs;
+    if (stats) *stats = st;
+    return 0;
+}
+
+int hwbrj_build_group_rows_device(hwbrj_build_t* b, int agg, int kind, void* d_out, uint64_t capacity, uint64_t* n_out,
+                                  uint64_t* n_pairs, void* stream, double* ms) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = agg_ok(agg)) return rc;
+    if (kind != HWBRJ_GROUP_MATCHED && kind != HWBRJ_GROUP_ALL) {
+        set_last_error("unknown group join kind (HWBRJ_GROUP_MATCHED, HWBRJ_GROUP_ALL)");
+        return 2;
+    }
+    if (capacity > 0 && !d_out) {
+        set_last_error("d_out must hold capacity rows");
+        return 2;
+    }
+    if (((uintptr_t) d_out & 15u) != 0) {
+        set_last_error("d_out must be 16-byte aligned (a row is written as one 16-byte store)");
+        return 2;
+    }
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    if (!e) return rc;
+    uint64_t n = 0, pairs = 0;
+    if ((rc = e->group_rows(b, (uint32_t) agg, kind == HWBRJ_GROUP_ALL, (uint4*) d_out, capacity, &n, &pairs,
+                            (hipStream_t) stream, ms)))
+        return rc;
+    if (n_out) *n_out = n;
+    if (n_pairs) *n_pairs = pairs;
+    if (n > capacity) {
+        set_last_error("output capacity below the row count (*n_out holds the count)");
+        return 7;
+    }
+    return 0;
+}
+
+int hwbrj_build_group_reset(hwbrj_build_t* b, int agg) {
+    if (const int rc = probe_build_ok(b, true)) return rc;
+    if (const int rc = agg_ok(agg)) return rc;
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    return e ? e->group_acc_reset(b, (uint32_t) agg) : rc;
 }
 
 static int g_materialize = -1;  // -1: from HWBRJ_MATERIALIZE

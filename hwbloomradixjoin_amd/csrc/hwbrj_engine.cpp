@@ -1008,6 +1008,12 @@ int Engine::join_group(const JoinCtx& c, const JobInputs& ji) {
     gp.agg     = q.agg;
     gp.out     = (uint4*) q.out;
     gp.n_pairs = (unsigned long long*) c.result() + 6;  // the pair counter: u64 word 6 of the slot (last_slot_)
+    if (q.gacc) {
+        // the accumulating probe: the same jobs fold into the build's entries and write no row. A NULL
+        // R row is in no partition, so its entry keeps the identity row it was initialised with
+        launch_join_group_acc(GroupAccParams{gp, q.gacc}, c.s.NJ, c.in.stream);
+        return 0;
+    }
     launch_join_group(gp, c.s.NJ, c.in.stream);
     // NULL keys of R are in no partition, so no job saw them: under ALL their identity rows come
     // from here, through the same row counter
@@ -1470,6 +1476,63 @@ int Engine::unmatched(Build* b, uint2* out, uint64_t cap, uint64_t* n, hipStream
     (void) hipEventDestroy(e[0]);
     (void) hipEventDestroy(e[1]);
     return rc;
+}
+
+void Build::release() {
+    r.release();
+    for (DevBuf* d : {&marks, &cnt, &gacc[0], &gacc[1]}) d->release();
+}
+
+// The group accumulators (include/hwbrj.h, "group accumulators"): nR entries of 16 bytes, made at
+// the form's first use, so a build that never accumulates holds what it held without them.
+int Engine::group_acc_reset(Build* b, uint32_t agg) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!b->gacc[agg].ensure(b->r.nR * 16)) {
+        set_last_error("hipMalloc failed (device memory)");
+        return 4;
+    }
+    launch_group_acc_init(b->gacc[agg].as<uint4>(), b->r.nR, agg, own_stream_);
+    HWBRJ_CHECK(hipGetLastError());
+    HWBRJ_CHECK(hipStreamSynchronize(own_stream_));
+    b->gacc_ns[agg] = 0;
+    return 0;
+}
+
+// One pass over the entries, with Engine::unmatched's counters: b->cnt holds {rows, pairs}. A form
+// that has no accumulators yet has matched nothing: under `all` its rows are the identity rows, which
+// k_group_acc_init writes straight to out[0, min(nR, cap)).
+int Engine::group_rows(Build* b, uint32_t agg, bool all, uint4* out, uint64_t cap, uint64_t* n, uint64_t* pairs,
+                       hipStream_t stream, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    const uint4* acc = b->gacc[agg].as<uint4>();
+    hipEvent_t   e[2] = {nullptr, nullptr};
+    HWBRJ_CHECK(hipEventCreate(&e[0]));
+    HWBRJ_CHECK(hipEventCreate(&e[1]));
+    uint64_t res[2] = {0, 0};
+    auto run = [&]() -> int {
+        HWBRJ_CHECK(hipMemsetAsync(b->cnt.p, 0, 16, stream));
+        HWBRJ_CHECK(hipEventRecord(e[0], stream));
+        if (acc) launch_group_acc_rows(acc, b->r.nR, all ? 1u : 0u, out, cap, b->cnt.as<unsigned long long>(), stream);
+        else if (all) launch_group_acc_init(out, std::min<uint64_t>(b->r.nR, cap), agg, stream);
+        HWBRJ_CHECK(hipEventRecord(e[1], stream));
+        HWBRJ_CHECK(hipGetLastError());
+        HWBRJ_CHECK(hipMemcpyAsync(res, b->cnt.p, 16, hipMemcpyDeviceToHost, stream));
+        HWBRJ_CHECK(hipStreamSynchronize(stream));
+        if (ms) {
+            float f = 0;
+            HWBRJ_CHECK(hipEventElapsedTime(&f, e[0], e[1]));
+            *ms = f;
+        }
+        return 0;
+    };
+    const int rc = run();
+    (void) hipEventDestroy(e[0]);
+    (void) hipEventDestroy(e[1]);
+    if (rc) return rc;
+    *n     = acc ? res[0] : all ? b->r.nR : 0;
+    *pairs = res[1];
+    return 0;
 }
 
 int Engine::export_build_filter(const Build& b, uint8_t* host_out, uint64_t nbytes) {

@@ -60,6 +60,9 @@ struct KeyMasks {
 // kind's own emit kernels, through the same row counter.
 // rmark: the marking probes of a prepared build (OUTER, keep_r off): every R row with a partner sets
 // its bit there (k_join_outer_mark), and no R-only row is written.
+// gacc: the accumulating group probe of a prepared build (GROUP, all off): the build's accumulators
+// of form agg, one entry per R row; every R row with a partner folds its count and aggregate into
+// its entry (k_join_group_acc), and no row is written (out and cap are not read).
 enum JoinKind : int { JOIN_COUNT = 0, JOIN_PAIRS, JOIN_SEMI, JOIN_OUTER, JOIN_GROUP };
 struct JoinReq {
     JoinKind    kind = JOIN_COUNT;
@@ -74,6 +77,7 @@ struct JoinReq {
     int         jkind = 0, layout = SRC_TUPLES;
     KeyMasks    masks;
     uint32_t*   rmark = nullptr;  // OUTER on a prepared build: the build's marks (the marking probes)
+    uint4*      gacc  = nullptr;  // GROUP on a prepared build: the build's accumulators (the accumulating probe)
     bool carries_s_payloads() const { return kind != JOIN_COUNT; }
     bool carries_r_payloads() const { return kind == JOIN_PAIRS || kind == JOIN_OUTER || kind == JOIN_GROUP; }
 };
@@ -181,13 +185,20 @@ struct RSide {
 // R's row indices as payloads, and one mark bit per R row (marks; bit i & 31 of dword i >> 5) that
 // the marking probes OR into and Engine::unmatched reads; cnt: its row counter. args: the filter the
 // build was made with (has_args), kept for the probes' stats and export.
+// gacc[agg]: the group accumulators of form agg (GroupAgg), one 16-byte entry per R row in the layout
+// of the form's output row, empty until the first accumulating probe or reset of that form
+// (Engine::group_acc_reset); gacc_ns[agg]: the sum of the nS of the accumulating probes since then or
+// since the last reset, which stays below 2^32 so that 32-bit counts and 64-bit sums stay exact.
 struct Build {
     RSide               r;
     bool                rows = false, has_args = false;
     int                 device = 0;
     bloom_filter_args_t args{};
     DevBuf              marks, cnt;
-    size_t              bytes() const { return r.bytes() + marks.bytes + cnt.bytes; }
+    DevBuf              gacc[2];
+    uint64_t            gacc_ns[2] = {0, 0};
+    size_t              bytes() const { return r.bytes() + marks.bytes + cnt.bytes + gacc[0].bytes + gacc[1].bytes; }
+    void                release();  // every device buffer
 };
 
 class Engine {
@@ -208,6 +219,14 @@ class Engine {
                Build* b, double* ms);
     // {R row, -1} of every R row whose mark is clear (k_null_rows over the marks); *n: all of them
     int  unmatched(Build* b, uint2* out, uint64_t cap, uint64_t* n, hipStream_t stream, double* ms);
+    // The group accumulators of form agg: allocated if they are not yet, set to the identity rows, and
+    // the form's running nS to 0. Synchronous.
+    int  group_acc_reset(Build* b, uint32_t agg);
+    // The rows of the accumulators of form agg (k_group_acc_rows): all nR of them, or those with a
+    // count; *n: all of them, *pairs: the sum of their counts. A form without accumulators is one after
+    // a reset, and is answered without allocating them.
+    int  group_rows(Build* b, uint32_t agg, bool all, uint4* out, uint64_t cap, uint64_t* n, uint64_t* pairs,
+                    hipStream_t stream, double* ms);
     int  export_build_filter(const Build& b, uint8_t* host_out, uint64_t nbytes);
     // Enqueue only, a counting join without masks: wait() then waits for the last enqueued join.
     int  run_async(const JoinIn& in, int jkind = 0, int layout = SRC_TUPLES);

@@ -314,6 +314,25 @@ struct GroupJoinParams {
     unsigned long long* n_pairs;  // zero on entry
 };
 void   launch_join_group(const GroupJoinParams& p, uint32_t jobs, hipStream_t st);
+// The accumulating group probe of a prepared build (k_join_group_acc): k_join_group's job with g.all
+// off, but at the end of a piece no row is written: every R tuple with a count folds its LDS
+// accumulator into acc[R.payload], the build's entry of that R row, which has the row's own layout
+// ({row, count, sum} or {row, count, min, max} as one uint4). g.out and g.m.cap are not read;
+// *g.m.count += the R tuples with a partner in this batch, *g.n_pairs += their counts. The pointer
+// stands behind GroupJoinParams in a type of its own, the argument of that kernel alone (as
+// OuterMarkParams): k_join_group's argument block is what it was.
+struct GroupAccParams {
+    GroupJoinParams g;
+    uint4*          acc;  // [|R|]
+};
+void   launch_join_group_acc(const GroupAccParams& p, uint32_t jobs, hipStream_t st);
+// The accumulators' two streaming passes, the same for both forms since an entry is stored as its
+// row. init: the identity rows {i, 0, 0, 0} (GRP_COUNT_SUM) or {i, 0, INT32_MAX, INT32_MIN}
+// (GRP_COUNT_MINMAX) into rows[0, n). rows: the entries of acc[0, n) (all of them, or those with a
+// count) appended to out, up to cap; res[0] += rows, res[1] += their counts. Neither reads R.
+void   launch_group_acc_init(uint4* rows, uint64_t n, uint32_t agg, hipStream_t st);
+void   launch_group_acc_rows(const uint4* acc, uint64_t n, uint32_t all, uint4* out, uint64_t cap,
+                             unsigned long long* res, hipStream_t st);
 // The group join's rows of R's NULL keys (k_null_group_rows; GROUP_ALL with a bitmap on R's key
 // column): the identity row {i, 0, 0} (GRP_COUNT_SUM) or {i, 0, INT32_MAX, INT32_MIN}
 // (GRP_COUNT_MINMAX) of every row i < n whose bit is clear, appended to out (up to cap) through the row

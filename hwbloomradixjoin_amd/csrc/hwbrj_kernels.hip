@@ -5062,6 +5062,145 @@ void launch_join_group(const GroupJoinParams& p0, uint32_t jobs, hipStream_t st)
     }
 }
 
+// ------------------------------------------------ the accumulating probe of a prepared build
+// k_join_group_acc (GroupAccParams): GroupPolicy<false, AGG>'s LDS state, clear, batch and early
+// returns, and another end(). At the end of a piece the accumulators in LDS are final for this probe;
+// instead of a row, every R tuple with a count folds its accumulator into the build's entry of its R
+// row, acc[R.payload], which is stored as the row it will become: one 16-byte load, the combination
+// (count += c; sum += s as int64, or a signed min and max), one 16-byte store.
+// No global atomic on the entries, and why that is enough: an R tuple lies in exactly one piece of
+// exactly one (q, sub) job ("Group joins": the exactly-once argument), the payload joins
+// run no skew split, so no second workgroup works on that job, and a tuple's payload is its R row, so
+// within one launch exactly one thread touches an entry, once. Launches of one build do not overlap:
+// the accumulating probes are synchronous. An R tuple without a partner in this batch does not touch
+// its entry at all, so a batch costs at most one read-modify-write per matched R row whatever S's
+// skew.
+// The counters: the piece's matched tuples and their counts are summed in LDS (L.obase, which no
+// row uses here, and L.ptot; both zero on entry and between pieces), and one thread adds them to the
+// row counter and the pair counter, one atomic each per piece. No scan, no output range, no row.
+template <uint32_t AGG>
+struct GroupAccPolicy : GroupPolicy<false, AGG> {
+    using Base = GroupPolicy<false, AGG>;
+    uint4* acc;
+
+    __device__ __forceinline__ GroupAccPolicy(const GroupJoinParams& G, uint32_t* smem, JobLds& L, uint4* acc)
+        : Base{G, smem, L}, acc(acc) {}
+
+    template <bool BM, int U, class Index>
+    __device__ __forceinline__ void end(const uint32_t (&rv)[U], const uint32_t (&rp)[U], uint32_t, Index&& index) const {
+        constexpr uint32_t        N  = Base::template N<BM>;
+        const uint32_t*           gc = this->template counts<BM>();
+        const unsigned long long* gs = this->template sums<BM>();
+        JobLds&                   L  = this->L;
+        __syncthreads();  // the piece's accumulators are complete
+        uint32_t           rows = 0;
+        unsigned long long pairs = 0;
+        static_assert(U % 4 == 0, "entries are combined four loads in flight");
+#pragma unroll
+        for (int k0 = 0; k0 < U; k0 += 4) {
+            uint32_t idx[4], c[4];
+            uint4    e[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                idx[j] = rv[k0 + j] != kEmpty ? index(k0 + j) : kEmpty;
+                c[j]   = idx[j] != kEmpty ? gc[idx[j]] : 0u;
+                if (c[j]) e[j] = acc[rp[k0 + j]];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (!c[j]) continue;
+                e[j].y += c[j];
+                if constexpr (AGG == GRP_COUNT_SUM) {
+                    const unsigned long long sm = (((unsigned long long) e[j].w << 32) | e[j].z) + gs[idx[j]];
+                    e[j].z = (uint32_t) sm;
+                    e[j].w = (uint32_t) (sm >> 32);
+                } else {
+                    const int32_t* gm = (const int32_t*) gs;
+                    e[j].z = (uint32_t) min((int32_t) e[j].z, gm[idx[j]]);
+                    e[j].w = (uint32_t) max((int32_t) e[j].w, gm[N + idx[j]]);
+                }
+                acc[rp[k0 + j]] = e[j];
+                rows++;
+                pairs += c[j];
+            }
+        }
+        if (rows) {
+            atomicAdd(&L.obase, (unsigned long long) rows);
+            atomicAdd(&L.ptot, pairs);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 && L.obase) {
+            atomicAdd(this->G.m.count, L.obase);
+            atomicAdd(this->G.n_pairs, L.ptot);
+            L.obase = 0;
+            L.ptot  = 0;
+        }
+    }
+};
+
+template <uint32_t AGG>
+__global__ __launch_bounds__(kMatThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_join_group_acc(GroupAccParams A) {
+    __shared__ __attribute__((aligned(16))) uint32_t smem[kGrpWords];
+    __shared__ JobLds L;
+    if (threadIdx.x == 0) {  // (first added to after a barrier, zero between pieces)
+        L.obase = 0;
+        L.ptot  = 0;
+    }
+    GroupAccPolicy<AGG> pol(A.g, smem, L, A.acc);
+    payload_job(A.g.m, pol, smem, L);
+}
+
+void launch_join_group_acc(const GroupAccParams& p0, uint32_t jobs, hipStream_t st) {
+    GroupAccParams p = p0;
+    p.g.m.j.xcd8     = job_xcd8(jobs, p.g.m.j.log2NSUB);
+    if (p.g.agg == GRP_COUNT_MINMAX) k_join_group_acc<GRP_COUNT_MINMAX><<<jobs, kMatThreads, 0, st>>>(p);
+    else k_join_group_acc<GRP_COUNT_SUM><<<jobs, kMatThreads, 0, st>>>(p);
+}
+
+// The identity rows of n entries, in index order: what HWBRJ_GROUP_ALL writes for a row without a
+// partner. One 16-byte store per entry.
+__global__ __launch_bounds__(256) void k_group_acc_init(uint4* __restrict__ rows, uint64_t n, uint32_t agg) {
+    const bool     mm     = agg == GRP_COUNT_MINMAX;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (uint64_t i = blockIdx.x * (uint64_t) blockDim.x + threadIdx.x; i < n; i += stride)
+        rows[i] = make_uint4((uint32_t) i, 0u, mm ? 0x7FFFFFFFu : 0u, mm ? 0x80000000u : 0u);
+}
+
+// The rows of the entries: k_group_rows' wave-ballot compaction over the entries themselves (an entry
+// is its row; .y is the count): all of them, or those with a count. A wave takes its output range
+// with one atomic and adds its counts to the pair total with it. Does not read R.
+__global__ __launch_bounds__(256) void k_group_acc_rows(const uint4* __restrict__ acc, uint64_t n, uint32_t all,
+                                                         uint4* __restrict__ out, uint64_t cap,
+                                                         unsigned long long* __restrict__ res) {
+    const int      lane   = threadIdx.x & 63;
+    const uint64_t stride = (uint64_t) gridDim.x * blockDim.x;
+    for (uint64_t i0 = blockIdx.x * (uint64_t) blockDim.x; i0 < n; i0 += stride) {  // (wave-uniform trip count)
+        const uint64_t i = i0 + threadIdx.x;
+        const uint4    e = i < n ? acc[i] : make_uint4(0u, 0u, 0u, 0u);
+        const bool     w = i < n && (all || e.y);
+        const uint64_t b = __ballot(w);
+        const uint64_t pairs = wave_sum_u64((uint64_t) e.y);
+        if (b == 0) continue;  // (wave-uniform; no row, so no pair either)
+        unsigned long long base = 0;
+        if (lane == 0) {
+            base = atomicAdd(&res[0], (unsigned long long) __builtin_popcountll(b));
+            if (pairs) atomicAdd(&res[1], (unsigned long long) pairs);
+        }
+        base = __shfl(base, 0, 64);
+        const uint64_t o = base + (uint64_t) __builtin_popcountll(b & ((1ull << lane) - 1ull));
+        if (w && o < cap) out[o] = e;
+    }
+}
+
+void launch_group_acc_init(uint4* rows, uint64_t n, uint32_t agg, hipStream_t st) {
+    if (n) k_group_acc_init<<<kSideGrid, 256, 0, st>>>(rows, n, agg);
+}
+
+void launch_group_acc_rows(const uint4* acc, uint64_t n, uint32_t all, uint4* out, uint64_t cap,
+                           unsigned long long* res, hipStream_t st) {
+    if (n) k_group_acc_rows<<<kSideGrid, 256, 0, st>>>(acc, n, all, out, cap, res);
+}
+
 // ===================================================================== launch wrappers
 void launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                 hipStream_t st) {

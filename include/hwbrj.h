@@ -529,7 +529,7 @@ int hwbrj_join_keys_group_minmax_nulls_device(const int32_t * d_Rkeys, const uin
  * the build's filter: the same bytes as after the one-shot join of the same R and args (5 for a build
  * without a filter, 6 unless nbytes == m / 8).
  * Not offered: tuple relations, async probes, the global-bitmap and basic k >= 2 configurations, the
- * partitioned joins, group accumulators kept across batches (the caller combines the batches' rows). */
+ * partitioned joins. (Group aggregates over all batches: the group accumulators below.) */
 typedef struct hwbrj_build_t hwbrj_build_t; /* opaque; owns its device buffers */
 enum { HWBRJ_BUILD_COUNT = 0, HWBRJ_BUILD_ROWS = 1 };
 enum {
@@ -594,6 +594,51 @@ int hwbrj_probe_keys_group_minmax_device(hwbrj_build_t * build, const int32_t * 
 int hwbrj_build_unmatched_device(hwbrj_build_t * build, tuple_t * d_out, uint64_t capacity, uint64_t * n_out,
                                  void * stream, double * ms /* optional */);
 int hwbrj_build_reset_marks(hwbrj_build_t * build);
+/* Group accumulators kept across batches (a HWBRJ_BUILD_ROWS build; 2 otherwise). The two group
+ * probes above return each batch's partial rows, which the caller must combine per R row. For SELECT
+ * R.row, COUNT, SUM | MIN, MAX ... GROUP BY R row over a streamed S the build keeps the aggregates
+ * itself: one 16-byte entry per R row and form (agg: HWBRJ_AGG_SUM, hwbrj_group_row_t, or
+ * HWBRJ_AGG_MINMAX, hwbrj_group_minmax_row_t), stored as the row it will become and starting at the
+ * identity row HWBRJ_GROUP_ALL writes for a row without a partner ({i, 0, 0}, or {i, 0, INT32_MAX,
+ * INT32_MIN}). The entries of a form are allocated and initialised at its first accumulating probe or
+ * its first hwbrj_build_group_reset: until then the build holds, and HWBRJ_BI_BYTES reports, what it
+ * did without them; afterwards BYTES includes them. The two forms are independent and a build may hold
+ * both. hwbrj_build_free frees them; hwbrj_release, every other entry (the MATCHED / ALL group probes
+ * and the marking probes among them) and other builds leave them alone.
+ *  - hwbrj_probe_keys_group_accum_device folds one S batch into the entries of form agg inside the
+ *    join kernel and writes no row: no output, no capacity. The batch, its bitmaps and the
+ *    participation rule (key bit and value bit both set) are hwbrj_probe_keys_group_device's, and so
+ *    are the refusals and their order (NULL build or wrong purpose 2, alignment 2, d_Svals NULL with
+ *    nS > 0 2, an unknown agg 2, nS >= 2^32 3, another current device 2), all before any device call
+ *    and with nothing written. *n_rows (optional): the R rows with at least one partner in this batch,
+ *    and *n_pairs (optional) the pairs of this batch: *n_out and *n_pairs of the HWBRJ_GROUP_MATCHED
+ *    probe of the same batch, whose stats this probe's are too (matches = *n_rows, the R phases 0).
+ *    Counts are 32 bits and sums 64: the build keeps, per form, the sum of the nS of its accumulating
+ *    probes since the last reset, and a probe that would bring it to 2^32 or more returns 3 before
+ *    any device call and changes nothing (hwbrj_last_error() names the total). nS = 0 is accepted and
+ *    changes no entry. Synchronous; collects pending async joins; hwbrj_tables_* answer 13 afterwards.
+ *    Accumulating probes of one build must not overlap: each is synchronous, and a caller with
+ *    several threads serialises them per build (an entry is updated without atomics).
+ *  - hwbrj_build_group_rows_device writes the rows of everything accumulated since the build or the
+ *    last reset: under HWBRJ_GROUP_ALL all nR entries (a NULL R row carries its identity row, since
+ *    nothing ever matched it), under HWBRJ_GROUP_MATCHED those with count > 0, in no particular order.
+ *    The group join's capacity rule: capacity in rows, *n_out always the full count, 7 above capacity,
+ *    capacity 0 with d_out NULL counts only, d_out 16-byte aligned, an unknown kind or agg 2 without
+ *    writing *n_out. *n_pairs (optional): the sum of the counts. The entries stay as they are, so a
+ *    second call returns the same rows. A form never touched answers as after a reset. R's column is
+ *    not read.
+ *  - hwbrj_build_group_reset restores the identity rows and the form's running nS (NULL build, a
+ *    counting build or an unknown agg: 2). */
+enum { HWBRJ_AGG_SUM = 0, HWBRJ_AGG_MINMAX = 1 };
+int hwbrj_probe_keys_group_accum_device(hwbrj_build_t * build, const int32_t * d_Skeys,
+                                        const uint8_t * d_Svalid, const int32_t * d_Svals,
+                                        const uint8_t * d_Svals_valid, uint64_t nS, int agg,
+                                        uint64_t * n_rows /* optional */, uint64_t * n_pairs /* optional */,
+                                        void * stream, hwbrj_stats_t * stats, double * ms);
+int hwbrj_build_group_rows_device(hwbrj_build_t * build, int agg, int kind, void * d_out, uint64_t capacity,
+                                  uint64_t * n_out, uint64_t * n_pairs /* optional */, void * stream,
+                                  double * ms /* optional */);
+int hwbrj_build_group_reset(hwbrj_build_t * build, int agg);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
