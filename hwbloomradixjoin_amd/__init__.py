@@ -70,6 +70,101 @@ class _Stats(ctypes.Structure):  # include/hwbrj.h hwbrj_stats_t
 JOIN_KEYS_32, JOIN_KEYS_PACKED, JOIN_KEYS_MIXED = 0, 1, 2
 
 
+def _signatures():
+    """What lib() declares: one (entry, restype, argtypes) row per entry; argtypes None leaves them unset.
+    A wrong row corrupts memory silently on the first call: tests/test_bindings_abi.py holds every
+    hwbrj_* row against its prototype in include/hwbrj.h."""
+    P = ctypes.POINTER
+    ci, i32, u32, i64, u64 = ctypes.c_int, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_uint64
+    dbl, vp, cstr = ctypes.c_double, ctypes.c_void_p, ctypes.c_char_p
+    pu64, pdb, pst, pba, prel, pres = P(u64), P(dbl), P(_Stats), P(_BloomArgs), P(_Relation), P(_Result)
+
+    def valid(a):  # the validity-bitmap form: d_Rvalid before nR, d_Svalid before nS
+        return [a[0], vp, a[1], a[2], vp] + a[3:]
+
+    def values(a, masked=False):  # the value column of a group join: d_Svals (and its bitmap) before nS
+        i = 5 if masked else 3
+        return a[:i] + ([vp, vp] if masked else [vp]) + a[i:]
+
+    rel = [vp, u64, vp, u64]                       # d_R, nR, d_S, nS: tuples or key columns
+    out, tail = [vp, u64, pu64], [vp, pst, pdb]    # d_out, capacity, n_out; stream, stats, ms
+    count, enqueue = rel + [pba, ci, vp, pst], rel + [vp, vp]   # (args, algorithm); args, stream
+    pairs, semi = rel + [pba] + out + tail, rel + [pba, ci] + out + tail   # (kind)
+    outer = rel + [pba, ci] + out + [pu64] + tail  # (kind, n_class); the group joins' too (kind, n_pairs)
+    probe, vprobe = [vp, vp, vp, u64], [vp, vp, vp, vp, vp, u64]   # build, d_Skeys, d_Svalid(, d_Svals, its bitmap), nS
+    bpro, pro, from_pk = [prel, prel, ci, pba], [prel, prel, ci], [vp, u64, vp, u64, i64, dbl, u32]
+    return [
+        ("BPRO", pres, bpro), ("BPRH", pres, bpro), ("BPRHO", pres, bpro), ("BRJ", pres, bpro),
+        ("PRO", pres, pro), ("PRH", pres, pro), ("PRHO", pres, pro), ("RJ", pres, pro),
+        ("assert_args", ci, [pba]),
+        ("hwbrj_join_device", ci, rel + [pba, vp, pst]),
+        ("hwbrj_join_device_algo", ci, count),
+        ("hwbrj_join_device_async", ci, enqueue),
+        ("hwbrj_join_wait", ci, [vp]),
+        ("hwbrj_join_wait_all", ci, [vp, ci, P(ci)]),
+        ("hwbrj_set_async_timing", ci, [ci]),
+        ("hwbrj_join_materialize_device", ci, pairs),
+        ("hwbrj_join_semi_device", ci, semi),
+        ("hwbrj_join_outer_device", ci, rel + [pba, ci, i32] + out + [pu64] + tail),   # (null_payload)
+        ("hwbrj_join_group_device", ci, outer),
+        ("hwbrj_join_group_minmax_device", ci, outer),
+        ("hwbrj_join_keys_device", ci, count),
+        ("hwbrj_join_keys_device_async", ci, enqueue),
+        ("hwbrj_join_keys_pairs_device", ci, pairs),
+        ("hwbrj_join_keys_semi_device", ci, semi),
+        ("hwbrj_join_keys_outer_device", ci, outer),
+        ("hwbrj_join_keys_group_device", ci, values(outer)),
+        ("hwbrj_join_keys_group_minmax_device", ci, values(outer)),
+        ("hwbrj_join_keys_nulls_device", ci, valid(count)),
+        ("hwbrj_join_keys_pairs_nulls_device", ci, valid(pairs)),
+        ("hwbrj_join_keys_semi_nulls_device", ci, valid(semi)),
+        ("hwbrj_join_keys_outer_nulls_device", ci, valid(outer)),
+        ("hwbrj_join_keys_group_nulls_device", ci, values(valid(outer), masked=True)),
+        ("hwbrj_join_keys_group_minmax_nulls_device", ci, values(valid(outer), masked=True)),
+        # prepared builds: the build's handle first, then the counterpart's S-side arguments
+        ("hwbrj_build_keys_device", ci, [vp, vp, u64, pba, ci, vp, P(vp), pdb]),
+        ("hwbrj_build_free", ci, [vp]),
+        ("hwbrj_build_info", ci, [vp, pu64, ci]),
+        ("hwbrj_build_export_filter", ci, [vp, vp, u64]),
+        ("hwbrj_build_unmatched_device", ci, [vp] + out + [vp, pdb]),
+        ("hwbrj_build_reset_marks", ci, [vp]),
+        ("hwbrj_probe_keys_device", ci, probe + [ci, vp, pst]),
+        ("hwbrj_probe_keys_pairs_device", ci, probe + out + tail),
+        ("hwbrj_probe_keys_semi_device", ci, probe + [ci] + out + tail),
+        ("hwbrj_probe_keys_outer_device", ci, probe + [ci] + out + [pu64] + tail),
+        ("hwbrj_probe_keys_group_device", ci, vprobe + [ci] + out + [pu64] + tail),
+        ("hwbrj_probe_keys_group_minmax_device", ci, vprobe + [ci] + out + [pu64] + tail),
+        ("hwbrj_probe_keys_group_accum_device", ci, vprobe + [ci, pu64, pu64] + tail),
+        ("hwbrj_build_group_rows_device", ci, [vp, ci, ci] + out + [pu64, vp, pdb]),
+        ("hwbrj_build_group_reset", ci, [vp, ci]),
+        ("hwbrj_set_materialize", None, [ci]),
+        ("hwbrj_set_gpus", ci, [ci]),
+        ("hwbrj_generate_device", ci, [vp, u64, u32, u64, u64, dbl, u64, vp]),
+        ("hwbrj_generate_device_range", ci, [vp, u64, u64, u64, u32, u64, u64, dbl, u64, vp]),
+        ("hwbrj_generate_host", ci, [vp, u64, u32, u64, u64, dbl, u64, ci]),
+        ("hwbrj_nonunique_threshold", u64, [u64, dbl, ci]),
+        ("hwbrj_create_relation_nonunique", ci, [vp, u64, i64, u32]),
+        ("hwbrj_create_relation_nonunique_from_pk", ci, from_pk),
+        ("hwbrj_create_relation_fk_from_pk", ci, from_pk),
+        ("hwbrj_create_relation_zipf", ci, [vp, u64, u64, dbl, u32, ci]),
+        ("hwbrj_create_relation_zipf_device", ci, [vp, u64, u64, dbl, u32, dbl, ci, vp]),
+        ("hwbrj_rand_stream", ci, [u32, vp, u64]),
+        ("hwbrj_write_relation", ci, [prel, cstr]),
+        ("hwbrj_write_result_relation", ci, [vp, cstr]),
+        ("hwbrj_export_filter", ci, [vp, u64]),
+        ("hwbrj_hash_crc", u32, [u32, i32]),
+        ("hwbrj_hash_crapwow", u32, [u32, i32]),
+        ("hwbrj_device_count", ci, None),
+        ("hwbrj_set_device", ci, [ci]),
+        ("hwbrj_last_error", cstr, None),
+        ("hwbrj_version", cstr, None),
+        ("hwbrj_set_test_hook", ci, [ci, i64]),
+        ("hwbrj_tsc_hz", u64, None),
+        ("hwbrj_copy_bandwidth", ci, [u64, ci, pdb]),
+        ("hwbrj_release", None, None),
+    ]
+
+
 _LIB = None
 
 
@@ -89,175 +184,11 @@ def lib() -> ctypes.CDLL:
         except ImportError:
             pass
         L = ctypes.CDLL(LIB_PATH)
-        L.BPRO.restype = ctypes.POINTER(_Result)
-        L.BPRO.argtypes = [ctypes.POINTER(_Relation), ctypes.POINTER(_Relation), ctypes.c_int,
-                           ctypes.POINTER(_BloomArgs)]
-        L.PRO.restype = ctypes.POINTER(_Result)
-        L.PRO.argtypes = [ctypes.POINTER(_Relation), ctypes.POINTER(_Relation), ctypes.c_int]
-        for nm in ("BPRH", "BPRHO", "BRJ"):
-            getattr(L, nm).restype = ctypes.POINTER(_Result)
-            getattr(L, nm).argtypes = L.BPRO.argtypes
-        for nm in ("PRH", "PRHO", "RJ"):
-            getattr(L, nm).restype = ctypes.POINTER(_Result)
-            getattr(L, nm).argtypes = L.PRO.argtypes
-        L.assert_args.argtypes = [ctypes.POINTER(_BloomArgs)]
-        L.hwbrj_join_device.restype = ctypes.c_int
-        L.hwbrj_join_device_async.restype = ctypes.c_int
-        L.hwbrj_join_device_async.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                              ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
-        L.hwbrj_join_device_algo.restype = ctypes.c_int
-        L.hwbrj_join_device_algo.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                             ctypes.c_uint64, ctypes.POINTER(_BloomArgs),
-                                             ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(_Stats)]
-        L.hwbrj_join_keys_device.restype = ctypes.c_int
-        L.hwbrj_join_keys_device.argtypes = L.hwbrj_join_device_algo.argtypes
-        L.hwbrj_join_keys_device_async.restype = ctypes.c_int
-        L.hwbrj_join_keys_device_async.argtypes = L.hwbrj_join_device_async.argtypes
-        L.hwbrj_join_wait.restype = ctypes.c_int
-        L.hwbrj_join_wait.argtypes = [ctypes.c_void_p]
-        L.hwbrj_set_async_timing.restype = ctypes.c_int
-        L.hwbrj_set_async_timing.argtypes = [ctypes.c_int]
-        L.hwbrj_join_wait_all.restype = ctypes.c_int
-        L.hwbrj_join_wait_all.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-        L.hwbrj_join_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
-                                        ctypes.c_uint64, ctypes.POINTER(_BloomArgs),
-                                        ctypes.c_void_p, ctypes.POINTER(_Stats)]
-        L.hwbrj_join_materialize_device.restype = ctypes.c_int
-        L.hwbrj_join_materialize_device.argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(_BloomArgs), ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(_Stats),
-            ctypes.POINTER(ctypes.c_double)]
-        L.hwbrj_join_semi_device.restype = ctypes.c_int
-        L.hwbrj_join_semi_device.argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p, ctypes.POINTER(_Stats),
-            ctypes.POINTER(ctypes.c_double)]
-        L.hwbrj_join_outer_device.restype = ctypes.c_int
-        L.hwbrj_join_outer_device.argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
-            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
-        L.hwbrj_join_keys_pairs_device.restype = ctypes.c_int
-        L.hwbrj_join_keys_pairs_device.argtypes = L.hwbrj_join_materialize_device.argtypes
-        L.hwbrj_join_keys_semi_device.restype = ctypes.c_int
-        L.hwbrj_join_keys_semi_device.argtypes = L.hwbrj_join_semi_device.argtypes
-        L.hwbrj_join_keys_outer_device.restype = ctypes.c_int
-        L.hwbrj_join_keys_outer_device.argtypes = [  # (hwbrj_join_outer_device's without null_payload)
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
-            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
-        # the validity-bitmap forms: the counterpart's arguments with d_Rvalid before nR, d_Svalid before nS
-        def with_valid(argtypes):
-            return [argtypes[0], ctypes.c_void_p, argtypes[1], argtypes[2], ctypes.c_void_p] + list(argtypes[3:])
-        for nm in ("hwbrj_join_keys", "hwbrj_join_keys_pairs", "hwbrj_join_keys_semi", "hwbrj_join_keys_outer"):
-            getattr(L, nm + "_nulls_device").restype = ctypes.c_int
-            getattr(L, nm + "_nulls_device").argtypes = with_valid(getattr(L, nm + "_device").argtypes)
-        L.hwbrj_join_group_device.restype = ctypes.c_int
-        L.hwbrj_join_group_device.argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
-            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
-        L.hwbrj_join_group_minmax_device.restype = ctypes.c_int
-        L.hwbrj_join_group_minmax_device.argtypes = L.hwbrj_join_group_device.argtypes
-        L.hwbrj_join_keys_group_device.restype = ctypes.c_int
-        L.hwbrj_join_keys_group_device.argtypes = [  # (hwbrj_join_group_device's with d_Svals before nS)
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(_BloomArgs), ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64,
-            ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p,
-            ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)]
-        L.hwbrj_join_keys_group_minmax_device.restype = ctypes.c_int
-        L.hwbrj_join_keys_group_minmax_device.argtypes = L.hwbrj_join_keys_group_device.argtypes
-        # (their validity-bitmap forms: d_Rvalid before nR, d_Svalid before d_Svals, d_Svals_valid before nS)
-        g = L.hwbrj_join_keys_group_device.argtypes
-        for nm in ("hwbrj_join_keys_group_nulls_device", "hwbrj_join_keys_group_minmax_nulls_device"):
-            getattr(L, nm).restype = ctypes.c_int
-            getattr(L, nm).argtypes = [g[0], ctypes.c_void_p, g[1], g[2], ctypes.c_void_p, g[3], ctypes.c_void_p] + list(g[4:])
-        # prepared builds: the build's handle first, then the counterpart's S-side arguments
-        vp, u64, pu64 = ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)
-        pst, pdb = ctypes.POINTER(_Stats), ctypes.POINTER(ctypes.c_double)
-        for nm, at in (
-                ("hwbrj_build_keys_device", [vp, vp, u64, ctypes.POINTER(_BloomArgs), ctypes.c_int, vp,
-                                             ctypes.POINTER(vp), pdb]),
-                ("hwbrj_build_free", [vp]),
-                ("hwbrj_build_info", [vp, pu64, ctypes.c_int]),
-                ("hwbrj_build_export_filter", [vp, vp, u64]),
-                ("hwbrj_build_unmatched_device", [vp, vp, u64, pu64, vp, pdb]),
-                ("hwbrj_build_reset_marks", [vp]),
-                ("hwbrj_probe_keys_device", [vp, vp, vp, u64, ctypes.c_int, vp, pst]),
-                ("hwbrj_probe_keys_pairs_device", [vp, vp, vp, u64, vp, u64, pu64, vp, pst, pdb]),
-                ("hwbrj_probe_keys_semi_device", [vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, vp, pst, pdb]),
-                ("hwbrj_probe_keys_outer_device", [vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64, vp, pst, pdb]),
-                ("hwbrj_probe_keys_group_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64, vp,
-                                                   pst, pdb]),
-                ("hwbrj_probe_keys_group_minmax_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, pu64, pu64,
-                                                          vp, pst, pdb]),
-                ("hwbrj_probe_keys_group_accum_device", [vp, vp, vp, vp, vp, u64, ctypes.c_int, pu64, pu64, vp, pst,
-                                                         pdb]),
-                ("hwbrj_build_group_rows_device", [vp, ctypes.c_int, ctypes.c_int, vp, u64, pu64, pu64, vp, pdb]),
-                ("hwbrj_build_group_reset", [vp, ctypes.c_int])):
-            getattr(L, nm).restype = ctypes.c_int
-            getattr(L, nm).argtypes = at
-        L.hwbrj_set_materialize.restype = None
-        L.hwbrj_set_materialize.argtypes = [ctypes.c_int]
-        L.hwbrj_set_gpus.restype = ctypes.c_int
-        L.hwbrj_set_gpus.argtypes = [ctypes.c_int]
-        L.hwbrj_generate_device.restype = ctypes.c_int
-        L.hwbrj_generate_device.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
-                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
-                                            ctypes.c_uint64, ctypes.c_void_p]
-        L.hwbrj_generate_device_range.restype = ctypes.c_int
-        L.hwbrj_generate_device_range.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
-                                                  ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
-                                                  ctypes.c_uint64, ctypes.c_double, ctypes.c_uint64,
-                                                  ctypes.c_void_p]
-        L.hwbrj_generate_host.restype = ctypes.c_int
-        L.hwbrj_generate_host.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
-                                          ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
-                                          ctypes.c_uint64, ctypes.c_int]
-        L.hwbrj_nonunique_threshold.restype = ctypes.c_uint64
-        L.hwbrj_nonunique_threshold.argtypes = [ctypes.c_uint64, ctypes.c_double, ctypes.c_int]
-        L.hwbrj_create_relation_nonunique.restype = ctypes.c_int
-        L.hwbrj_create_relation_nonunique.argtypes = [ctypes.c_void_p, ctypes.c_uint64,
-                                                      ctypes.c_int64, ctypes.c_uint32]
-        for fn in (L.hwbrj_create_relation_nonunique_from_pk, L.hwbrj_create_relation_fk_from_pk):
-            fn.restype = ctypes.c_int
-            fn.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
-                           ctypes.c_int64, ctypes.c_double, ctypes.c_uint32]
-        L.hwbrj_create_relation_zipf.restype = ctypes.c_int
-        L.hwbrj_create_relation_zipf.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
-                                                 ctypes.c_double, ctypes.c_uint32, ctypes.c_int]
-        L.hwbrj_create_relation_zipf_device.restype = ctypes.c_int
-        L.hwbrj_create_relation_zipf_device.argtypes = [
-            ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double, ctypes.c_uint32,
-            ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
-        L.hwbrj_rand_stream.restype = ctypes.c_int
-        L.hwbrj_rand_stream.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64]
-        L.hwbrj_write_relation.restype = ctypes.c_int
-        L.hwbrj_write_relation.argtypes = [ctypes.POINTER(_Relation), ctypes.c_char_p]
-        L.hwbrj_write_result_relation.restype = ctypes.c_int
-        L.hwbrj_write_result_relation.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-        L.hwbrj_export_filter.restype = ctypes.c_int
-        L.hwbrj_export_filter.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
-        L.hwbrj_hash_crc.restype = ctypes.c_uint32
-        L.hwbrj_hash_crc.argtypes = [ctypes.c_uint32, ctypes.c_int32]
-        L.hwbrj_hash_crapwow.restype = ctypes.c_uint32
-        L.hwbrj_hash_crapwow.argtypes = [ctypes.c_uint32, ctypes.c_int32]
-        L.hwbrj_device_count.restype = ctypes.c_int
-        L.hwbrj_set_device.restype = ctypes.c_int
-        L.hwbrj_set_device.argtypes = [ctypes.c_int]
-        L.hwbrj_last_error.restype = ctypes.c_char_p
-        L.hwbrj_version.restype = ctypes.c_char_p
-        L.hwbrj_set_test_hook.restype = ctypes.c_int
-        L.hwbrj_set_test_hook.argtypes = [ctypes.c_int, ctypes.c_int64]
-        L.hwbrj_tsc_hz.restype = ctypes.c_uint64
-        L.hwbrj_copy_bandwidth.restype = ctypes.c_int
-        L.hwbrj_copy_bandwidth.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
-        L.hwbrj_release.restype = None
+        for name, restype, argtypes in _signatures():
+            fn = getattr(L, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
         _LIB = L
     return _LIB
 
@@ -495,6 +426,22 @@ def _ptr(t) -> int:
     return int(t.data_ptr())
 
 
+def _sp(stream):
+    """An entry's stream argument: the caller's torch.cuda.Stream as a pointer; None is the library's own."""
+    return ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
+
+
+def _ap(args: Optional[BloomFilterArgs]):
+    """An entry's filter argument: a pointer to args as a _BloomArgs; None runs without a filter. The
+    byref object owns a reference to the struct it points to, so the struct lives as long as the pointer:
+    a wrapper converts once and hands the same pointer to every call it makes, a retry's included."""
+    return ctypes.byref(args._c()) if args is not None else None
+
+
+def _stats(st) -> Stats:
+    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
+
+
 def _check_rel(R, S):
     """Both relations: contiguous (N, 2) torch.int32 tensors ({key, payload}) on one GPU. The
     library's current HIP device is switched to that GPU (the join runs on its Engine)."""
@@ -513,10 +460,7 @@ def join_device_async(R, S, args: Optional[BloomFilterArgs] = None, stream=None)
     join_wait() returns the Stats of the last join enqueued on this device (counts; an async join
     records no phase events, so its ms_* fields are 0)."""
     _check_rel(R, S)
-    a = args._c() if args is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    _err(lib().hwbrj_join_device_async(_ptr(R), R.shape[0], _ptr(S), S.shape[0],
-                                       ctypes.byref(a) if a is not None else None, sp),
+    _err(lib().hwbrj_join_device_async(_ptr(R), R.shape[0], _ptr(S), S.shape[0], _ap(args), _sp(stream)),
          "hwbrj_join_device_async")
 
 
@@ -524,7 +468,7 @@ def join_wait() -> Stats:
     """Wait for the last enqueued join on this device and return its Stats."""
     st = _Stats()
     _err(lib().hwbrj_join_wait(ctypes.byref(st)), "hwbrj_join_wait")
-    return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
+    return _stats(st)
 
 
 def set_async_timing(on: bool) -> None:
@@ -540,7 +484,7 @@ def join_wait_all(capacity: int = 256) -> list:
     arr = (_Stats * max(1, capacity))()
     n = ctypes.c_int(0)
     _err(lib().hwbrj_join_wait_all(arr, capacity, ctypes.byref(n)), "hwbrj_join_wait_all")
-    return [Stats(**{f: getattr(arr[i], f) for f, _ in _Stats._fields_}) for i in range(n.value)]
+    return [_stats(arr[i]) for i in range(n.value)]
 
 
 ALGO_PRO, ALGO_PRH, ALGO_PRHO = 0, 1, 2  # include/hwbrj.h HWBRJ_ALGO_* (per-partition join)
@@ -554,13 +498,9 @@ def join_device(R, S, args: Optional[BloomFilterArgs] = None, stream=None,
     histogram joins of src/parallel_radix_join_bloom.c:350-555)."""
     _check_rel(R, S)
     st = _Stats()
-    a = args._c() if args is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    rc = lib().hwbrj_join_device_algo(_ptr(R), R.shape[0], _ptr(S), S.shape[0],
-                                      ctypes.byref(a) if a is not None else None, int(algorithm),
-                                      sp, ctypes.byref(st))
-    _err(rc, "hwbrj_join_device_algo")
-    return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
+    _err(lib().hwbrj_join_device_algo(*_rel_head(R, S), _ap(args), int(algorithm), _sp(stream), ctypes.byref(st)),
+         "hwbrj_join_device_algo")
+    return _stats(st)
 
 
 def _check_keys(Rk, Sk, stream, Sv=None):
@@ -638,6 +578,67 @@ def _vptr(valid):
     return _ptr(valid) if valid is not None and valid.numel() else None
 
 
+def _rel_head(R, S):
+    """The leading arguments of a join of tuple relations."""
+    return [_ptr(R), R.shape[0], _ptr(S), S.shape[0]]
+
+
+def _s_side(Sk, vs, Sv, vv):
+    """The S side where bitmaps are taken: S keys, bitmap, a group join's value column and its bitmap, nS."""
+    return [_ptr(Sk), _vptr(vs)] + ([] if Sv is None else [_ptr(Sv), _vptr(vv)]) + [Sk.shape[0]]
+
+
+def _keys_head(entry: str, Rk, vr, Sk, vs, Sv=None, vv=None):
+    """(entry, head) of a join on key columns: its leading arguments (R keys, nR, S keys, a group join's
+    value column, nS) and, when a bitmap was given, the entry's _nulls_ form with each bitmap after its
+    column. vr, vs, vv are what _check_valid returned. The head holds plain addresses: the wrapper keeps
+    vr, vs and vv bound until its last call of the entry has returned (a bool mask was packed into a
+    tensor that nothing else references)."""
+    if vr is None and vs is None and vv is None:
+        return entry, [_ptr(Rk), Rk.shape[0], _ptr(Sk)] + ([] if Sv is None else [_ptr(Sv)]) + [Sk.shape[0]]
+    return entry.replace("_device", "_nulls_device"), [_ptr(Rk), _vptr(vr), Rk.shape[0]] + _s_side(Sk, vs, Sv, vv)
+
+
+def _probe_head(h, Sk, vs, Sv=None, vv=None):
+    """_keys_head's sibling for the probes of the build with handle h, whose entries always take the
+    bitmaps. The keep-alive rule for vs and vv is _keys_head's."""
+    return [h] + _s_side(Sk, vs, Sv, vv)
+
+
+_ROWS, _GROUP, _MINMAX = (2, "int32"), (2, "int64"), (4, "int32")  # row formats: columns, dtype
+
+
+def _rows(entry: str, head, mid, stream, device, fmt, capacity, known=None, extra=(), stats=True):
+    """The protocol of every entry that writes rows: (Stats, rows, ms) of
+    entry(*head, *mid, d_out, capacity, &n, *extra, stream, &stats, &ms); stats=False for an entry
+    without a stats argument (Stats is then None).
+    capacity None is resolved first. known None: by one count-only call (d_out NULL, capacity 0; 0 and 7
+    both leave the count in n). A callable known: by known(), a row count that needs no call (nR under
+    GROUP_ALL). A wrapper that sizes by a counting join resolves capacity itself and passes the number.
+    Then max(capacity, 1) rows of format fmt are allocated on device while capacity itself is passed;
+    code 7 (too small, n = the full count) runs the entry once more at that size, and any other failure
+    raises under the entry's name. rows is the buffer cut to n."""
+    import torch
+    fn = getattr(lib(), entry)
+    n, st, ms = ctypes.c_uint64(), _Stats(), ctypes.c_double()
+    tail = [ctypes.byref(n), *extra, _sp(stream)] + ([ctypes.byref(st)] if stats else []) + [ctypes.byref(ms)]
+    if capacity is None and known is not None:
+        capacity = known()
+    elif capacity is None:
+        rc = fn(*head, *mid, None, 0, *tail)  # count only
+        if rc not in (0, 7):
+            _err(rc, entry)
+        capacity = n.value
+    for _ in range(2):
+        out = torch.empty((max(int(capacity), 1), fmt[0]), dtype=getattr(torch, fmt[1]), device=device)
+        rc = fn(*head, *mid, _ptr(out), int(capacity), *tail)
+        if rc != 7:
+            break
+        capacity = n.value
+    _err(rc, entry)
+    return _stats(st) if stats else None, out[: n.value], ms.value
+
+
 def join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None,
                      algorithm: int = ALGO_PRO, *, r_valid=None, s_valid=None) -> Stats:
     """The counting join of join_device on key columns (hwbrj_join_keys_device): Rk, Sk are
@@ -653,20 +654,10 @@ def join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None
     on the valid rows. Partition-slice filters and no filter only."""
     vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
     _check_keys(Rk, Sk, stream)
+    entry, head = _keys_head("hwbrj_join_keys_device", Rk, vr, Sk, vs)
     st = _Stats()
-    a = args._c() if args is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    if vr is not None or vs is not None:
-        rc = lib().hwbrj_join_keys_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs), Sk.shape[0],
-                                                ctypes.byref(a) if a is not None else None, int(algorithm),
-                                                sp, ctypes.byref(st))
-        _err(rc, "hwbrj_join_keys_nulls_device")
-        return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
-    rc = lib().hwbrj_join_keys_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0],
-                                      ctypes.byref(a) if a is not None else None, int(algorithm),
-                                      sp, ctypes.byref(st))
-    _err(rc, "hwbrj_join_keys_device")
-    return Stats(**{n: getattr(st, n) for n, _ in _Stats._fields_})
+    _err(getattr(lib(), entry)(*head, _ap(args), int(algorithm), _sp(stream), ctypes.byref(st)), entry)
+    return _stats(st)
 
 
 def join_keys_device_async(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None) -> None:
@@ -675,10 +666,7 @@ def join_keys_device_async(Rk, Sk, args: Optional[BloomFilterArgs] = None, strea
     is refused: call .contiguous() first. The stream rule is join_keys_device's: a stream of the
     caller's must already order whatever wrote the columns."""
     _check_keys(Rk, Sk, stream)
-    a = args._c() if args is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    _err(lib().hwbrj_join_keys_device_async(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0],
-                                            ctypes.byref(a) if a is not None else None, sp),
+    _err(lib().hwbrj_join_keys_device_async(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], _ap(args), _sp(stream)),
          "hwbrj_join_keys_device_async")
 
 
@@ -688,26 +676,13 @@ def join_materialize_device(R, S, args: Optional[BloomFilterArgs] = None, stream
     int32 GPU tensor of {R.payload, S.payload} pairs, unordered (JOIN_RESULT_MATERIALIZE); ms is
     the device time of the materializing pipeline. capacity: output rows to allocate (None: sized
     by a counting join first; too small: the pipeline runs again at the exact size)."""
-    import torch
     if capacity is None:
-        capacity = join_device(R, S, args, stream).matches
-    a = args._c() if args is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    for _ in range(2):
-        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=R.device)
-        n = ctypes.c_uint64()
-        st2 = _Stats()
-        ms = ctypes.c_double()
-        rc = lib().hwbrj_join_materialize_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0],
-                                                 ctypes.byref(a) if a is not None else None,
-                                                 _ptr(out), out.shape[0], ctypes.byref(n), sp,
-                                                 ctypes.byref(st2), ctypes.byref(ms))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, "hwbrj_join_materialize_device")
-    stats = Stats(**{f: getattr(st2, f) for f, _ in _Stats._fields_})
-    return stats, out[: n.value], ms.value
+        capacity = join_device(R, S, args, stream).matches  # (checks R and S first, as the else branch does)
+    else:
+        _check_rel(R, S)
+    # (this wrapper has always passed the rows it allocates, so 1 where the others pass a capacity of 0)
+    return _rows("hwbrj_join_materialize_device", _rel_head(R, S), [_ap(args)], stream, R.device, _ROWS,
+                 max(int(capacity), 1))
 
 
 JOIN_SEMI, JOIN_ANTI = 0, 1  # include/hwbrj.h HWBRJ_JOIN_SEMI / HWBRJ_JOIN_ANTI
@@ -721,34 +696,9 @@ def semi_join_device(R, S, args: Optional[BloomFilterArgs] = None, anti: bool = 
     "S-tuples after filter", Stats.matches the row count; ms the device time. capacity: output rows
     to allocate (None: one count-only call first; too small: the pipeline runs again at the exact
     size)."""
-    import torch
     _check_rel(R, S)
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    kind = JOIN_ANTI if anti else JOIN_SEMI
-    n = ctypes.c_uint64()
-    st = _Stats()
-    ms = ctypes.c_double()
-
-    def call(out, cap):
-        return lib().hwbrj_join_semi_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, kind, out, cap,
-                                            ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
-
-    if capacity is None:
-        rc = call(None, 0)  # count only
-        if rc not in (0, 7):
-            _err(rc, "hwbrj_join_semi_device")
-        capacity = n.value
-    for _ in range(2):
-        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=R.device)
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, "hwbrj_join_semi_device")
-    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-    return stats, out[: n.value], ms.value
+    return _rows("hwbrj_join_semi_device", _rel_head(R, S), [_ap(args), JOIN_ANTI if anti else JOIN_SEMI], stream,
+                 R.device, _ROWS, capacity)
 
 
 OUTER_S, OUTER_R, OUTER_FULL = 0, 1, 2  # include/hwbrj.h HWBRJ_OUTER_S / _R / _FULL
@@ -765,49 +715,11 @@ def outer_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = 
     the counting join's "S-tuples after filter", Stats.matches the row count; ms the device time.
     capacity: output rows to allocate (None: one count-only call first; too small: the pipeline runs
     again at the exact size)."""
-    import torch
     _check_rel(R, S)
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n = ctypes.c_uint64()
     cls = (ctypes.c_uint64 * 3)()
-    st = _Stats()
-    ms = ctypes.c_double()
-
-    def call(out, cap):
-        return lib().hwbrj_join_outer_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, int(kind),
-                                             int(null_payload), out, cap, ctypes.byref(n), cls, sp,
-                                             ctypes.byref(st), ctypes.byref(ms))
-
-    if capacity is None:
-        rc = call(None, 0)  # count only
-        if rc not in (0, 7):
-            _err(rc, "hwbrj_join_outer_device")
-        capacity = n.value
-    for _ in range(2):
-        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=R.device)
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, "hwbrj_join_outer_device")
-    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-    return stats, out[: n.value], (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
-
-
-def _rows_out(call, what: str, capacity: int, n, device):
-    """The (n, 2) int32 rows of call(out_ptr, capacity), run again at the exact size when capacity
-    was too small (code 7, n = the full count)."""
-    import torch
-    for _ in range(2):
-        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int32, device=device)
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, what)
-    return out[: n.value]
+    stats, rows, ms = _rows("hwbrj_join_outer_device", _rel_head(R, S), [_ap(args), int(kind), int(null_payload)],
+                            stream, R.device, _ROWS, capacity, extra=[cls])
+    return stats, rows, tuple(int(c) for c in cls), ms
 
 
 def join_keys_pairs_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, stream=None,
@@ -821,28 +733,11 @@ def join_keys_pairs_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, strea
     again at the exact size). r_valid, s_valid: join_keys_device's (hwbrj_join_keys_pairs_nulls_device):
     the pairs of the valid rows, as positions in the caller's columns."""
     vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
-    masked = vr is not None or vs is not None
     _check_keys(Rk, Sk, stream)
     if capacity is None:
         capacity = join_keys_device(Rk, Sk, args, stream, r_valid=vr, s_valid=vs).matches
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n = ctypes.c_uint64()
-    st = _Stats()
-    ms = ctypes.c_double()
-
-    def call(out, cap):
-        if masked:
-            return lib().hwbrj_join_keys_pairs_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs),
-                                                            Sk.shape[0], ap, out, cap, ctypes.byref(n), sp,
-                                                            ctypes.byref(st), ctypes.byref(ms))
-        return lib().hwbrj_join_keys_pairs_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, out, cap,
-                                                  ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
-
-    out = _rows_out(call, "hwbrj_join_keys_pairs_nulls_device" if masked else "hwbrj_join_keys_pairs_device",
-                    capacity, n, Rk.device)
-    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_}), out, ms.value
+    entry, head = _keys_head("hwbrj_join_keys_pairs_device", Rk, vr, Sk, vs)
+    return _rows(entry, head, [_ap(args)], stream, Rk.device, _ROWS, capacity)
 
 
 def semi_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, anti: bool = False, stream=None,
@@ -855,32 +750,9 @@ def semi_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, anti: 
     (hwbrj_join_keys_semi_nulls_device): the valid S rows with a partner among the valid R rows;
     anti=True: every other S row, the NULL ones included (their key field is what the column stores)."""
     vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
-    masked = vr is not None or vs is not None
-    entry = "hwbrj_join_keys_semi_nulls_device" if masked else "hwbrj_join_keys_semi_device"
     _check_keys(Rk, Sk, stream)
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    kind = JOIN_ANTI if anti else JOIN_SEMI
-    n = ctypes.c_uint64()
-    st = _Stats()
-    ms = ctypes.c_double()
-
-    def call(out, cap):
-        if masked:
-            return lib().hwbrj_join_keys_semi_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs),
-                                                           Sk.shape[0], ap, kind, out, cap, ctypes.byref(n), sp,
-                                                           ctypes.byref(st), ctypes.byref(ms))
-        return lib().hwbrj_join_keys_semi_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, kind, out, cap,
-                                                 ctypes.byref(n), sp, ctypes.byref(st), ctypes.byref(ms))
-
-    if capacity is None:
-        rc = call(None, 0)  # count only
-        if rc not in (0, 7):
-            _err(rc, entry)
-        capacity = n.value
-    out = _rows_out(call, entry, capacity, n, Rk.device)
-    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_}), out, ms.value
+    entry, head = _keys_head("hwbrj_join_keys_semi_device", Rk, vr, Sk, vs)
+    return _rows(entry, head, [_ap(args), JOIN_ANTI if anti else JOIN_SEMI], stream, Rk.device, _ROWS, capacity)
 
 
 def outer_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, kind: int = OUTER_S, stream=None,
@@ -894,33 +766,11 @@ def outer_join_keys_device(Rk, Sk, args: Optional[BloomFilterArgs] = None, kind:
     is an S-only row under OUTER_S / OUTER_FULL, a NULL R row an R-only row under OUTER_R / OUTER_FULL,
     counted in their classes."""
     vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
-    masked = vr is not None or vs is not None
-    entry = "hwbrj_join_keys_outer_nulls_device" if masked else "hwbrj_join_keys_outer_device"
     _check_keys(Rk, Sk, stream)
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n = ctypes.c_uint64()
+    entry, head = _keys_head("hwbrj_join_keys_outer_device", Rk, vr, Sk, vs)
     cls = (ctypes.c_uint64 * 3)()
-    st = _Stats()
-    ms = ctypes.c_double()
-
-    def call(out, cap):
-        if masked:
-            return lib().hwbrj_join_keys_outer_nulls_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs),
-                                                            Sk.shape[0], ap, int(kind), out, cap, ctypes.byref(n),
-                                                            cls, sp, ctypes.byref(st), ctypes.byref(ms))
-        return lib().hwbrj_join_keys_outer_device(_ptr(Rk), Rk.shape[0], _ptr(Sk), Sk.shape[0], ap, int(kind), out,
-                                                  cap, ctypes.byref(n), cls, sp, ctypes.byref(st), ctypes.byref(ms))
-
-    if capacity is None:
-        rc = call(None, 0)  # count only
-        if rc not in (0, 7):
-            _err(rc, entry)
-        capacity = n.value
-    out = _rows_out(call, entry, capacity, n, Rk.device)
-    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-    return stats, out, (int(cls[0]), int(cls[1]), int(cls[2])), ms.value
+    stats, rows, ms = _rows(entry, head, [_ap(args), int(kind)], stream, Rk.device, _ROWS, capacity, extra=[cls])
+    return stats, rows, tuple(int(c) for c in cls), ms
 
 
 GROUP_MATCHED, GROUP_ALL = 0, 1  # include/hwbrj.h HWBRJ_GROUP_MATCHED / _ALL
@@ -951,39 +801,9 @@ def group_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind: int = 
     Stats.filtered is the counting join's "S-tuples after filter", Stats.matches the row count; ms the
     device time. capacity: output rows to allocate (None: one count-only call first, or len(R) rows
     under GROUP_ALL without that call; too small: the pipeline runs again at the exact size)."""
-    import torch
     _check_rel(R, S)
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n, pairs = ctypes.c_uint64(), ctypes.c_uint64()
-    st = _Stats()
-    ms = ctypes.c_double()
-
-    def call(out, cap):
-        return lib().hwbrj_join_group_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, int(kind), out, cap,
-                                             ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st),
-                                             ctypes.byref(ms))
-
-    if capacity is None:
-        if int(kind) == GROUP_ALL:
-            capacity = R.shape[0]
-        else:
-            rc = call(None, 0)  # count only
-            if rc not in (0, 7):
-                _err(rc, "hwbrj_join_group_device")
-            capacity = n.value
-    for _ in range(2):
-        out = torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=R.device)
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, "hwbrj_join_group_device")
-    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-    raw = out[: n.value]
-    rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
-    return stats, rows, int(pairs.value), ms.value
+    return _group("hwbrj_join_group_device", False, _rel_head(R, S), [_ap(args)], kind, stream, R.device, capacity,
+                  lambda: R.shape[0])
 
 
 class _GroupMinMaxRow(ctypes.Structure):  # include/hwbrj.h hwbrj_group_minmax_row_t
@@ -1012,86 +832,40 @@ def group_minmax_join_device(R, S, args: Optional[BloomFilterArgs] = None, kind:
     min > max marks an empty group and partial rows over batches of S combine with a plain min and
     max), GROUP_MATCHED only the rows with count > 0. n_pairs, Stats, ms and capacity are
     group_join_device's."""
-    import torch
     _check_rel(R, S)
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n, pairs = ctypes.c_uint64(), ctypes.c_uint64()
-    st = _Stats()
-    ms = ctypes.c_double()
+    return _group("hwbrj_join_group_minmax_device", True, _rel_head(R, S), [_ap(args)], kind, stream, R.device,
+                  capacity, lambda: R.shape[0])
 
-    def call(out, cap):
-        return lib().hwbrj_join_group_minmax_device(_ptr(R), R.shape[0], _ptr(S), S.shape[0], ap, int(kind), out,
-                                                    cap, ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st),
-                                                    ctypes.byref(ms))
 
-    if capacity is None:
-        if int(kind) == GROUP_ALL:
-            capacity = R.shape[0]
-        else:
-            rc = call(None, 0)  # count only
-            if rc not in (0, 7):
-                _err(rc, "hwbrj_join_group_minmax_device")
-            capacity = n.value
-    for _ in range(2):
-        out = torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=R.device)
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, "hwbrj_join_group_minmax_device")
-    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-    raw = out[: n.value]
-    rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
-    return stats, rows, int(pairs.value), ms.value
+def _group_view(raw, minmax: bool):
+    """The GroupRows (GroupMinMaxRows) of a raw buffer of hwbrj_group_row_t (hwbrj_group_minmax_row_t)
+    rows: views of raw, except the zero-extended count."""
+    import torch
+    if minmax:
+        return GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
+    return GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
+
+
+def _group(entry: str, minmax: bool, head, mid, kind, stream, device, capacity, nR, stats=True):
+    """_rows for a group entry, whose kind follows mid and whose n_pairs follows n: (Stats, GroupRows |
+    GroupMinMaxRows, n_pairs, ms). Under GROUP_ALL every R row comes back, so capacity None means nR()
+    rows without a count-only call."""
+    pairs = ctypes.c_uint64()
+    stats, raw, ms = _rows(entry, head, mid + [int(kind)], stream, device, _MINMAX if minmax else _GROUP, capacity,
+                           nR if int(kind) == GROUP_ALL else None, [ctypes.byref(pairs)], stats)
+    return stats, _group_view(raw, minmax), int(pairs.value), ms
 
 
 def _group_keys(entry: str, minmax: bool, Rk, Sk, Sv, args, kind, stream, capacity, r_valid=None, s_valid=None,
                 sv_valid=None):
-    """group_join_keys_device / group_minmax_join_keys_device: (Stats, raw rows, n_pairs, ms) of
+    """group_join_keys_device / group_minmax_join_keys_device: (Stats, rows, n_pairs, ms) of
     `entry`, with the capacity behaviour of the tuple wrappers. With a validity argument the entry is
     its _nulls_ form (hwbrj_join_keys_group_nulls_device / _minmax_nulls_device)."""
-    import torch
     vr, vs = _check_valid("r_valid", r_valid, Rk), _check_valid("s_valid", s_valid, Sk)
     vv = _check_valid("sv_valid", sv_valid, Sk)  # (a value per key: the key column's length)
     _check_keys(Rk, Sk, stream, Sv)
-    masked = vr is not None or vs is not None or vv is not None
-    if masked:
-        entry = entry.replace("_device", "_nulls_device")
-    a = args._c() if args is not None else None
-    ap = ctypes.byref(a) if a is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n, pairs = ctypes.c_uint64(), ctypes.c_uint64()
-    st = _Stats()
-    ms = ctypes.c_double()
-    fn = getattr(lib(), entry)
-
-    def call(out, cap):
-        if masked:
-            return fn(_ptr(Rk), _vptr(vr), Rk.shape[0], _ptr(Sk), _vptr(vs), _ptr(Sv), _vptr(vv), Sk.shape[0], ap,
-                      int(kind), out, cap, ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
-        return fn(_ptr(Rk), Rk.shape[0], _ptr(Sk), _ptr(Sv), Sk.shape[0], ap, int(kind), out, cap, ctypes.byref(n),
-                  ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
-
-    if capacity is None:
-        if int(kind) == GROUP_ALL:
-            capacity = Rk.shape[0]
-        else:
-            rc = call(None, 0)  # count only
-            if rc not in (0, 7):
-                _err(rc, entry)
-            capacity = n.value
-    for _ in range(2):
-        out = (torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=Rk.device) if minmax else
-               torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=Rk.device))
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, entry)
-    stats = Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-    return stats, out[: n.value], int(pairs.value), ms.value
+    entry, head = _keys_head(entry, Rk, vr, Sk, vs, Sv, vv)
+    return _group(entry, minmax, head, [_ap(args)], kind, stream, Rk.device, capacity, lambda: Rk.shape[0])
 
 
 def group_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED, stream=None,
@@ -1108,11 +882,8 @@ def group_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, k
     iff its key and its value are valid: count is COUNT(Sv), sum over the same rows, and n_pairs their
     total. A NULL R row matches nothing and, under GROUP_ALL, still gets its row with count 0.
     r_payload stays the position in the caller's column. Partition-slice filters and no filter only."""
-    import torch
-    stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_device", False, Rk, Sk, Sv, args, kind, stream, capacity,
-                                        r_valid, s_valid, sv_valid)
-    rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
-    return stats, rows, pairs, ms
+    return _group_keys("hwbrj_join_keys_group_device", False, Rk, Sk, Sv, args, kind, stream, capacity, r_valid,
+                       s_valid, sv_valid)
 
 
 def group_minmax_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = None, kind: int = GROUP_MATCHED,
@@ -1123,11 +894,8 @@ def group_minmax_join_keys_device(Rk, Sk, Sv, args: Optional[BloomFilterArgs] = 
     index, min and max over Sv of the S rows with the R row's key, compared as signed int32.
     r_valid, s_valid, sv_valid: group_join_keys_device's (hwbrj_join_keys_group_minmax_nulls_device); a
     row with count 0 carries min = INT32_MAX and max = INT32_MIN."""
-    import torch
-    stats, raw, pairs, ms = _group_keys("hwbrj_join_keys_group_minmax_device", True, Rk, Sk, Sv, args, kind, stream,
-                                        capacity, r_valid, s_valid, sv_valid)
-    rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
-    return stats, rows, pairs, ms
+    return _group_keys("hwbrj_join_keys_group_minmax_device", True, Rk, Sk, Sv, args, kind, stream, capacity, r_valid,
+                       s_valid, sv_valid)
 
 
 # ---- prepared builds (include/hwbrj.h "Prepared builds"): build R once, probe it with S batches ----
@@ -1191,18 +959,8 @@ class Build:
         has matched since the build or the last reset_marks(), NULL R rows included, unordered
         (hwbrj_build_unmatched_device). capacity None: one count-only call first."""
         h = self._handle()
-        sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-        n, ms = ctypes.c_uint64(), ctypes.c_double()
-
-        def call(out, cap):
-            return lib().hwbrj_build_unmatched_device(h, out, cap, ctypes.byref(n), sp, ctypes.byref(ms))
-
-        if capacity is None:
-            rc = call(None, 0)
-            if rc not in (0, 7):
-                _err(rc, "hwbrj_build_unmatched_device")
-            capacity = n.value
-        return _rows_out(call, "hwbrj_build_unmatched_device", capacity, n, self.device), ms.value
+        _, rows, ms = _rows("hwbrj_build_unmatched_device", [h], [], stream, self.device, _ROWS, capacity, stats=False)
+        return rows, ms
 
     def reset_marks(self) -> None:
         _err(lib().hwbrj_build_reset_marks(self._handle()), "hwbrj_build_reset_marks")
@@ -1214,38 +972,10 @@ class Build:
         and rows without a partner with the identities; GROUP_MATCHED: the rows with count > 0. The
         accumulators stay as they are. capacity None: nR rows under GROUP_ALL, else one count-only call
         first."""
-        import torch
         h = self._handle()
-        sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-        n, pairs, ms = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_double()
-        minmax = int(agg) == AGG_MINMAX
-
-        def call(out, cap):
-            return lib().hwbrj_build_group_rows_device(h, int(agg), int(kind), out, cap, ctypes.byref(n),
-                                                       ctypes.byref(pairs), sp, ctypes.byref(ms))
-
-        if capacity is None:
-            if int(kind) == GROUP_ALL:
-                capacity = self.info()["nR"]
-            else:
-                rc = call(None, 0)  # count only
-                if rc not in (0, 7):
-                    _err(rc, "hwbrj_build_group_rows_device")
-                capacity = n.value
-        for _ in range(2):
-            raw = (torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=self.device) if minmax else
-                   torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=self.device))
-            rc = call(_ptr(raw), int(capacity))
-            if rc != 7:
-                break
-            capacity = n.value
-        _err(rc, "hwbrj_build_group_rows_device")
-        raw = raw[: n.value]
-        if minmax:
-            rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
-        else:
-            rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
-        return rows, int(pairs.value), ms.value
+        _, rows, pairs, ms = _group("hwbrj_build_group_rows_device", int(agg) == AGG_MINMAX, [h], [int(agg)], kind,
+                                    stream, self.device, capacity, lambda: self.info()["nR"], stats=False)
+        return rows, pairs, ms
 
     def reset_group(self, agg: int = AGG_SUM) -> None:
         """The accumulators of form agg back to the identity rows (hwbrj_build_group_reset)."""
@@ -1261,12 +991,9 @@ def build_keys_device(Rk, args: Optional[BloomFilterArgs] = None, purpose: int =
     import torch
     vr = _check_valid("r_valid", r_valid, Rk)
     _check_keys(Rk, torch.empty(0, dtype=torch.int32, device=Rk.device) if isinstance(Rk, torch.Tensor) else Rk, stream)
-    a = args._c() if args is not None else None
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     h, ms = ctypes.c_void_p(), ctypes.c_double()
-    rc = lib().hwbrj_build_keys_device(_ptr(Rk), _vptr(vr), Rk.shape[0], ctypes.byref(a) if a is not None else None,
-                                       int(purpose), sp, ctypes.byref(h), ctypes.byref(ms))
-    _err(rc, "hwbrj_build_keys_device")
+    _err(lib().hwbrj_build_keys_device(_ptr(Rk), _vptr(vr), Rk.shape[0], _ap(args), int(purpose), _sp(stream),
+                                       ctypes.byref(h), ctypes.byref(ms)), "hwbrj_build_keys_device")
     return Build(h.value, Rk.device, ms.value)
 
 
@@ -1282,42 +1009,23 @@ def _check_probe(build, Sk, stream, Sv=None):
     return h
 
 
-def _stats(st) -> Stats:
-    return Stats(**{f: getattr(st, f) for f, _ in _Stats._fields_})
-
-
 def probe_keys_device(build: Build, Sk, stream=None, algorithm: int = ALGO_PRO, *, s_valid=None) -> Stats:
     """join_keys_device of the build's R and this S batch (hwbrj_probe_keys_device; a BUILD_COUNT
     build): the same Stats, the R phases 0."""
     vs = _check_valid("s_valid", s_valid, Sk)
     h = _check_probe(build, Sk, stream)
     st = _Stats()
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    _err(lib().hwbrj_probe_keys_device(h, _ptr(Sk), _vptr(vs), Sk.shape[0], int(algorithm), sp, ctypes.byref(st)),
+    _err(lib().hwbrj_probe_keys_device(*_probe_head(h, Sk, vs), int(algorithm), _sp(stream), ctypes.byref(st)),
          "hwbrj_probe_keys_device")
     return _stats(st)
 
 
-def _probe_rows(entry: str, build, Sk, s_valid, stream, capacity, kind=None, n_class=None, count_first=True):
+def _probe_rows(entry: str, build, Sk, s_valid, stream, capacity, mid=(), extra=()):
     """(Stats, rows, ms) of a probe that returns (n, 2) rows, with the one-shot wrappers' capacity
     behaviour (None: one count-only call first; too small: run again at the exact size)."""
     vs = _check_valid("s_valid", s_valid, Sk)
     h = _check_probe(build, Sk, stream)
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n, st, ms = ctypes.c_uint64(), _Stats(), ctypes.c_double()
-    fn = getattr(lib(), entry)
-
-    def call(out, cap):
-        a = [h, _ptr(Sk), _vptr(vs), Sk.shape[0]] + ([int(kind)] if kind is not None else []) + [out, cap, ctypes.byref(n)]
-        return fn(*(a + ([n_class] if n_class is not None else []) + [sp, ctypes.byref(st), ctypes.byref(ms)]))
-
-    if capacity is None:
-        rc = call(None, 0)  # count only
-        if rc not in (0, 7):
-            _err(rc, entry)
-        capacity = n.value
-    out = _rows_out(call, entry, capacity, n, build.device)
-    return _stats(st), out, ms.value
+    return _rows(entry, _probe_head(h, Sk, vs), mid, stream, build.device, _ROWS, capacity, extra=extra)
 
 
 def probe_keys_pairs_device(build: Build, Sk, stream=None, capacity: Optional[int] = None, *, s_valid=None):
@@ -1331,7 +1039,7 @@ def semi_probe_keys_device(build: Build, Sk, anti: bool = False, stream=None, ca
     """(Stats, rows, ms): semi_join_keys_device of the build's R and this S batch
     (hwbrj_probe_keys_semi_device; a BUILD_ROWS build)."""
     return _probe_rows("hwbrj_probe_keys_semi_device", build, Sk, s_valid, stream, capacity,
-                       kind=JOIN_ANTI if anti else JOIN_SEMI)
+                       mid=[JOIN_ANTI if anti else JOIN_SEMI])
 
 
 def outer_probe_keys_device(build: Build, Sk, kind: int = OUTER_S, stream=None, capacity: Optional[int] = None, *,
@@ -1341,41 +1049,17 @@ def outer_probe_keys_device(build: Build, Sk, kind: int = OUTER_S, stream=None, 
     PROBE_MARK_INNER (the batch's inner pairs) and PROBE_MARK_S (plus its S-only rows): both mark the
     R rows matched, for Build.unmatched_rows() after the last batch, and write no R-only row."""
     cls = (ctypes.c_uint64 * 3)()
-    stats, out, ms = _probe_rows("hwbrj_probe_keys_outer_device", build, Sk, s_valid, stream, capacity, kind=kind,
-                                 n_class=cls)
-    return stats, out, (int(cls[0]), int(cls[1]), int(cls[2])), ms
+    stats, rows, ms = _probe_rows("hwbrj_probe_keys_outer_device", build, Sk, s_valid, stream, capacity,
+                                  mid=[int(kind)], extra=[cls])
+    return stats, rows, tuple(int(c) for c in cls), ms
 
 
 def _group_probe(entry: str, minmax: bool, build, Sk, Sv, kind, stream, capacity, s_valid, sv_valid):
-    """_group_keys for a probe: (Stats, raw rows, n_pairs, ms)."""
-    import torch
+    """_group_keys for a probe: (Stats, rows, n_pairs, ms)."""
     vs, vv = _check_valid("s_valid", s_valid, Sk), _check_valid("sv_valid", sv_valid, Sk)
     h = _check_probe(build, Sk, stream, Sv)
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
-    n, pairs, st, ms = ctypes.c_uint64(), ctypes.c_uint64(), _Stats(), ctypes.c_double()
-    fn = getattr(lib(), entry)
-
-    def call(out, cap):
-        return fn(h, _ptr(Sk), _vptr(vs), _ptr(Sv), _vptr(vv), Sk.shape[0], int(kind), out, cap, ctypes.byref(n),
-                  ctypes.byref(pairs), sp, ctypes.byref(st), ctypes.byref(ms))
-
-    if capacity is None:
-        if int(kind) == GROUP_ALL:
-            capacity = build.info()["nR"]
-        else:
-            rc = call(None, 0)  # count only
-            if rc not in (0, 7):
-                _err(rc, entry)
-            capacity = n.value
-    for _ in range(2):
-        out = (torch.empty((max(int(capacity), 1), 4), dtype=torch.int32, device=build.device) if minmax else
-               torch.empty((max(int(capacity), 1), 2), dtype=torch.int64, device=build.device))
-        rc = call(_ptr(out), int(capacity))
-        if rc != 7:
-            break
-        capacity = n.value
-    _err(rc, entry)
-    return _stats(st), out[: n.value], int(pairs.value), ms.value
+    return _group(entry, minmax, _probe_head(h, Sk, vs, Sv, vv), [], kind, stream, build.device, capacity,
+                  lambda: build.info()["nR"])
 
 
 def group_probe_keys_device(build: Build, Sk, Sv, kind: int = GROUP_MATCHED, stream=None,
@@ -1383,22 +1067,16 @@ def group_probe_keys_device(build: Build, Sk, Sv, kind: int = GROUP_MATCHED, str
     """(Stats, GroupRows, n_pairs, ms): group_join_keys_device of the build's R and this S batch
     (hwbrj_probe_keys_group_device; a BUILD_ROWS build). The rows are this batch's partial
     aggregates: the caller combines the batches' rows per R row."""
-    import torch
-    stats, raw, pairs, ms = _group_probe("hwbrj_probe_keys_group_device", False, build, Sk, Sv, kind, stream, capacity,
-                                         s_valid, sv_valid)
-    rows = GroupRows(raw.view(torch.int32)[:, 0], (raw[:, 0] >> 32) & 0xFFFFFFFF, raw[:, 1], raw)
-    return stats, rows, pairs, ms
+    return _group_probe("hwbrj_probe_keys_group_device", False, build, Sk, Sv, kind, stream, capacity, s_valid,
+                        sv_valid)
 
 
 def group_minmax_probe_keys_device(build: Build, Sk, Sv, kind: int = GROUP_MATCHED, stream=None,
                                    capacity: Optional[int] = None, *, s_valid=None, sv_valid=None):
     """(Stats, GroupMinMaxRows, n_pairs, ms): group_minmax_join_keys_device of the build's R and this
     S batch (hwbrj_probe_keys_group_minmax_device; a BUILD_ROWS build)."""
-    import torch
-    stats, raw, pairs, ms = _group_probe("hwbrj_probe_keys_group_minmax_device", True, build, Sk, Sv, kind, stream,
-                                         capacity, s_valid, sv_valid)
-    rows = GroupMinMaxRows(raw[:, 0], raw[:, 1].to(torch.int64) & 0xFFFFFFFF, raw[:, 2], raw[:, 3], raw)
-    return stats, rows, pairs, ms
+    return _group_probe("hwbrj_probe_keys_group_minmax_device", True, build, Sk, Sv, kind, stream, capacity, s_valid,
+                        sv_valid)
 
 
 def group_accum_probe_keys_device(build: Build, Sk, Sv, agg: int = AGG_SUM, stream=None, *, s_valid=None,
@@ -1410,10 +1088,9 @@ def group_accum_probe_keys_device(build: Build, Sk, Sv, agg: int = AGG_SUM, stre
     The arguments are group_probe_keys_device's."""
     vs, vv = _check_valid("s_valid", s_valid, Sk), _check_valid("sv_valid", sv_valid, Sk)
     h = _check_probe(build, Sk, stream, Sv)
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     n, pairs, st, ms = ctypes.c_uint64(), ctypes.c_uint64(), _Stats(), ctypes.c_double()
-    _err(lib().hwbrj_probe_keys_group_accum_device(h, _ptr(Sk), _vptr(vs), _ptr(Sv), _vptr(vv), Sk.shape[0], int(agg),
-                                                   ctypes.byref(n), ctypes.byref(pairs), sp, ctypes.byref(st),
+    _err(lib().hwbrj_probe_keys_group_accum_device(*_probe_head(h, Sk, vs, Sv, vv), int(agg), ctypes.byref(n),
+                                                   ctypes.byref(pairs), _sp(stream), ctypes.byref(st),
                                                    ctypes.byref(ms)),
          "hwbrj_probe_keys_group_accum_device")
     return _stats(st), int(n.value), int(pairs.value), ms.value
@@ -1431,17 +1108,15 @@ def generate_device(out, nthreads: int, maxid: int, threshold: int, selectivity:
                     seed: int, stream=None) -> None:
     """Fill a (N, 2) int32 GPU tensor with the reference generator's multiset
     (src/generator.c:304-415), seeded permuted order, payload = row index."""
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     _err(lib().hwbrj_generate_device(_ptr(out), out.shape[0], nthreads, maxid, threshold,
-                                     selectivity, seed, sp), "hwbrj_generate_device")
+                                     selectivity, seed, _sp(stream)), "hwbrj_generate_device")
 
 
 def generate_device_range(out, n: int, offset: int, nthreads: int, maxid: int, threshold: int,
                           selectivity: float, seed: int, stream=None) -> None:
     """Rows [offset, offset + out.shape[0]) of the n-row relation generate_device would build."""
-    sp = ctypes.c_void_p(stream.cuda_stream) if stream is not None else None
     _err(lib().hwbrj_generate_device_range(_ptr(out), n, offset, out.shape[0], nthreads, maxid,
-                                           threshold, selectivity, seed, sp),
+                                           threshold, selectivity, seed, _sp(stream)),
          "hwbrj_generate_device_range")
 
 
