@@ -26,6 +26,7 @@ __all__ = [
     "probe_keys_device", "probe_keys_pairs_device", "semi_probe_keys_device", "outer_probe_keys_device",
     "group_probe_keys_device", "group_minmax_probe_keys_device",
     "AGG_SUM", "AGG_MINMAX", "group_accum_probe_keys_device",
+    "filter_keys_device",
     "export_filter", "tables_info", "tables_read", "hash_crc", "hash_crapwow", "lib", "LIB_PATH", "shard_range", "write_relation",
 ]
 
@@ -137,6 +138,7 @@ def _signatures():
         ("hwbrj_probe_keys_group_accum_device", ci, vprobe + [ci, pu64, pu64] + tail),
         ("hwbrj_build_group_rows_device", ci, [vp, ci, ci] + out + [pu64, vp, pdb]),
         ("hwbrj_build_group_reset", ci, [vp, ci]),
+        ("hwbrj_build_filter_keys_device", ci, probe + [vp, pu64, vp, pdb]),   # d_out, n_pass, stream, ms
         ("hwbrj_set_materialize", None, [ci]),
         ("hwbrj_set_gpus", ci, [ci]),
         ("hwbrj_generate_device", ci, [vp, u64, u32, u64, u64, dbl, u64, vp]),
@@ -1094,6 +1096,44 @@ def group_accum_probe_keys_device(build: Build, Sk, Sv, agg: int = AGG_SUM, stre
                                                    ctypes.byref(ms)),
          "hwbrj_probe_keys_group_accum_device")
     return _stats(st), int(n.value), int(pairs.value), ms.value
+
+
+def filter_keys_device(build: Build, Sk, stream=None, *, s_valid=None, out=None):
+    """(bitmap, n_pass, ms): the build's Bloom filter applied to the key column Sk in one streaming
+    pass (hwbrj_build_filter_keys_device; a build of either purpose, made with a filter). bitmap is a
+    torch.uint8 validity bitmap of (len(Sk) + 31) // 32 * 4 bytes on the build's device (pack_validity's
+    padding, the padding bits 0): bit i is set iff row i is valid under s_valid and Sk[i] passes the
+    filter. No false negatives, so it serves as s_valid of any probe of the build without changing its
+    rows; n_pass, its set bits, is what that probe reports as Stats.filtered. out: a contiguous 1-D
+    torch.uint8 tensor on that device of at least that many bytes, starting at a 4-byte boundary,
+    written in place of a new tensor and returned cut to the size; it may be the s_valid tensor itself
+    (a star join ANDs one column's filter after another into one bitmap)."""
+    import torch
+    vs = _check_valid("s_valid", s_valid, Sk)
+    n = Sk.shape[0] if isinstance(Sk, torch.Tensor) and Sk.dim() == 1 else 0
+    nbytes = (n + 31) // 32 * 4
+    # Order: what can be said of s_valid and out alone (type, shape, size for Sk's length, alignment) comes
+    # first, as _check_valid's checks do, so that it needs neither a live build nor a GPU; a bad Sk (n = 0
+    # here) is reported by _check_probe next; out's device is compared last, once the build's is known.
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8:
+            raise ValueError("out must be a torch.uint8 tensor")
+        if out.dim() != 1 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous 1-D tensor")
+        if out.shape[0] < nbytes:
+            raise ValueError(f"out has {out.shape[0]} bytes, {n} keys need {nbytes}")
+        if n and out.data_ptr() % 4:
+            raise ValueError("out must start at a 4-byte boundary")
+    h = _check_probe(build, Sk, stream)
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=build.device)
+    elif out.device != build.device:
+        raise ValueError(f"out is on {out.device} but the build is on {build.device}")
+    n_pass, ms = ctypes.c_uint64(), ctypes.c_double()
+    _err(lib().hwbrj_build_filter_keys_device(h, _ptr(Sk), _vptr(vs), n, _ptr(out) if n else None,
+                                              ctypes.byref(n_pass), _sp(stream), ctypes.byref(ms)),
+         "hwbrj_build_filter_keys_device")
+    return out[:nbytes], int(n_pass.value), ms.value
 
 
 def copy_bandwidth(nbytes: int = 4 << 30, reps: int = 5) -> float:

@@ -760,6 +760,46 @@ int hwbrj_build_export_filter(const hwbrj_build_t* b, uint8_t* host_out, uint64_
     return e ? e->export_build_filter(*b, host_out, nbytes) : rc;
 }
 
+// The build's filter applied to a key column (include/hwbrj.h): every refusal before any device call,
+// in the header's order, with nothing written.
+int hwbrj_build_filter_keys_device(const hwbrj_build_t* b, const int32_t* d_Skeys, const uint8_t* d_Svalid, uint64_t nS,
+                                   uint8_t* d_out, uint64_t* n_pass, void* stream, double* ms) {
+    if (!b) {
+        set_last_error("build is NULL");
+        return 2;
+    }
+    if (!b->has_args) {
+        set_last_error("no filter has been built");
+        return 5;
+    }
+    if (!keys_aligned(nullptr, 0, d_Skeys, nS)) return 2;
+    if (d_Svalid && nS && ((uintptr_t) d_Svalid & 3u)) {
+        set_last_error("validity bitmap of S is not 4-byte aligned (shard a masked column at multiples of 32 rows)");
+        return 2;
+    }
+    if (nS && ((uintptr_t) d_out & 3u)) {
+        set_last_error("d_out is not 4-byte aligned (the bitmap is written as dwords)");
+        return 2;
+    }
+    if (nS && !d_out) {
+        set_last_error("d_out must hold 4 * ceil(nS / 32) bytes");
+        return 2;
+    }
+    if (nS >= (1ull << 32)) {
+        set_last_error("nS must be below 2^32");
+        return 3;
+    }
+    int     rc = 0;
+    Engine* e  = build_engine(b, &rc);
+    if (!e) return rc;
+    if (nS == 0) {
+        if (n_pass) *n_pass = 0;
+        if (ms) *ms = 0;
+        return 0;
+    }
+    return e->filter_keys(*b, d_Skeys, d_Svalid, nS, d_out, n_pass, (hipStream_t) stream, ms);
+}
+
 // What every probe checks first, before any device call: the build and its purpose
 static int probe_build_ok(const hwbrj_build_t* b, bool rows) {
     if (!b) {

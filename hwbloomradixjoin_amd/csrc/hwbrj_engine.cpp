@@ -317,6 +317,7 @@ void Engine::release() {
                       &pjIstart, &pjJobs, &ppoolR, &ppoolS, &rpay, &survpos, &smark, &gcnt, &gsum, &gmin, &gmax, &dense2, &kkcnt, &xcnt_, &pjBsum, &pjBound, &pjWtot, &pjWscan, &pjTab2})
         b->release();
     for (DevBuf& b : xslot_) b.release();
+    fkcnt_.release();
     if (pending_) (void) hipEventSynchronize(ev_[8]);  // (the ring's joins end before it is freed)
     ring_drop();
     jring_.release();
@@ -1546,6 +1547,49 @@ int Engine::export_build_filter(const Build& b, uint8_t* host_out, uint64_t nbyt
         return 6;
     }
     return export_slices(b.r.slices, b.r.g, host_out, nbytes);
+}
+
+// The build's filter as a selection bitmap (include/hwbrj.h hwbrj_build_filter_keys_device): one
+// launch of k_filter_keys between two events, with a counter of the Engine's own (fkcnt_), so nothing
+// a join owns is read or written and a pending join stays pending.
+int Engine::filter_keys(const Build& b, const int32_t* dS, const uint8_t* vS, uint64_t nS, uint8_t* out,
+                        uint64_t* n_pass, hipStream_t stream, double* ms) {
+    HWBRJ_CHECK(hipSetDevice(device_));
+    if (!stream) stream = own_stream_;
+    if (!fkcnt_.ensure(8)) {
+        set_last_error("hipMalloc failed (device memory)");
+        return 4;
+    }
+    hipEvent_t e[2] = {nullptr, nullptr};
+    uint64_t   n    = 0;
+    auto run = [&]() -> int {  // (the events are created inside: a failure of the second still frees the first)
+        HWBRJ_CHECK(hipEventCreate(&e[0]));
+        HWBRJ_CHECK(hipEventCreate(&e[1]));
+        HWBRJ_CHECK(hipMemsetAsync(fkcnt_.p, 0, 8, stream));
+        HWBRJ_CHECK(hipEventRecord(e[0], stream));
+        if (!launch_filter_keys(FilterKeysParams{(const uint32_t*) dS, vS, nS, b.r.g, b.r.slices.as<uint32_t>(), d_tabs_,
+                                                 (uint32_t*) out, fkcnt_.as<unsigned long long>()},
+                                (uint32_t) cus_ * 8, stream)) {
+            set_last_error("the build's filter is not kept in partition slices");
+            return kRcMaskFilter;
+        }
+        HWBRJ_CHECK(hipEventRecord(e[1], stream));
+        HWBRJ_CHECK(hipGetLastError());
+        HWBRJ_CHECK(hipMemcpyAsync(&n, fkcnt_.p, 8, hipMemcpyDeviceToHost, stream));
+        HWBRJ_CHECK(hipStreamSynchronize(stream));
+        if (ms) {
+            float f = 0;
+            HWBRJ_CHECK(hipEventElapsedTime(&f, e[0], e[1]));
+            *ms = f;
+        }
+        return 0;
+    };
+    const int rc = run();
+    for (hipEvent_t ev : e)
+        if (ev) (void) hipEventDestroy(ev);
+    if (rc) return rc;
+    if (n_pass) *n_pass = n;
+    return 0;
 }
 
 // ---- test-only table readback (include/hwbrj.h hwbrj_tables_info / hwbrj_tables_read) ----

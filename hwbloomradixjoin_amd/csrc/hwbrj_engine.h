@@ -228,6 +228,12 @@ class Engine {
     int  group_rows(Build* b, uint32_t agg, bool all, uint4* out, uint64_t cap, uint64_t* n, uint64_t* pairs,
                     hipStream_t stream, double* ms);
     int  export_build_filter(const Build& b, uint8_t* host_out, uint64_t nbytes);
+    // The build's filter applied to a key column (k_filter_keys): the selection bitmap of dS[0, nS) under
+    // vS (or nullptr) into out, *n_pass = its set bits, *ms = the pass's device time. Synchronous. Reads
+    // b's slices and geometry only: no join state, no ring slot, no pending join is touched. The caller
+    // (hwbrj_api.cpp) has checked the arguments; nS > 0 and b has a filter.
+    int  filter_keys(const Build& b, const int32_t* dS, const uint8_t* vS, uint64_t nS, uint8_t* out, uint64_t* n_pass,
+                     hipStream_t stream, double* ms);
     // Enqueue only, a counting join without masks: wait() then waits for the last enqueued join.
     int  run_async(const JoinIn& in, int jkind = 0, int layout = SRC_TUPLES);
     int  wait(hwbrj_stats_t* st);
@@ -372,6 +378,7 @@ class Engine {
     bool         bcast_      = false;
     DevBuf       xslot_[HWBRJ_PJ_NSLOTS], xcnt_;  // the native exchange's buffers
     DevBuf       agree_;                           // status words of the broadcast join's agreement
+    DevBuf       fkcnt_;                           // filter_keys' row counter
     int          device_;
     int          cus_ = 256;
     hipStream_t  own_stream_ = nullptr;

@@ -510,6 +510,23 @@ void   launch_pj_surv_pack(const uint32_t* surv, const uint64_t* region, const u
                            const PjOwn& own = PjOwn{});
 void   launch_export(const uint32_t* slices, const Geometry& g, uint32_t* out, uint64_t nwords,
                      hipStream_t st);
+// A build's filter applied to a key column (k_filter_keys): bit i of out (a validity bitmap of
+// ceil(n / 32) dwords, the bits past n clear) = row i is valid and keys[i] passes the filter of the
+// partition slices (g: MODE_SLICE_BLOCK or MODE_SLICE_BASIC); *count += the set bits. valid: nullptr
+// (every row valid) or ceil(n / 8) bytes, 4-byte aligned, no byte past them read; it may be out
+// itself. keys: 16-byte aligned, n < 2^32. grid: the most workgroups to launch. Returns false, with
+// nothing launched, for a geometry no prepared build has (not MODE_SLICE_BLOCK and not basic k = 1).
+struct FilterKeysParams {
+    const uint32_t*     keys;
+    const uint8_t*      valid;
+    uint64_t            n;
+    Geometry            g;
+    const uint32_t*     slices;
+    const CrcTables*    tabs;
+    uint32_t*           out;
+    unsigned long long* count;
+};
+bool   launch_filter_keys(const FilterKeysParams& p, uint32_t grid, hipStream_t st);
 // a streaming copy of bytes (multiple of 16) from src to dst, grid workgroups of contiguous ranges
 // (hwbrj_copy_bandwidth)
 void   launch_copy_bw(const void* src, void* dst, uint64_t bytes, int grid, hipStream_t st);

@@ -5201,6 +5201,179 @@ void launch_group_acc_rows(const uint4* acc, uint64_t n, uint32_t all, uint4* ou
     if (n) k_group_acc_rows<<<kSideGrid, 256, 0, st>>>(acc, n, all, out, cap, res);
 }
 
+// ========================= K14: a build's filter as a selection bitmap over a key column
+// One streaming pass (FilterKeysParams): no partitioning, no survivors. A tile is 1024 keys: lane t of
+// the workgroup reads keys 4 t .. 4 t + 3 of the tile with one 16-byte buffer load (a tile's own
+// descriptor, so lanes past n read 0 and a column of any size < 2^32 keys is covered), locates each
+// key's bits as mat_filter does, and gathers the word of its first bit. The slices of a build are one
+// array in which slice q's bit sb is bit (q << log2 of the slice stride) + sb: segments are stored
+// back to back, and a padded segment (seg_bits < 128) is its slice's only one. The key loads of U
+// tiles are issued before the first is used, and a tile's four gathers before any is tested; bits
+// 2..k (K1 false) are read only for the keys whose first bit is set, from the block the first gather
+// has brought into the cache. Each lane's four results form a nibble; eight lanes OR theirs into the
+// dword of their 32 rows by DPP (quad_perm, row_half_mirror), and the first of the eight ANDs in the
+// dword of `valid` it loaded before (with the keys: in place it overwrites that dword itself), masks
+// the bits past n and stores it. The last dword of a bitmap whose byte count is no multiple of 4 is put
+// together from its bytes (k_null_rows). Counts: popcount per stored dword, a wave reduction, one
+// atomic per workgroup.
+// BASIC: MODE_SLICE_BASIC (bit b of the filter is bit b >> log2F of slice b & (F - 1); no CRC code, so
+// no tables), else MODE_SLICE_BLOCK (blocked and sectorized). K1: k == 1. A build is never basic with
+// k >= 2 (masks_supported), so that instance does not exist and the launcher refuses its geometry.
+constexpr uint32_t kFkTile = 1024;
+#ifndef HWBRJ_FK_U
+#define HWBRJ_FK_U 4  // tiles in flight at k = 1: 4 U gathers per lane (A/B: 1, 2, 8)
+#endif
+
+__device__ __forceinline__ uint32_t fk_or8(uint32_t v) {  // OR over each group of 8 lanes
+    v |= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0xB1, 0xf, 0xf, false);   // quad_perm:[1,0,3,2]
+    v |= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x4E, 0xf, 0xf, false);   // quad_perm:[2,3,0,1]
+    v |= (uint32_t) __builtin_amdgcn_update_dpp(0, (int) v, 0x141, 0xf, 0xf, false);  // row_half_mirror
+    return v;
+}
+
+template <bool BASIC, bool K1>
+__global__ __launch_bounds__(256) void k_filter_keys(FilterKeysParams P) {
+    static_assert(!BASIC || K1, "basic k >= 2 has no prepared build");
+    constexpr int       U = K1 ? HWBRJ_FK_U : 2;  // tiles whose key loads are in flight together
+    __shared__ uint32_t crc_tab[128];
+    __shared__ uint32_t wcnt[4];
+    const uint32_t      tid = threadIdx.x;
+    if (!BASIC) {
+        load_tab(crc_tab, &P.tabs->fwd[0][0]);
+        __syncthreads();
+    }
+    const Geometry& g        = P.g;
+    const uint32_t  F1       = (1u << g.log2F) - 1u;
+    const uint32_t  l2stride = 5u + (uint32_t) __builtin_ctz(g.nseg * g.seg_words);  // bits between slices
+    const uint32_t  msz = (uint32_t) g.m, bmask = g.B - 1u, secw1 = (1u << g.log2secw) - 1u;
+    const bool      sect = g.variant == VAR_SECTORIZED;
+    const uint32_t* __restrict__ slices = P.slices;
+    const uint64_t  n      = P.n;
+    const uint32_t  ntiles = (uint32_t) ((n + kFkTile - 1) / kFkTile), ndw = (uint32_t) ((n + 31) >> 5);
+    const uint64_t  vbytes = (n + 7) >> 3;
+    const bool      own    = (tid & 7u) == 0;  // the lane that stores the dword of its 8 lanes
+    uint32_t        cnt    = 0;
+    // bit `pos` (block-relative) of step i for the first-bit state (h0 -> s0): sectorize()
+    auto place = [&](uint32_t h, uint32_t s0, uint32_t i) {
+        return sect ? (((s0 + i) & g.nsecmask) << g.log2secw) | (h & secw1) : h;
+    };
+    for (uint32_t t0 = blockIdx.x * U; t0 < ntiles; t0 += gridDim.x * U) {  // (uniform)
+        v4u      kq[U];
+        uint32_t vd[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t t   = t0 + u;
+            const uint64_t e0  = (uint64_t) t * kFkTile;
+            const uint32_t len = __builtin_amdgcn_readfirstlane(t < ntiles ? (uint32_t) (n - e0 < kFkTile ? n - e0 : kFkTile) : 0u);
+            const auto     rs  = buf_rsrc(P.keys + (len ? e0 : 0), len * 4u);
+            if (len == kFkTile) {
+                kq[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16u, 0, HWBRJ_SC_LAUX);
+            } else {  // the column's last tile: every key checked (the scatters' partial round)
+                uint32_t x[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t i = 4u * tid + j;
+                    x[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, i < len ? i * 4u : kOob, 0, 0);
+                }
+                kq[u] = v4u{x[0], x[1], x[2], x[3]};
+            }
+            const uint32_t d = t * 32u + (tid >> 3);
+            uint32_t       v = 0xFFFFFFFFu;
+            if (own && P.valid && d < ndw) {
+                if ((uint64_t) d * 4 + 4 <= vbytes) {
+                    v = ((const uint32_t*) P.valid)[d];
+                } else {
+                    v = 0;
+                    for (uint64_t b = (uint64_t) d * 4; b < vbytes; b++) v |= (uint32_t) P.valid[b] << (8 * (b - (uint64_t) d * 4));
+                }
+            }
+            vd[u] = v;
+        }
+        // first bits: the four locations of a tile, then its four gathers
+        uint32_t gb[U][4], w[U][4];
+        [[maybe_unused]] uint32_t h0[U][4];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t key = j == 0 ? kq[u].x : j == 1 ? kq[u].y : j == 2 ? kq[u].z : kq[u].w;
+                const uint32_t cw  = crapwow(kSeed, key);
+                if (BASIC) {
+                    const uint32_t h = mod_m(cw, msz);
+                    h0[u][j] = h;
+                    gb[u][j] = ((h & F1) << l2stride) + (h >> g.log2F);
+                } else {
+                    const uint32_t code = key_code(crc_tab, key);
+                    const uint32_t h    = cw & bmask;
+                    h0[u][j] = h;
+                    gb[u][j] = ((code & F1) << l2stride) + (((code >> g.log2F) & g.lbmask) << g.log2B) + h;  // (place(h, s0, 0) == h)
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++) w[u][j] = slices[gb[u][j] >> 5];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            uint32_t nib = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) nib |= ((w[u][j] >> (gb[u][j] & 31u)) & 1u) << j;
+            if (!K1 && g.k == 0) nib = 0xFu;  // (no bit to test: contains is true)
+            if (!K1) {  // bits 2..k of the keys still alive (src/bloom_filter.c:73-111's sequence)
+                uint32_t h[4], y[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t key = j == 0 ? kq[u].x : j == 1 ? kq[u].y : j == 2 ? kq[u].z : kq[u].w;
+                    y[j] = (key + kSeed) & bmask;
+                    h[j] = h0[u][j];
+                }
+                for (uint32_t i = 1; i < g.k && nib; i++) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {  // the step after bit i - 1
+                        h[j] = (h[j] + y[j]) & bmask;
+                        y[j] = (y[j] + i) & bmask;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if (!((nib >> j) & 1u)) continue;
+                        // the block's first bit, then bit i's place in it
+                        const uint32_t b = gb[u][j] - h0[u][j] + place(h[j], h0[u][j] >> g.log2secw, i);
+                        if (!((slices[b >> 5] >> (b & 31u)) & 1u)) nib &= ~(1u << j);
+                    }
+                }
+            }
+            const uint32_t v = fk_or8(nib << (4u * (tid & 7u)));
+            const uint32_t d = (t0 + u) * 32u + (tid >> 3);
+            if (own && d < ndw) {
+                const uint64_t left = n - (uint64_t) d * 32;
+                const uint32_t o    = v & vd[u] & (left >= 32 ? 0xFFFFFFFFu : (1u << (uint32_t) left) - 1u);
+                P.out[d] = o;
+                cnt += (uint32_t) __builtin_popcount(o);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+    if ((tid & 63u) == 0) wcnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long s = (unsigned long long) wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        if (s) atomicAdd(P.count, s);
+    }
+}
+
+bool launch_filter_keys(const FilterKeysParams& p, uint32_t grid, hipStream_t st) {
+    const bool basic = p.g.mode == MODE_SLICE_BASIC, k1 = p.g.k == 1;
+    // what a prepared build can hold (masks_supported): anything else has no slices in this layout
+    if (!(p.g.mode == MODE_SLICE_BLOCK || (basic && k1)) || p.g.nseg == 0 || p.g.seg_words == 0) return false;
+    if (!p.n) return true;
+    const uint64_t tiles = (p.n + kFkTile - 1) / kFkTile, per = k1 ? HWBRJ_FK_U : 2;
+    const uint32_t G     = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(grid, (tiles + per - 1) / per));
+    if (basic) k_filter_keys<true, true><<<G, 256, 0, st>>>(p);
+    else if (k1) k_filter_keys<false, true><<<G, 256, 0, st>>>(p);
+    else k_filter_keys<false, false><<<G, 256, 0, st>>>(p);
+    return true;
+}
+
 // ===================================================================== launch wrappers
 void launch_gen(uint2* out, uint64_t offset, uint64_t count, const GenPlan* d_plan, const Perm& perm,
                 hipStream_t st) {

@@ -639,6 +639,42 @@ int hwbrj_build_group_rows_device(hwbrj_build_t * build, int agg, int kind, void
                                   uint64_t * n_out, uint64_t * n_pairs /* optional */, void * stream,
                                   double * ms /* optional */);
 int hwbrj_build_group_reset(hwbrj_build_t * build, int agg);
+/* The build's filter as a selection bitmap over a key column, for a scan that pushes the filter
+ * sideways: one streaming pass over d_Skeys, no partitioning, no survivors, no join. The result is a
+ * validity bitmap in the layout every hwbrj_probe_keys_* entry takes as d_Svalid, and a Bloom filter
+ * has no false negatives, so a probe given it returns the rows it returns without it; bitmaps of
+ * several builds (a star join: one key column of S per dimension) intersect by plain AND.
+ *  - Bit i of d_out (bit i & 7 of byte i >> 3) is set iff row i is valid (d_Svalid NULL, or its bit i
+ *    set) and d_Skeys[i] passes the filter the build made from R's valid keys: the reference's
+ *    contains of the build's variant, m, k, B and seed 42 (src/bloom_filter.c:73-141), false positives
+ *    included. The set rows are exactly the rows stats->filtered of hwbrj_probe_keys_device counts for
+ *    the same build, batch and bitmap; *n_pass (optional) is their number.
+ *  - d_out holds 4 * ceil(nS / 32) bytes and starts at a 4-byte boundary. All of them are written,
+ *    the bits past nS in the last dword as 0, and no byte past them.
+ *  - Of d_Svalid no byte past ceil(nS / 8) is read and bits past nS are ignored; d_Skeys follows the
+ *    key columns' 16-byte rule and no key past nS is read.
+ *  - d_out == d_Svalid is allowed when that buffer has d_out's size: each dword of d_Svalid is read
+ *    by the thread that overwrites it, before its store (a star join ANDs column after column into one
+ *    bitmap this way). Any other overlap of the two is the caller's error.
+ *  - Either purpose serves (HWBRJ_BUILD_COUNT or HWBRJ_BUILD_ROWS), with byte-identical results.
+ *  - Refused in this order, before any device call and with nothing written: build NULL (2, "build is
+ *    NULL"); a build made with args == NULL (5, as hwbrj_build_export_filter); a non-empty key column
+ *    off a 16-byte boundary (2, "align"); a non-NULL d_Svalid off a 4-byte boundary with nS > 0 (2,
+ *    "align"); d_out off a 4-byte boundary with nS > 0 (2, "align"); nS > 0 with d_out NULL (2);
+ *    nS >= 2^32 (3); a current device other than the build's (2).
+ *  - nS = 0 returns 0 with *n_pass = 0 and writes nothing to d_out, which may then be NULL.
+ *  - Synchronous: on return the bitmap is complete. stream NULL: the library's own. *ms (optional):
+ *    the device time of the pass. As every entry of a device's engine it is not thread-safe: calls on
+ *    one device, whatever their streams, share one row counter and must not overlap.
+ *  - Nothing of the join state is read or written: pending async joins stay pending and are collected
+ *    later with their own counts, hwbrj_tables_info, hwbrj_tables_read and hwbrj_export_filter answer
+ *    after it as before it, and the build's marks and accumulators are untouched.
+ * Not offered: tuple relations, an async form, a bit offset, a compacted row-index list, builds
+ * without a filter, the one-shot entries' filter. */
+int hwbrj_build_filter_keys_device(const hwbrj_build_t * build, const int32_t * d_Skeys,
+                                   const uint8_t * d_Svalid, uint64_t nS, uint8_t * d_out,
+                                   uint64_t * n_pass /* optional */, void * stream,
+                                   double * ms /* optional */);
 /* Host BPRO/PRO (and the PRH/PRHO/RJ entries) fill result_t.resultlist with the reference's
  * chained result buffers (src/tuple_buffer.h) when on (default: on iff HWBRJ_MATERIALIZE is set). */
 void hwbrj_set_materialize(int on);
